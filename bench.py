@@ -5,6 +5,18 @@ Metric (BASELINE.json): GB/s of text scanned, bit-exact occurrence count,
 Horspool m=32 on 1 GiB of rand128 per GPU.
 
     python bench.py [--gpus N --steps K --warmup W] [--algo hor --plen 32 --sigma 128 --gib 1]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-sweep]]
+
+A plain run does only what the headline needs: it sets up, warms up, times the
+K steps, writes the last step's output if --dump-outputs is given, and prints
+the result line.  The checks and the side measurements described below (count
+verification, cpu_baseline, the per-pattern spread, the streaming-read probe,
+the per-cell sweep) run with --full only.
+
+--dump-outputs DIR: after the timed steps, DIR/count.npy holds what the last
+timed step computed, the occurrence count of its pattern (float64, shape (1,)).
+The text and the patterns are seeded, so the same arguments give the same
+inputs on every run and two builds can be compared output for output.
 
 One "step" = one search: one pattern (cut from the text at a seeded offset, as
 setOfRandomPatterns does, src/smart.c:148-158) scanned over the whole resident
@@ -24,12 +36,12 @@ K counts are summed with ONE RCCL all-reduce inside the timed region
 ("scaling": "weak").  `--gib 4` gives every GPU the 4 GiB shard of BASELINE
 configs 4-5; `--scaling strong` splits ONE text of --gib GiB over the ranks.
 
-After the timed region every count is checked: against a kernel of a different
+With --full, after the timed region every count is checked: against a kernel of a different
 family (the KMP automaton when the timed plans run on the packed matcher, the
 packed matcher otherwise) for all K patterns and against the real reference
 build / the CPU oracle for the cpu_baseline sample.  A mismatch aborts the run.
 
-At N = 1 a per-cell sweep follows: every cell of BASELINE config 2
+With --full at N = 1 a per-cell sweep follows: every cell of BASELINE config 2
 (HOR/BM/KMP/SO/BNDM/EPSM x m in {4,8,32,256} on the 1 GiB rand128 text), of
 config 3 (SO, BNDM x sigma in {2,4} x m in {2..64} on 1 GiB) and of configs 4 and
 5 at the 4 GiB BASELINE.json states per GPU, each timed with HIP events (the median of 4 rounds of 3 patterns), with the kernel that
@@ -134,10 +146,15 @@ def main():
                     help="weak (the contract's default): --gib per GPU; strong: one text of --gib GiB split over the ranks")
     ap.add_argument("--corpus", default="rand", help="rand (counter-based rand<sigma>) or english "
                     "(tests/golden/english_bible_world192.txt.xz tiled to --gib per GPU, BASELINE config 4)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the per-cell sweep of configs 2 to 5")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also verify the counts and run the cpu_baseline, per-pattern spread, "
+                         "streaming-read probe and (N = 1) per-cell sweep legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output (its occurrence count) to DIR/count.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the per-cell sweep of configs 2 to 5")
     ap.add_argument("--sweep-out", default=os.path.join(ROOT, "bench_sweep.json"),
-                    help="file the sweep's cells are written to (the stdout line carries their summary only)")
+                    help="with --full: file the sweep's cells are written to (the stdout line carries their summary only)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: every rank uses GPU 0 (needs --backend gloo); the numbers mean nothing")
@@ -283,44 +300,50 @@ def main():
         group = {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "distinct_devices": len(set(ids)),
                  "devices": [[e["rank"], e["pci"], e["uuid"][-12:]] for e in everyone]}
 
-    # ---- verification (outside the timed region) -------------------------------
     got = got.numpy().astype(np.uint64)
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step computed: the occurrence count of its pattern (exact in float64 below 2^53)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "count.npy"), got[-1:].astype(np.float64))
     kernel_hist = collections.Counter(plans[j].kernel_name for j in range(W, W + K))
     main_kernel = kernel_hist.most_common(1)[0][0]
-    check = torch.zeros(K, dtype=torch.int64, device="cuda")
-    others = []
-    oplans = []
-    for j in range(K):
-        # a kernel of another family than the one that produced the count
-        # (the packed matcher, the KMP automaton, Shift-Or: the first whose plan for THIS pattern leads elsewhere —
-        # on a binary text EPSM's own plan counts on so_runs too)
-        pl = None
-        for other in ("epsm", "kmp", "so"):
-            if other == algo:
-                continue
-            cand = Plan(other, pats[W + j][1], device=local_rank)
-            if cand.kernel_name != plans[W + j].kernel_name:
-                pl = cand
-                break
-            cand.free()
-        assert pl is not None, (plans[W + j].kernel_name, algo)
-        others.append(other)
-        pl.set_result_buffer(check.data_ptr() + 8 * j, 1)
-        pl.launch(text, slot=0)
-        oplans.append(pl)
-    engine.device_sync(local_rank)
-    all_reduce_counts(check)
-    want = check.cpu().numpy().astype(np.uint64)
-    if not np.array_equal(got, want):
-        raise SystemExit("COUNT MISMATCH %s vs %s: %s != %s" % (algo, sorted(set(others)), got.tolist(), want.tolist()))
     if int(got.min()) < 1:
         raise SystemExit("a planted pattern was not found: %s" % got.tolist())
-    for pl in oplans:
-        pl.free()
 
-    # ---- CPU baseline (rank 0, N=1 only): SMART's own algorithm on host cores ---
+    # ---- verification (--full, outside the timed region) -----------------------
+    others = []
+    if args.full:
+        check = torch.zeros(K, dtype=torch.int64, device="cuda")
+        oplans = []
+        for j in range(K):
+            # a kernel of another family than the one that produced the count
+            # (the packed matcher, the KMP automaton, Shift-Or: the first whose plan for THIS pattern leads elsewhere —
+            # on a binary text EPSM's own plan counts on so_runs too)
+            pl = None
+            for other in ("epsm", "kmp", "so"):
+                if other == algo:
+                    continue
+                cand = Plan(other, pats[W + j][1], device=local_rank)
+                if cand.kernel_name != plans[W + j].kernel_name:
+                    pl = cand
+                    break
+                cand.free()
+            assert pl is not None, (plans[W + j].kernel_name, algo)
+            others.append(other)
+            pl.set_result_buffer(check.data_ptr() + 8 * j, 1)
+            pl.launch(text, slot=0)
+            oplans.append(pl)
+        engine.device_sync(local_rank)
+        all_reduce_counts(check)
+        want = check.cpu().numpy().astype(np.uint64)
+        if not np.array_equal(got, want):
+            raise SystemExit("COUNT MISMATCH %s vs %s: %s != %s" % (algo, sorted(set(others)), got.tolist(), want.tolist()))
+        for pl in oplans:
+            pl.free()
+
+    # ---- CPU baseline (--full, rank 0, N=1 only): SMART's own algorithm on host cores ---
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import pyoracle
         pyoracle.build(ref=False)
         T = text.read(0, local_len)
@@ -363,7 +386,7 @@ def main():
     # per-pattern spread of the kernel time, as SMART reports mean/best/worst/std over a pattern set
     # (smart.c:347-351): a second, untimed pass over the same K plans with one event pair per launch
     spread = None
-    if rank == 0:
+    if args.full and rank == 0:
         for j in range(W, W + K):
             plans[j].launch(text, slot=0, timed=True)
         per = np.array([plans[j].result(0)[1] for j in range(W, W + K)])
@@ -371,13 +394,13 @@ def main():
                   "worst": round(float(per.max()), 4), "std": round(float(per.std()), 4),
                   "note": "ms per pattern, separate pass after the timed region, HIP events per launch"}
 
-    read_probe = engine.probe_read_gbs(text) if rank == 0 else None
+    read_probe = engine.probe_read_gbs(text) if args.full and rank == 0 else None
     for pl in plans:
         pl.free()
 
-    # ---- per-cell sweep of BASELINE configs 2 and 3 (N = 1) ---------------------
+    # ---- per-cell sweep of BASELINE configs 2 and 3 (--full, N = 1) ------------
     sweep = None
-    if rank == 0 and world == 1 and not args.no_sweep and english is None:
+    if args.full and rank == 0 and world == 1 and not args.no_sweep and english is None:
         sweep = run_sweep(text if (args.sigma == 128 and local_len == 1 << 30) else None, local_rank)
     text.free()
 
@@ -416,12 +439,13 @@ def main():
                          "kernel": main_kernel, "kernels_of_the_timed_plans": dict(kernel_hist),
                          "kernel_ms": round(kernel_ms, 4),
                          "bytes_per_launch": bytes_per_launch, "kernel_ms_per_pattern": spread,
-                         "measured_stream_read_GBps": round(read_probe, 1),
-                         "frac_of_measured_stream_read": round(achieved / read_probe, 4)},
+                         "measured_stream_read_GBps": round(read_probe, 1) if read_probe else None,
+                         "frac_of_measured_stream_read": round(achieved / read_probe, 4) if read_probe else None},
             "cpu_baseline": cpu,
             "rccl": group,  # N > 1: the live group — backend, world size, every rank's device (PCI id, uuid tail)
-            "counts_verified": "all %d counts equal a kernel of another family (%s)%s"
-                               % (K, "/".join(sorted(set(others))), " and the CPU sample" if cpu else ""),
+            "counts_verified": ("all %d counts equal a kernel of another family (%s)%s"
+                                % (K, "/".join(sorted(set(others))), " and the CPU sample" if cpu else "")) if args.full
+                               else "not checked (a plain run; --full checks every count against a kernel of another family)",
         }
         if sweep is not None:
             out["roofline_secondary"] = sweep["roofline_secondary"]

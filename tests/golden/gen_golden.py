@@ -22,6 +22,7 @@ Files written:
                         BASELINE config 4's unit: data/englishTexts as getText loads it through index.txt
                         (smart.c:95-138: bible.txt then world192.txt, 6,520,792 bytes), xz-compressed DATA,
                         and the reference's counts on it for every length of sets.h:25
+  reference_cases.json  the reference's counts on the 1500 seeded cases of test_oracle.py (every algorithm)
 
     python tests/golden/gen_golden.py                 # everything
     python tests/golden/gen_golden.py config5 english_corpus   # only these
@@ -301,11 +302,23 @@ def english_corpus():
         "survey_rows": prefix_rows, "survey_rows_text": "the first 1,048,576 bytes of the same text (SURVEY.md §8c table)"})
 
 
+def reference_cases():
+    """The reference's counts on the seeded cases of tests/test_oracle.py::test_against_reference_builds, which
+    checks the oracle against them where oracle/_ref is not built."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import test_oracle
+    rows = []
+    for sigma, n, m, k, P, T in test_oracle.reference_cases(po):
+        rows.append({"sigma": sigma, "n": n, "m": m, "k": k, "ref": [REF[a].search(P, T) for a in test_oracle.ALGOS]})
+    dump("reference_cases.json", {"cases": "tests/test_oracle.py reference_cases(): numpy default_rng(12345), 1500 draws",
+                                  "algos": list(test_oracle.ALGOS), "rows": rows})
+
+
 if __name__ == "__main__":
     po.build(ref=True)
-    todo = sys.argv[1:] or ["survey", "testc", "fuzz", "deviations", "english", "config5", "english_corpus"]
+    todo = sys.argv[1:] or ["survey", "testc", "fuzz", "deviations", "english", "config5", "english_corpus", "reference_cases"]
     for name, fn in (("survey", survey_vectors), ("testc", testc_cases), ("fuzz", fuzz_vectors),
                      ("deviations", deviations), ("english", english_vectors), ("config5", config5_vectors),
-                     ("english_corpus", english_corpus)):
+                     ("english_corpus", english_corpus), ("reference_cases", reference_cases)):
         if name in todo:
             fn()

@@ -156,6 +156,39 @@ def test_plain_multi_gpu_invocation_launches_its_ranks():
     assert bad.returncode != 0 and "WORLD_SIZE=3" in (bad.stderr + bad.stdout)
 
 
+def test_plain_run_options():
+    """The checks and side measurements sit behind --full; --dump-outputs names the directory of the outputs."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs DIR" in out.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_steps_count(tmp_path, oracle):
+    """A plain run (no --full) times exactly --steps steps and prints the line; --dump-outputs writes the count of
+    the last timed step, which the oracle recounts on the CPU from the same seeded text and pattern."""
+    import subprocess
+    import sys
+    import numpy as np
+    K, W, m, n = 7, 2, 32, 1 << 26
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(K), "--warmup", str(W), "--gib", "0.0625",
+                          "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-3000:])
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) <= bench.LINE_LIMIT
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["warmup"] == W and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GB/s" and d["dtype"] == "u8" and d["higher_is_better"] is True and d["n_gpus"] == 1
+    assert d["cpu_baseline"] is None and "sweep_file" not in d and d["counts_verified"].startswith("not checked")
+    got = np.load(tmp_path / "out" / "count.npy")
+    assert got.dtype == np.float64 and got.shape == (1,)
+    k = bench.splitmix64(bench.PATTERN_SALT + 4096 * (W + K - 1) + m) % (n - m)
+    T = oracle.gen_text(bench.SEED, 128, 0, n)
+    assert got[0] == oracle.search("hor", T[k:k + m], T) >= 1
+
+
 @pytest.mark.gpu
 def test_two_ranks_rehearsed_on_one_gpu():
     """bench.py's multi-rank code on a one-GPU box: two gloo ranks share GPU 0, each holds its shard of a 2 x 64 MiB
@@ -166,7 +199,7 @@ def test_two_ranks_rehearsed_on_one_gpu():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
-                          "--steps", "5", "--warmup", "2", "--gib", "0.0625", "--no-sweep", "--no-cpu"],
+                          "--steps", "5", "--warmup", "2", "--gib", "0.0625", "--full", "--no-sweep", "--no-cpu"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

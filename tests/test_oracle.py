@@ -1,6 +1,6 @@
 """CPU tests: the oracle (this project's restatement) against the golden
-vectors the real reference produced, and — where oracle/_ref is built —
-against the reference itself on fresh random cases."""
+vectors the real reference produced, and against the reference itself on
+seeded random cases (live where oracle/_ref is built, recorded elsewhere)."""
 import hashlib
 
 import numpy as np
@@ -109,13 +109,10 @@ def test_multithread_split_matches_single(oracle):
             assert oracle.search(a, P, T, threads=5) == oracle.search(a, P, T)
 
 
-def test_against_reference_builds(oracle):
-    """Fresh random cases against oracle/_ref (the real reference), when built."""
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference on this host)")
-    ref = {a: oracle.RefAlgo(a) for a in ALGOS}
+def reference_cases(oracle, count=1500):
+    """The seeded random cases of test_against_reference_builds: (sigma, n, m, k, P, T) each."""
     rng = np.random.default_rng(12345)
-    for it in range(1500):
+    for it in range(count):
         sigma = int(rng.choice([2, 4, 8, 128, 256]))
         n = int(rng.integers(16, 3000))
         m = int(rng.integers(1, min(n, 320) + 1))
@@ -124,11 +121,27 @@ def test_against_reference_builds(oracle):
         P = T[k:k + m].copy()
         if it % 3 == 0:
             P[int(rng.integers(0, m))] ^= 1
-        truth = ref["bf"].search(P, T)
-        for a in ALGOS:
+        yield sigma, n, m, k, P, T
+
+
+def test_against_reference_builds(oracle):
+    """Random cases against oracle/_ref (the real reference) where it is built; elsewhere against the
+    reference's counts on the same seeded cases, recorded in reference_cases.json by gen_golden.py."""
+    live = oracle.have_ref()
+    ref = {a: oracle.RefAlgo(a) for a in ALGOS} if live else None
+    rec = load_golden("reference_cases.json")
+    assert rec["algos"] == list(ALGOS) and len(rec["rows"]) == 1500
+    for row, (sigma, n, m, k, P, T) in zip(rec["rows"], reference_cases(oracle)):
+        assert [row["sigma"], row["n"], row["m"], row["k"]] == [sigma, n, m, k]
+        if live:
+            counts = [ref[a].search(P, T) for a in ALGOS]
+            assert counts == row["ref"], (sigma, n, m, k)  # the recording is what the reference returns
+        else:
+            counts = row["ref"]
+        truth = counts[ALGOS.index("bf")]
+        for a, theirs in zip(ALGOS, counts):
             mine = oracle.search(a, P, T)
             assert mine == truth, (a, sigma, n, m, k)
-            theirs = ref[a].search(P, T)
             if m < MIN_M.get(a, 1):  # not applicable
                 assert theirs == -1
                 continue

@@ -12,7 +12,7 @@ step() { echo "== $1"; shift; "$@"; rc=$?; if [ $rc -ne 0 ]; then echo "FAILED r
 rm -f "$OUT/SESSION_FAILED"
 python3 -c "import json; from smart_amd import sources; print(json.dumps(sources.all_unit_shas()))" > "$OUT/kernel_sources.sha256.json"   # what roofline.traffic gets bound to, per kernel family (collect_profiles.py)
 step "pytest -m gpu" bash -c "timeout -k 10 900 python -m pytest tests -m gpu -x -q > '$OUT/pytest_gpu.log' 2>&1; rc=\$?; tail -3 '$OUT/pytest_gpu.log'; exit \$rc"
-step "bench" bash -c "timeout -k 10 900 python bench.py --sweep-out '$OUT/bench_sweep.json' > '$OUT/bench.json' 2> '$OUT/bench.err'; rc=\$?; cut -c1-600 '$OUT/bench.json'; tail -3 '$OUT/bench.err'; exit \$rc"
+step "bench" bash -c "timeout -k 10 900 python bench.py --full --sweep-out '$OUT/bench_sweep.json' > '$OUT/bench.json' 2> '$OUT/bench.err'; rc=\$?; cut -c1-600 '$OUT/bench.json'; tail -3 '$OUT/bench.err'; exit \$rc"
 cd /tmp
 step "rocprofv3 stats" bash -c "timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d '$OUT/prof_stats' -- python3 '$ROOT/bench.py' --steps 20 --warmup 5 --no-cpu --no-sweep > '$OUT/prof_stats.log' 2>&1"
 find "$OUT/prof_stats" -name "*kernel_stats.csv" | head -1 | xargs -r head -8
