@@ -288,6 +288,48 @@ int smartgpu_tune(int key, int value);
  *          13/15/18 HASH3/5/8 shifts[256] followed by the shift after a candidate (hash3.c:36-56)   */
 int smartgpu_build_table(int which, const uint8_t *P, uint32_t m, int32_t *out, uint32_t cap);
 
+/* ---- packed texts: at most four distinct byte values, held as bit planes -------------------------------------
+ * A text of n symbols over k <= 4 distinct byte values, resident in one GPU's HBM as BIT PLANES: plane b holds bit b of
+ * every symbol's code, 32 symbols per dword (symbol i = bit i % 32 of dword i / 32).  Codes are the ranks of the byte
+ * values that occur, ascending; k <= 2 keeps ONE plane, k = 3, 4 two.  The same symbols in an eighth / a quarter of the
+ * bytes of the byte text, counted by planes_scan (smart_amd/csrc/k_planes.hip) — three vector instructions per pattern
+ * symbol for 32 start positions at once.  None of the reference's search() functions reads such a text, so there is no
+ * algorithm id: the contract is the count BY DEFINITION (src/algos/bf.c:25-39), overlapping occurrences counted, for
+ * every 1 <= m <= SMARTGPU_XSIZE; none of the reference's documented deviations applies.
+ * Measured on an MI355X (profiles/packed/RESULTS.md), symbols per second against the byte text's best of SO / BNDM / HOR,
+ * m = 2 .. 4096: 8 Gi symbols of four values 2.9-3.6 x, 1 Gi of four values 2.7-3.9 x, 1 Gi of two values 2.9-6.7 x. */
+typedef struct smartgpu_ptext smartgpu_ptext;
+/* Pure arithmetic, no device: planes (1 or 2) and HBM bytes per plane, pads excluded, for n symbols of `nvalues` distinct
+ * values: 4 * ceil(n / 32).  SMARTGPU_ERR_ARG for nvalues < 1 or > 4.  Either pointer may be NULL. */
+int smartgpu_ptext_layout(uint64_t n, int nvalues, int *planes, uint64_t *plane_bytes);
+/* Packs a resident text ON THE DEVICE (one pass over it, planes_pack).  NULL, and a message that names the number of
+ * values in smartgpu_last_error(), when the text holds more than four distinct values.  The byte text stays valid and
+ * independent. */
+smartgpu_ptext *smartgpu_ptext_pack(const smartgpu_text *t);
+/* host bytes -> packed, through smartgpu_text_upload and the pack kernel; the byte copy is released */
+smartgpu_ptext *smartgpu_ptext_upload(const void *host, uint64_t n, int device);
+void smartgpu_ptext_free(smartgpu_ptext *t);
+uint64_t smartgpu_ptext_length(const smartgpu_ptext *t); /* symbols */
+int smartgpu_ptext_device(const smartgpu_ptext *t);
+int smartgpu_ptext_planes(const smartgpu_ptext *t);      /* 1 or 2 */
+uint64_t smartgpu_ptext_bytes(const smartgpu_ptext *t);  /* HBM bytes of the planes, pads excluded */
+/* returns k, the number of distinct values; values[code] = the byte value of each code, ascending */
+int smartgpu_ptext_symbols(const smartgpu_ptext *t, uint8_t values[4]);
+/* symbols [off, off+len) unpacked to bytes on the host */
+int smartgpu_ptext_read(const smartgpu_ptext *t, uint64_t off, uint64_t len, void *host);
+/* Occurrences of P[0..m) with start s in [off, off+n-m]: the range convention, count width, pre_ms / run_ms meaning and
+ * error codes of smartgpu_search64 (m = 0 or m > SMARTGPU_XSIZE: SMARTGPU_ERR_ARG; m > n: count 0).  A pattern byte the
+ * text does not hold: count 0, no launch.  Not slower than the byte text in any measured cell (rand4 and rand2, m = 2 ..
+ * 4096, profiles/packed/RESULTS.md); texts with long partial matches were not measured for speed. */
+int smartgpu_psearch64(const uint8_t *P, uint32_t m, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                       uint64_t *count, double *pre_ms, double *run_ms);
+/* K patterns of m bytes: K launches back to back on the device's stream, ONE read-back (the shape of
+ * smartgpu_search_batch64 without its one-grid form).  *batch_ms (or NULL): first launch to the counts on the host. */
+int smartgpu_psearch_batch64(const uint8_t *const *P, uint32_t m, uint32_t K, const smartgpu_ptext *text,
+                             uint64_t off, uint64_t n, uint64_t *counts, double *batch_ms);
+/* smartgpu_probe_read_ms on the planes: the streaming-read time of the bytes a packed search reads (the plane roofline) */
+int smartgpu_ptext_probe_read_ms(const smartgpu_ptext *t, int reps, double *ms_per_pass);
+
 #ifdef __cplusplus
 }
 #endif

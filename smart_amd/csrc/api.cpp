@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "planes.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -1726,6 +1727,258 @@ int smartgpu_build_table(int which, const uint8_t* P, uint32_t m, int32_t* out, 
     if (v.size() > cap) { set_error("table needs %zu entries, cap %u", v.size(), cap); return SMARTGPU_ERR_ARG; }
     std::memcpy(out, v.data(), v.size() * sizeof(int32_t));
     return static_cast<int>(v.size());
+}
+
+}  // extern "C"
+
+/* ---- packed texts: at most four byte values as bit planes (planes.hpp, k_planes.hip) ------------------------------ */
+struct smartgpu_ptext {
+    int device = 0;
+    uint64_t n = 0;            // symbols
+    int planes = 1;            // 1: at most two values, 2: three or four
+    int nvalues = 0;
+    uint8_t values[4] = {0, 0, 0, 0};  // values[code], ascending
+    uint8_t* base = nullptr;   // allocation start; plane b at base + kFrontPad + b * plane_stride(n)
+    uint32_t* plane(int b) const { return reinterpret_cast<uint32_t*>(base + sg::kFrontPad + static_cast<uint64_t>(b) * sg::plane_stride(n)); }
+    uint64_t alloc_bytes() const { return sg::kFrontPad + static_cast<uint64_t>(planes) * sg::plane_stride(n); }
+};
+
+namespace {
+
+// The pattern as planes: X[0][w], X[1][w] = bits 0 / 1 of the codes of symbols 32 w .. 32 w + 31.  false: a pattern byte
+// the text does not hold (no occurrence).
+bool pattern_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint32_t* X0, uint32_t* X1)
+{
+    int code_of[256];
+    for (int c = 0; c < 256; ++c) code_of[c] = -1;
+    for (int k = 0; k < t->nvalues; ++k) code_of[t->values[k]] = k;
+    std::memset(X0, 0, 4 * sg::kPatWords);
+    std::memset(X1, 0, 4 * sg::kPatWords);
+    for (uint32_t j = 0; j < m; ++j) {
+        const int c = code_of[P[j]];
+        if (c < 0) return false;
+        X0[j >> 5] |= static_cast<uint32_t>(c & 1) << (j & 31);
+        X1[j >> 5] |= static_cast<uint32_t>(c >> 1) << (j & 31);
+    }
+    return true;
+}
+
+int check_psearch_args(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n)
+{
+    if (!P || m < 1 || m > SMARTGPU_XSIZE) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return SMARTGPU_ERR_ARG; }
+    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
+    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
+    return SMARTGPU_OK;
+}
+
+// K patterns of m symbols: their planes to the device's arena (m > 32 only: shorter patterns travel as kernel arguments),
+// K launches back to back on the device's stream, ONE read-back.  A pattern with a byte the text does not hold: no launch.
+int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                 uint64_t* counts, double* pre_ms, double* run_ms)
+{
+    DeviceCtx* d = device_ctx(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const double t_pre = now_ms();
+    constexpr size_t kPatBytes = 2 * 4 * sg::kPatWords;  // one pattern's two planes
+    if (static_cast<size_t>(K) * kPatBytes > d->pinned_bytes) { set_error("psearch_batch: %u patterns exceed the staging buffer", K); return SMARTGPU_ERR_ARG; }
+    if (!batch_reserve(d, static_cast<size_t>(K) * kPatBytes, K)) return SMARTGPU_ERR_NOMEM;
+    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
+    uint32_t* host_pat = reinterpret_cast<uint32_t*>(d->pinned);
+    std::vector<uint8_t> present(K, 0);
+    for (uint32_t k = 0; k < K; ++k) {
+        if (!P[k]) { set_error("pattern %u is NULL", k); return SMARTGPU_ERR_ARG; }
+        present[k] = pattern_planes(text, P[k], m, host_pat + 2 * sg::kPatWords * k, host_pat + 2 * sg::kPatWords * k + sg::kPatWords);
+    }
+    const bool fits = n >= m;  // m > n: no window fits, count 0
+    if (m > 32 && fits)
+        HIP_TRY(hipMemcpyAsync(d->arena, host_pat, static_cast<size_t>(K) * kPatBytes, hipMemcpyHostToDevice, d->stream), return SMARTGPU_ERR_HIP);
+    if (pre_ms) *pre_ms = now_ms() - t_pre;
+    const double t0 = now_ms();
+    HIP_TRY(hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream), return SMARTGPU_ERR_HIP);
+    for (uint32_t k = 0; k < K && fits; ++k) {
+        if (!present[k]) continue;
+        sg::PlaneArgs a;
+        a.p0 = text->plane(0);
+        a.p1 = text->plane(text->planes - 1);
+        a.s_begin = off;
+        a.s_end = off + n - m + 1;
+        a.m = m;
+        a.x0 = host_pat[2 * sg::kPatWords * k];
+        a.x1 = host_pat[2 * sg::kPatWords * k + sg::kPatWords];
+        a.pat = reinterpret_cast<const uint32_t*>(d->arena) + 2 * sg::kPatWords * k;
+        a.count = d->batch_counts + k;
+        HIP_TRY(sg::launch_planes_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+    }
+    HIP_TRY(hipMemcpyAsync(d->pinned_counts, d->batch_counts, static_cast<size_t>(K) * 8, hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+    if (run_ms) *run_ms = now_ms() - t0;
+    for (uint32_t k = 0; k < K; ++k) {
+        // more occurrences than start positions: refused like a poisoned count, never reported
+        if (d->pinned_counts[k] > (fits ? n - m + 1 : 0)) { set_error("planes_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[k], (unsigned long long)(fits ? n - m + 1 : 0)); return SMARTGPU_ERR_HIP; }
+        counts[k] = d->pinned_counts[k];
+    }
+    return SMARTGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smartgpu_ptext_layout(uint64_t n, int nvalues, int* planes, uint64_t* plane_bytes)
+{
+    if (nvalues < 1 || nvalues > 4) { set_error("a packed text holds 1 to 4 distinct byte values, not %d", nvalues); return SMARTGPU_ERR_ARG; }
+    if (planes) *planes = nvalues <= 2 ? 1 : 2;
+    if (plane_bytes) *plane_bytes = sg::plane_bytes(n);
+    return SMARTGPU_OK;
+}
+
+smartgpu_ptext* smartgpu_ptext_pack(const smartgpu_text* t)
+{
+    if (!t) { set_error("text handle is NULL"); return nullptr; }
+    uint8_t values[4] = {255, 255, 255, 255};
+    int k = 0;
+    for (int c = 0; c < 256; ++c)
+        if (t->alphabet[c >> 5] >> (c & 31) & 1u) {
+            if (k < 4) values[k] = static_cast<uint8_t>(c);
+            ++k;
+        }
+    if (k > 4) { set_error("the text holds %d distinct byte values: a packed text holds at most 4", k); return nullptr; }
+    DeviceCtx* d = device_ctx(t->device);
+    if (!d) return nullptr;
+    smartgpu_ptext* p = new smartgpu_ptext;
+    p->device = t->device;
+    p->n = t->n;
+    p->planes = k <= 2 ? 1 : 2;
+    p->nvalues = k;
+    for (int i = 0; i < k; ++i) p->values[i] = values[i];
+    if (hipMalloc(reinterpret_cast<void**>(&p->base), p->alloc_bytes()) != hipSuccess) {
+        set_error("hipMalloc of %llu bytes failed", (unsigned long long)p->alloc_bytes());
+        delete p;
+        return nullptr;
+    }
+    const uint8_t above[3] = {values[0], values[1], values[2]};  // code = number of these below the byte (255: none is)
+    hipError_t e = hipMemsetAsync(p->base, 0, p->alloc_bytes(), d->stream);  // pads and tail bits are zero
+    if (e == hipSuccess) e = sg::launch_planes_pack(t->data(), t->n, p->plane(0), p->plane(p->planes - 1), p->planes, above, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e != hipSuccess) {
+        set_error("planes_pack failed: %s", hipGetErrorString(e));
+        smartgpu_ptext_free(p);
+        return nullptr;
+    }
+    return p;
+}
+
+smartgpu_ptext* smartgpu_ptext_upload(const void* host, uint64_t n, int device)
+{
+    smartgpu_text* t = smartgpu_text_upload(host, n, device);
+    if (!t) return nullptr;
+    smartgpu_ptext* p = smartgpu_ptext_pack(t);
+    smartgpu_text_free(t);
+    return p;
+}
+
+void smartgpu_ptext_free(smartgpu_ptext* t)
+{
+    if (!t) return;
+    if (t->base) {
+        hipSetDevice(t->device);
+        hipFree(t->base);
+    }
+    delete t;
+}
+
+uint64_t smartgpu_ptext_length(const smartgpu_ptext* t) { return t ? t->n : 0; }
+int smartgpu_ptext_device(const smartgpu_ptext* t) { return t ? t->device : -1; }
+int smartgpu_ptext_planes(const smartgpu_ptext* t) { return t ? t->planes : 0; }
+uint64_t smartgpu_ptext_bytes(const smartgpu_ptext* t) { return t ? static_cast<uint64_t>(t->planes) * sg::plane_bytes(t->n) : 0; }
+
+int smartgpu_ptext_symbols(const smartgpu_ptext* t, uint8_t values[4])
+{
+    if (!t || !values) { set_error("bad ptext_symbols arguments"); return SMARTGPU_ERR_ARG; }
+    std::memcpy(values, t->values, 4);
+    return t->nvalues;
+}
+
+int smartgpu_ptext_read(const smartgpu_ptext* t, uint64_t off, uint64_t len, void* host)
+{
+    if (!t || (!host && len) || off > t->n || len > t->n - off) { set_error("bad ptext_read range"); return SMARTGPU_ERR_ARG; }
+    if (len == 0) return SMARTGPU_OK;
+    DeviceCtx* d = device_ctx(t->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+    const uint64_t w0 = off / 32, nw = (off + len + 31) / 32 - w0;
+    std::vector<uint32_t> w[2];
+    for (int b = 0; b < t->planes; ++b) {
+        w[b].resize(nw);
+        HIP_TRY(hipMemcpy(w[b].data(), t->plane(b) + w0, nw * 4, hipMemcpyDeviceToHost), return SMARTGPU_ERR_HIP);
+    }
+    uint8_t* out = static_cast<uint8_t*>(host);
+    for (uint64_t i = 0; i < len; ++i) {
+        const uint64_t s = off + i - 32 * w0;
+        uint32_t code = w[0][s >> 5] >> (s & 31) & 1u;
+        if (t->planes == 2) code |= (w[1][s >> 5] >> (s & 31) & 1u) << 1;
+        out[i] = t->values[code];
+    }
+    return SMARTGPU_OK;
+}
+
+int smartgpu_ptext_probe_read_ms(const smartgpu_ptext* t, int reps, double* ms_per_pass)
+{
+    if (!t || reps < 1 || !ms_per_pass) { set_error("bad probe arguments"); return SMARTGPU_ERR_ARG; }
+    DeviceCtx* d = device_ctx(t->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    // the planes and the pad between them: one contiguous region of the allocation
+    const uint8_t* first = reinterpret_cast<const uint8_t*>(t->plane(0));
+    const uint64_t bytes = static_cast<uint64_t>(t->planes - 1) * sg::plane_stride(t->n) + sg::plane_bytes(t->n);
+    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
+    unsigned long long* sink = d->batch_counts;  // probe_read adds to it practically never; every search zeroes its slots first
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipEventCreate(&e1), return SMARTGPU_ERR_HIP);
+    sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);  // warm-up
+    hipEventRecord(e0, d->stream);
+    for (int i = 0; i < reps; ++i) sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);
+    hipEventRecord(e1, d->stream);
+    HIP_TRY(hipEventSynchronize(e1), return SMARTGPU_ERR_HIP);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    *ms_per_pass = ms / reps;
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    return SMARTGPU_OK;
+}
+
+int smartgpu_psearch64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n, uint64_t* count,
+                       double* pre_ms, double* run_ms)
+{
+    const int rc = check_psearch_args(P, m, text, off, n);
+    if (rc != SMARTGPU_OK) return rc;
+    const uint8_t* set[1] = {P};
+    uint64_t c = 0;
+    double pre = 0.0, run = 0.0;
+    const int r = psearch_impl(set, m, 1, text, off, n, &c, &pre, &run);
+    if (r != SMARTGPU_OK) return r;
+    g_last_pre_ms = pre;
+    g_last_run_ms = run;
+    if (count) *count = c;
+    if (pre_ms) *pre_ms = pre;
+    if (run_ms) *run_ms = run;
+    return SMARTGPU_OK;
+}
+
+int smartgpu_psearch_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                             uint64_t* counts, double* batch_ms)
+{
+    if (!P || K < 1 || !counts) { set_error("psearch_batch: P/counts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
+    const int rc = check_psearch_args(P[0], m, text, off, n);
+    if (rc != SMARTGPU_OK) return rc;
+    double pre = 0.0, run = 0.0;
+    const int r = psearch_impl(P, m, K, text, off, n, counts, &pre, &run);
+    if (r != SMARTGPU_OK) return r;
+    if (batch_ms) *batch_ms = run;
+    g_last_pre_ms = pre / K;
+    g_last_run_ms = run / K;
+    return SMARTGPU_OK;
 }
 
 }  // extern "C"

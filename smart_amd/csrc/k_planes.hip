@@ -1,0 +1,214 @@
+// k_planes.hip — packed texts: planes_pack (byte text -> bit planes, once per text), planes_scan (the matcher on planes)
+// (one translation unit per kernel family: dev_common.hpp; the layout: planes.hpp)
+#include "dev_common.hpp"
+#include "launch_common.hpp"
+#include "planes.hpp"
+
+namespace sg {
+
+// ---------------------------------------------------------------------------
+// planes_pack: a lane reads 32 consecutive text bytes (two non-temporal 16-byte loads) and forms the dword of each plane
+// itself.  The code of a byte is its rank among the text's values: the number of values below it, three compares (v[] = 255
+// where the text has fewer values).  Zero bytes of the text's back pad beyond n give code 0: the planes' tail bits are zero.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void planes_pack(const uint8_t* __restrict__ text, uint64_t ndwords, uint32_t* __restrict__ p0,
+                                                   uint32_t* __restrict__ p1, uint32_t v0, uint32_t v1, uint32_t v2)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x; g < ndwords; g += stride) {
+        const uint4 a = ld_stream16(text + 32 * g), b = ld_stream16(text + 32 * g + 16);
+        const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        uint32_t b0 = 0, b1 = 0;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const uint32_t c = (d[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+            const uint32_t code = (uint32_t)(c > v0) + (uint32_t)(c > v1) + (uint32_t)(c > v2);
+            b0 |= (code & 1u) << i;
+            b1 |= (code >> 1) << i;
+        }
+        p0[g] = b0;
+        if (p1) p1[g] = b1;
+    }
+}
+
+hipError_t launch_planes_pack(const uint8_t* text, uint64_t n, uint32_t* p0, uint32_t* p1, int planes, const uint8_t values[3],
+                              hipStream_t stream)
+{
+    const uint64_t ndwords = (n + 31) / 32;
+    if (ndwords == 0) return hipSuccess;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((ndwords + 255) / 256, 65536);
+    hipLaunchKernelGGL(planes_pack, dim3(grid), dim3(256), 0, stream, text, ndwords, p0, planes == 2 ? p1 : nullptr,
+                       (uint32_t)values[0], (uint32_t)values[1], (uint32_t)values[2]);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// planes_scan<PLANES>: counts the start positions s in [s_begin, s_end) with T[s + j] == P[j] for all j < m.
+//
+// A lane owns kChunk = 4 consecutive dwords of start positions — 128 of them — per plane (one non-temporal
+// global_load_dwordx4) and keeps a dword M of live positions for each.  Pattern symbol j against the 32 positions of
+// dword w is t_b = v_alignbit(plane_b[w + 1], plane_b[w], j) per plane, then ONE three-input bit operation (v_bitop3) chosen by the
+// symbol's code, which is wave-uniform (a scalar branch): M &= ~(t0 | t1), t0 & ~t1, ~t0 & t1 or t0 & t1 — three vector
+// instructions per 32 positions and symbol on two planes, two on one.  The dword behind the lane's four comes by a second
+// (cached) load; a wave's last lane would need it anyway.
+// The first 32 symbols (x0, x1: kernel arguments) are taken eight at a time; after each eight the WAVE leaves when none of
+// its 8192 positions is live (random text of four values: 0.13 live positions per wave after eight symbols, of two values:
+// after sixteen).  Symbols from the 32nd on: planes_verify, the wave together for each lane that has a live position.
+// Positions outside [s_begin, s_end) are masked off the range's first and last chunk: the zero pad behind the text looks
+// like code 0 and is never counted.
+// kUnroll chunks per lane and trip: their loads are issued before any is worked on.
+// ---------------------------------------------------------------------------
+constexpr int kPlanesT = 256;
+constexpr uint32_t kChunk = 4;     // dwords per lane and plane
+constexpr int kUnroll = 2;         // chunks per lane and trip of the loop
+constexpr int kPlanesWgs = 8;      // workgroups per CU
+
+struct PlaneWords { uint32_t a[kChunk + 1], b[kChunk + 1]; };  // five consecutive dwords of plane 0 / plane 1
+
+// bits i with lo <= p + i < hi
+static __device__ __forceinline__ uint32_t range_mask(uint64_t p, uint64_t lo, uint64_t hi)
+{
+    uint32_t m = ~0u;
+    if (lo > p) m = lo - p >= 32 ? 0u : m << (uint32_t)(lo - p);
+    if (hi < p + 32) m = hi <= p ? 0u : m & (~0u >> (32u - (uint32_t)(hi - p)));
+    return m;
+}
+
+// symbols [j0, j1) (j1 <= 32) of a 32-symbol block of the pattern, bits x0 / x1, against the block's five dwords
+template <int PLANES>
+static __device__ __forceinline__ void planes_kill(uint32_t (&M)[kChunk], const PlaneWords& t, uint32_t x0, uint32_t x1, uint32_t j0, uint32_t j1)
+{
+    for (uint32_t j = j0; j < j1; ++j) {
+        const uint32_t c = ((x0 >> j) & 1u) | (PLANES == 2 ? ((x1 >> j) & 1u) << 1 : 0u);  // wave-uniform
+// M & f(t0, t1) as ONE v_bitop3_b32 (truth table over M = 0xF0, t0 = 0xCC, t1 = 0xAA); written with & | ~ the compiler
+// emits two or three instructions
+#define SG_PLANES_STEP(table_)                                                             \
+    _Pragma("unroll") for (uint32_t w = 0; w < kChunk; ++w) {                              \
+        const uint32_t t0 = __builtin_amdgcn_alignbit(t.a[w + 1], t.a[w], j);              \
+        const uint32_t t1 = PLANES == 2 ? __builtin_amdgcn_alignbit(t.b[w + 1], t.b[w], j) : 0u; \
+        M[w] = __builtin_amdgcn_bitop3_b32(M[w], t0, t1, table_);                          \
+    }
+        if (PLANES == 2) {
+            if (c == 0) { SG_PLANES_STEP(0x10) }       // M & ~(t0 | t1)
+            else if (c == 1) { SG_PLANES_STEP(0x40) }  // M & t0 & ~t1
+            else if (c == 2) { SG_PLANES_STEP(0x20) }  // M & ~t0 & t1
+            else { SG_PLANES_STEP(0x80) }              // M & t0 & t1
+        } else {
+            if (c == 0) { SG_PLANES_STEP(0x30) }       // M & ~t0
+            else { SG_PLANES_STEP(0xC0) }              // M & t0
+        }
+#undef SG_PLANES_STEP
+    }
+}
+
+// Symbols from the 32nd on, for the live positions of ONE lane's chunk, by the whole wave (every lane is here): a lane
+// that walks the pattern's up to 131 further dwords alone pays the latency of its loads 131 times in a row (0.4 ms for ONE
+// occurrence of a 4096-symbol pattern — measured: a 1 GiB scan of 50 us then takes 480).  So lane l takes block k0 + l — the
+// pattern's symbols 32 k .. 32 k + 31, x0 / x1 from the pattern's planes in memory, and the five text dwords k dwords behind
+// the chunk — and the wave goes over the live positions (R: wave-uniform, scalar): position i of dword w survives when in
+// every lane the 32 text symbols from it on equal the lane's block, one ballot.
+template <int PLANES>
+static __device__ __forceinline__ void planes_verify(uint32_t (&R)[kChunk], const PlaneArgs& a, uint64_t dw)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t k0 = 1; 32 * k0 < a.m && (R[0] | R[1] | R[2] | R[3]) != 0; k0 += 64) {
+        const bool valid = 32 * (k0 + lane) < a.m;
+        const uint32_t k = valid ? k0 + lane : k0;
+        const uint32_t left = a.m - 32 * k;
+        const uint32_t bmask = !valid ? 0u : left >= 32 ? ~0u : (1u << left) - 1u;  // the pattern's last block may be partial
+        uint32_t ta[kChunk + 1], tb[kChunk + 1];
+        __builtin_memcpy(ta, a.p0 + dw + k, 4 * (kChunk + 1));
+        if (PLANES == 2) __builtin_memcpy(tb, a.p1 + dw + k, 4 * (kChunk + 1));
+        const uint32_t x0 = a.pat[k], x1 = PLANES == 2 ? a.pat[kPatWords + k] : 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < kChunk; ++w) {
+            uint32_t r = R[w];
+            while (r) {
+                const uint32_t i = __builtin_ctz(r);
+                r &= r - 1;
+                uint32_t d = __builtin_amdgcn_alignbit(ta[w + 1], ta[w], i) ^ x0;
+                if (PLANES == 2) d |= __builtin_amdgcn_alignbit(tb[w + 1], tb[w], i) ^ x1;
+                if (__any((d & bmask) != 0)) R[w] &= ~(1u << i);
+            }
+        }
+    }
+}
+
+template <int PLANES>
+__global__ __launch_bounds__(kPlanesT, 8) void planes_scan(PlaneArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // 128 bytes: flush_hits
+    constexpr uint64_t kPos = 32 * kChunk;                          // start positions per chunk
+    const uint64_t c_end = (a.s_end + kPos - 1) / kPos;
+    const uint64_t stride = (uint64_t)gridDim.x * kPlanesT * kUnroll;
+    const uint32_t f1 = a.m < 32 ? a.m : 32u;
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t hits = 0;
+    // the trip count is the WAVE's (its first chunk decides): every lane stays for the ballots and the verification
+    for (uint64_t cw = a.s_begin / kPos + (uint64_t)blockIdx.x * kPlanesT * kUnroll + 64u * wave; cw < c_end; cw += stride) {
+        PlaneWords t[kUnroll];
+        uint32_t M[kUnroll][kChunk];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint64_t c = cw + (uint64_t)u * kPlanesT + lane;
+            const bool in = c < c_end;
+            const uint64_t dw = in ? c * kChunk : 0;
+            const uint4 va = ld_stream16(reinterpret_cast<const uint8_t*>(a.p0 + dw));
+            t[u].a[0] = va.x; t[u].a[1] = va.y; t[u].a[2] = va.z; t[u].a[3] = va.w;
+            t[u].a[4] = a.p0[dw + kChunk];
+            if (PLANES == 2) {
+                const uint4 vb = ld_stream16(reinterpret_cast<const uint8_t*>(a.p1 + dw));
+                t[u].b[0] = vb.x; t[u].b[1] = vb.y; t[u].b[2] = vb.z; t[u].b[3] = vb.w;
+                t[u].b[4] = a.p1[dw + kChunk];
+            }
+            const bool inner = c * kPos >= a.s_begin && (c + 1) * kPos <= a.s_end;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w)
+                M[u][w] = !in ? 0u : inner ? ~0u : range_mask(c * kPos + 32 * w, a.s_begin, a.s_end);
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint32_t live = 0;
+            for (uint32_t j0 = 0; j0 < f1; j0 += 8) {
+                planes_kill<PLANES>(M[u], t[u], a.x0, a.x1, j0, j0 + 8 < f1 ? j0 + 8 : f1);
+                live = M[u][0] | M[u][1] | M[u][2] | M[u][3];
+                if (!__any(live != 0)) break;
+            }
+            if (a.m > 32) {  // rarely: a lane has live positions after 32 symbols
+                unsigned long long todo = __ballot(live != 0);
+                while (todo) {
+                    const int src = __builtin_ctzll(todo);  // wave-uniform
+                    todo &= todo - 1;
+                    const uint64_t dw = (cw + (uint64_t)u * kPlanesT + (uint32_t)src) * kChunk;
+                    uint32_t R[kChunk];
+#pragma unroll
+                    for (uint32_t w = 0; w < kChunk; ++w) R[w] = __builtin_amdgcn_readlane(M[u][w], src);
+                    planes_verify<PLANES>(R, a, dw);
+                    if (lane == (uint32_t)src) {
+#pragma unroll
+                        for (uint32_t w = 0; w < kChunk; ++w) M[u][w] = R[w];
+                    }
+                }
+            }
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) hits += __builtin_popcount(M[u][w]);
+        }
+    }
+    flush_hits(hits, a.count, smem, reinterpret_cast<const uint8_t*>(a.p0));
+}
+
+hipError_t launch_planes_scan(const PlaneArgs& a, int planes, int num_cus, hipStream_t stream)
+{
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    constexpr uint64_t kPos = 32 * kChunk;
+    const uint64_t chunks = (a.s_end + kPos - 1) / kPos - a.s_begin / kPos;
+    const uint64_t want = (chunks + kPlanesT * kUnroll - 1) / (kPlanesT * kUnroll);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)num_cus * kPlanesWgs);
+    if (planes == 2)
+        hipLaunchKernelGGL(planes_scan<2>, dim3(grid), dim3(kPlanesT), 128, stream, a);
+    else
+        hipLaunchKernelGGL(planes_scan<1>, dim3(grid), dim3(kPlanesT), 128, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace sg

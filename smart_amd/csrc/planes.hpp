@@ -1,0 +1,44 @@
+// planes.hpp — packed texts (smartgpu_ptext): a text of at most four distinct byte values held as BIT PLANES, and the
+// launch interface of its two kernels (k_planes.hip).  Host-only types, as kernels.hpp.
+//
+// Plane b holds bit b of every symbol's code (the rank of its byte value among the values the text holds, ascending),
+// 32 symbols per dword: symbol i = bit i % 32 of dword i / 32.  One plane for at most two values, two for three or four.
+// One allocation:
+//     [kFrontPad zero bytes | plane 0 | kPlaneBackPad zero bytes | plane 1 | kPlaneBackPad zero bytes]
+// every plane 256-byte aligned.  The front pad is the byte text's (kernels.hpp): flush_hits finds its staging slots
+// kFrontPad - kHitSlotsOff bytes below plane 0, so planes_scan may run as a grid of any size.  The back pad lets every
+// load of the scan — a lane's four dwords, the dword behind them, and the same up to kPatWords dwords further on for the
+// symbols beyond the 32nd — stay inside the allocation with no bounds check.  Pad bits are zero and look like code 0:
+// they are never counted, the range [s_begin, s_end) keeps every window inside the text.
+#pragma once
+#include "kernels.hpp"
+
+#include "../../include/smartgpu.h"
+
+namespace sg {
+
+constexpr uint32_t kPatWords = (SMARTGPU_XSIZE + 31) / 32 + 1;  // dwords of one plane of a pattern (zero padded), 133
+constexpr uint64_t kPlaneBackPad = 4096;                        // bytes behind each plane
+static_assert(kPlaneBackPad >= 4 * (SMARTGPU_XSIZE / 32 + 1 + 8) && kPlaneBackPad % 256 == 0, "the scan's farthest load: the pattern's last dword + a lane's five");
+
+constexpr uint64_t plane_bytes(uint64_t n) { return 4 * ((n + 31) / 32); }                                   // pads excluded
+constexpr uint64_t plane_stride(uint64_t n) { return ((plane_bytes(n) + 255) & ~255ull) + kPlaneBackPad; }    // plane b at b * stride
+
+// What planes_scan receives (by value).
+struct PlaneArgs {
+    const uint32_t* p0;         // plane 0, dword 0 (flush_hits: the allocation's front pad lies kFrontPad below)
+    const uint32_t* p1;         // plane 1 (= p0 for a one-plane text; never read then)
+    uint64_t s_begin, s_end;    // start positions to count: s_begin <= s < s_end (s_end <= n - m + 1)
+    uint32_t m;                 // pattern length in symbols
+    uint32_t x0, x1;            // bits 0 / 1 of the codes of the pattern's first 32 symbols (symbol j = bit j)
+    const uint32_t* pat;        // device, m > 32 only: the pattern as planes, u32 X0[kPatWords], X1[kPatWords]
+    unsigned long long* count;  // device result slot (pre-zeroed)
+};
+
+// byte text -> planes.  values[0..2]: the byte values of codes 0..2 (255 where the text has fewer: no byte is greater);
+// the text's back pad (zero bytes) is read up to 31 bytes beyond n, the planes must be zero-filled before
+hipError_t launch_planes_pack(const uint8_t* text, uint64_t n, uint32_t* p0, uint32_t* p1, int planes, const uint8_t values[3],
+                              hipStream_t stream);
+hipError_t launch_planes_scan(const PlaneArgs& a, int planes, int num_cus, hipStream_t stream);
+
+}  // namespace sg

@@ -105,6 +105,20 @@ def _load(path):
         "smartgpu_selftest_launch_pool": (i32, [i32, i32]),
         "smartgpu_msearch64": (i32, [i32, vp, u32, vp, i32, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_probe_read_ms": (i32, [vp, i32, C.POINTER(C.c_double)]),
+        # packed texts (bit planes)
+        "smartgpu_ptext_layout": (i32, [u64, i32, C.POINTER(i32), C.POINTER(u64)]),
+        "smartgpu_ptext_pack": (vp, [vp]),
+        "smartgpu_ptext_upload": (vp, [vp, u64, i32]),
+        "smartgpu_ptext_free": (None, [vp]),
+        "smartgpu_ptext_length": (u64, [vp]),
+        "smartgpu_ptext_device": (i32, [vp]),
+        "smartgpu_ptext_planes": (i32, [vp]),
+        "smartgpu_ptext_bytes": (u64, [vp]),
+        "smartgpu_ptext_symbols": (i32, [vp, vp]),
+        "smartgpu_ptext_read": (i32, [vp, u64, u64, vp]),
+        "smartgpu_ptext_probe_read_ms": (i32, [vp, i32, C.POINTER(C.c_double)]),
+        "smartgpu_psearch64": (i32, [vp, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_psearch_batch64": (i32, [vp, u32, u32, vp, u64, u64, vp, C.POINTER(C.c_double)]),
     }
     for a in ALGOS:
         sig["smartgpu_%s_search" % a] = (i32, [vp, i32, vp, i32])
@@ -197,6 +211,89 @@ class Text:
         if self._h:
             self._L.smartgpu_text_free(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def ptext_layout(n, nvalues):
+    """(planes, plane_bytes) of a packed text of n symbols over nvalues distinct byte values — smartgpu_ptext_layout,
+    pure arithmetic, no device needed."""
+    planes, nbytes = C.c_int(0), C.c_uint64(0)
+    if lib().smartgpu_ptext_layout(n, nvalues, C.byref(planes), C.byref(nbytes)) != 0:
+        raise _err("ptext_layout")
+    return int(planes.value), int(nbytes.value)
+
+
+class PackedText:
+    """A text of at most four distinct byte values resident in one GPU's HBM as bit planes (smartgpu_ptext_*)."""
+
+    def __init__(self, handle):
+        if not handle:
+            raise _err("packed text")
+        self._h = handle
+        self._L = lib()  # the library that made the handle frees it
+
+    @classmethod
+    def pack(cls, text):
+        """Packs a resident Text on the device; the Text stays valid and independent."""
+        return cls(lib().smartgpu_ptext_pack(text._h))
+
+    @classmethod
+    def upload(cls, data, device=0):
+        data = _u8(data)
+        return cls(lib().smartgpu_ptext_upload(data.ctypes.data, len(data), device))
+
+    def __len__(self):
+        return int(lib().smartgpu_ptext_length(self._h))
+
+    @property
+    def device(self):
+        return lib().smartgpu_ptext_device(self._h)
+
+    @property
+    def planes(self):
+        return lib().smartgpu_ptext_planes(self._h)
+
+    @property
+    def nbytes(self):
+        """HBM bytes of the planes, pads excluded."""
+        return int(lib().smartgpu_ptext_bytes(self._h))
+
+    def symbols(self):
+        """The byte values the text holds, ascending: symbols()[code] is the value of a code."""
+        vals = np.zeros(4, dtype=np.uint8)
+        k = lib().smartgpu_ptext_symbols(self._h, vals.ctypes.data)
+        if k < 0:
+            raise _err("ptext_symbols")
+        return [int(v) for v in vals[:k]]
+
+    def read(self, off, length):
+        out = np.empty(length, dtype=np.uint8)
+        if lib().smartgpu_ptext_read(self._h, off, length, out.ctypes.data) != 0:
+            raise _err("ptext_read")
+        return out
+
+    def probe_read_gbs(self, reps=20):
+        """Practical streaming-read rate (GB/s) of the device over the planes: the packed layout's roofline."""
+        ms = C.c_double(0.0)
+        if lib().smartgpu_ptext_probe_read_ms(self._h, reps, C.byref(ms)) != 0:
+            raise _err("ptext_probe_read")
+        return self.nbytes / (ms.value * 1e-3) / 1e9
+
+    def free(self):
+        if self._h:
+            self._L.smartgpu_ptext_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
 
     def __del__(self):
         try:
@@ -345,6 +442,34 @@ def search(algo, P, text, off=0, n=None):
     if rc != 0:
         raise _err("search64(%s) rc=%d" % (algo, rc))
     return int(c.value), float(pre.value), float(run.value)
+
+
+def psearch(P, ptext, off=0, n=None):
+    """(count, pre_ms, run_ms) of P in symbols [off, off+n) of a PackedText: the count by definition (bf.c:25-39)."""
+    P = _u8(P)
+    if n is None:
+        n = len(ptext) - off
+    c = C.c_uint64(0)
+    pre = C.c_double(0.0)
+    run = C.c_double(0.0)
+    rc = lib().smartgpu_psearch64(P.ctypes.data, len(P), ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
+    if rc != 0:
+        raise _err("psearch64 rc=%d" % rc)
+    return int(c.value), float(pre.value), float(run.value)
+
+
+def psearch_batch(patterns, ptext, off=0, n=None):
+    """(counts, batch_ms) of a pattern set of one length over a PackedText: K launches, one read-back."""
+    pats, ptrs, m = _pattern_set(patterns)
+    K = len(pats)
+    if n is None:
+        n = len(ptext) - off
+    counts = np.zeros(K, dtype=np.uint64)
+    batch = C.c_double(0.0)
+    rc = lib().smartgpu_psearch_batch64(C.cast(ptrs, C.c_void_p), m, K, ptext._h, off, n, counts.ctypes.data, C.byref(batch))
+    if rc != 0:
+        raise _err("psearch_batch64 rc=%d" % rc)
+    return counts, float(batch.value)
 
 
 def _pattern_set(patterns):
