@@ -296,6 +296,8 @@ int smartgpu_build_table(int which, const uint8_t *P, uint32_t m, int32_t *out, 
  * symbol for 32 start positions at once.  None of the reference's search() functions reads such a text, so there is no
  * algorithm id: the contract is the count BY DEFINITION (src/algos/bf.c:25-39), overlapping occurrences counted, for
  * every 1 <= m <= SMARTGPU_XSIZE; none of the reference's documented deviations applies.
+ * Occurrence POSITIONS come from the same matcher with an output stage (planes_find; smartgpu_pfind64 and
+ * smartgpu_pfind_batch64 below), so a packed text needs no byte copy beside it for smartgpu_find64.
  * Measured on an MI355X (profiles/packed/RESULTS.md), symbols per second against the byte text's best of SO / BNDM / HOR,
  * m = 2 .. 4096: 8 Gi symbols of four values 2.9-3.6 x, 1 Gi of four values 2.7-3.9 x, 1 Gi of two values 2.9-6.7 x. */
 typedef struct smartgpu_ptext smartgpu_ptext;
@@ -327,6 +329,22 @@ int smartgpu_psearch64(const uint8_t *P, uint32_t m, const smartgpu_ptext *text,
  * smartgpu_search_batch64 without its one-grid form).  *batch_ms (or NULL): first launch to the counts on the host. */
 int smartgpu_psearch_batch64(const uint8_t *const *P, uint32_t m, uint32_t K, const smartgpu_ptext *text,
                              uint64_t off, uint64_t n, uint64_t *counts, double *batch_ms);
+/* Occurrence positions on a packed text: every s in [off, off+n-m] with symbols [s, s+m) == P, ascending, relative to
+ * symbol 0 of the text — the conventions of smartgpu_find64, the argument checks of smartgpu_psearch64.  *count always
+ * receives the number of occurrences.  SMARTGPU_OK when count <= cap: the list is complete.  SMARTGPU_ERR_NOMEM when it is
+ * not (the message names both numbers; the contents of positions are then unspecified).  cap == 0 with positions == NULL
+ * is a count.  count == NULL, or positions == NULL with cap > 0: SMARTGPU_ERR_ARG.  m > n, or a pattern byte the text does
+ * not hold: count 0, no launch.  The device buffer of up to 8 Mi positions is the device's own and kept between calls; when
+ * the device has no memory for min(cap, start positions) entries the call counts and reports SMARTGPU_ERR_NOMEM. */
+int smartgpu_pfind64(const uint8_t *P, uint32_t m, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                     uint64_t *positions, uint64_t cap, uint64_t *count);
+/* K patterns of m symbols: the positions of pattern k are positions[starts[k] .. starts[k+1]), each slice ascending;
+ * starts has K+1 entries, starts[0] = 0, starts[K] = the total.  Two passes over the planes: the counting batch
+ * (smartgpu_psearch_batch64), then K finds back to back, each into its own slice, and ONE copy to the host.
+ * starts[K] > cap: SMARTGPU_ERR_NOMEM with starts filled — every count and the room to allocate — and no find launched.
+ * K is bounded as in smartgpu_psearch_batch64. */
+int smartgpu_pfind_batch64(const uint8_t *const *P, uint32_t m, uint32_t K, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                           uint64_t *positions, uint64_t cap, uint64_t *starts);
 /* smartgpu_probe_read_ms on the planes: the streaming-read time of the bytes a packed search reads (the plane roofline) */
 int smartgpu_ptext_probe_read_ms(const smartgpu_ptext *t, int reps, double *ms_per_pass);
 

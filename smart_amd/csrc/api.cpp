@@ -70,6 +70,9 @@ struct DeviceCtx {
     size_t batch_slots = 0;
     unsigned long long* pinned_counts = nullptr;  // host side of the one read-back
     std::vector<hipEvent_t> batch_events;
+    // smartgpu_pfind64(): the positions' device buffer, kept between calls while it is small (find_reserve)
+    unsigned long long* find_out = nullptr;
+    size_t find_out_cap = 0;  // entries
 };
 DeviceCtx g_dev[kMaxDevices];
 
@@ -1771,6 +1774,23 @@ int check_psearch_args(const uint8_t* P, uint32_t m, const smartgpu_ptext* text,
     return SMARTGPU_OK;
 }
 
+// What the kernels receive for pattern k of a set staged at host_pat (pattern_planes) and, for m > 32, in the device's arena;
+// n >= m.  The result slot is d->batch_counts[k].
+sg::PlaneArgs plane_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* host_pat, uint32_t k, uint32_t m, uint64_t off, uint64_t n)
+{
+    sg::PlaneArgs a;
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.s_begin = off;
+    a.s_end = off + n - m + 1;
+    a.m = m;
+    a.x0 = host_pat[2 * sg::kPatWords * k];
+    a.x1 = host_pat[2 * sg::kPatWords * k + sg::kPatWords];
+    a.pat = reinterpret_cast<const uint32_t*>(d->arena) + 2 * sg::kPatWords * k;
+    a.count = d->batch_counts + k;
+    return a;
+}
+
 // K patterns of m symbols: their planes to the device's arena (m > 32 only: shorter patterns travel as kernel arguments),
 // K launches back to back on the device's stream, ONE read-back.  A pattern with a byte the text does not hold: no launch.
 int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
@@ -1797,16 +1817,7 @@ int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu
     HIP_TRY(hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream), return SMARTGPU_ERR_HIP);
     for (uint32_t k = 0; k < K && fits; ++k) {
         if (!present[k]) continue;
-        sg::PlaneArgs a;
-        a.p0 = text->plane(0);
-        a.p1 = text->plane(text->planes - 1);
-        a.s_begin = off;
-        a.s_end = off + n - m + 1;
-        a.m = m;
-        a.x0 = host_pat[2 * sg::kPatWords * k];
-        a.x1 = host_pat[2 * sg::kPatWords * k + sg::kPatWords];
-        a.pat = reinterpret_cast<const uint32_t*>(d->arena) + 2 * sg::kPatWords * k;
-        a.count = d->batch_counts + k;
+        const sg::PlaneArgs a = plane_args(d, text, host_pat, k, m, off, n);
         HIP_TRY(sg::launch_planes_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
     }
     HIP_TRY(hipMemcpyAsync(d->pinned_counts, d->batch_counts, static_cast<size_t>(K) * 8, hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
@@ -1818,6 +1829,100 @@ int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu
         counts[k] = d->pinned_counts[k];
     }
     return SMARTGPU_OK;
+}
+
+// The device buffer of `cap` positions for a find.  Up to kFindKeep entries it is the device's own, grown when a call needs
+// more and kept (no hipMalloc per call: a find on a packed text takes less time than an allocation); a larger one is the
+// call's (*own, to be freed by the caller).
+constexpr size_t kFindKeep = size_t(8) << 20;  // entries: 64 MiB
+unsigned long long* find_reserve(DeviceCtx* d, uint64_t cap, bool* own)
+{
+    *own = false;
+    if (cap <= d->find_out_cap) return d->find_out;
+    unsigned long long* out = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&out), cap * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("pfind: cannot allocate %llu positions on the device", (unsigned long long)cap);
+        return nullptr;
+    }
+    if (cap > kFindKeep) {
+        *own = true;
+        return out;
+    }
+    if (d->find_out) (void)hipFree(d->find_out);  // (idle: every find ends with a synchronisation of the device's stream)
+    d->find_out = out;
+    d->find_out_cap = static_cast<size_t>(cap);
+    return out;
+}
+
+// Positions from the device to the caller's (pageable) memory through the device's pinned staging buffer, part by part
+// (no overlap of copy and memcpy): a hipMemcpy into pageable memory stages as well, through buffers it sets up per call.
+// The staging buffer is free: the patterns it held have been launched and the stream is synchronised.
+bool copy_positions(DeviceCtx* d, uint64_t* dst, const unsigned long long* src, uint64_t count)
+{
+    for (uint64_t done = 0; done < count;) {
+        const uint64_t part = std::min<uint64_t>(count - done, d->pinned_bytes / 8);
+        if (hipMemcpyAsync(d->pinned, src + done, part * 8, hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
+            hipStreamSynchronize(d->stream) != hipSuccess)
+            return false;
+        std::memcpy(dst + done, d->pinned, part * 8);
+        done += part;
+    }
+    return true;
+}
+
+// planes_find's output in ascending order.  It is a sequence of spans (planes.hpp): each ascending and contiguous, each the
+// survivors of its own kFindSpan start positions counted from the range's first chunk, in the order the waves reserved them.
+// So the spans are found in one pass (the span number changes), ordered by it — one entry per span, not per position;
+// s_last is the last start position of the range — and moved only when they are out of order.  All `have` entries must be present (count <= cap).
+// false: the entries are not such spans (refused by the callers, never reported).
+bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t s_last)
+{
+    static_assert((sg::kFindSpan & (sg::kFindSpan - 1)) == 0, "span number by division");
+    const uint64_t base = s_begin / 128 * 128;
+    struct Span { uint64_t key, begin, len; };
+    std::vector<Span> spans;
+    bool ascending = true;
+    for (uint64_t i = 0; i < have; ++i) {
+        const uint64_t key = (pos[i] - base) / sg::kFindSpan;
+        if (!spans.empty() && spans.back().key == key) {
+            if (pos[i] <= pos[i - 1]) return false;  // not what planes_find writes (a retuned kernel whose spans are no longer these?)
+            ++spans.back().len;
+            continue;
+        }
+        if (!spans.empty() && key < spans.back().key) ascending = false;
+        spans.push_back({key, i, 1});
+    }
+    if (ascending) return true;
+    std::vector<uint64_t> tmp(have);
+    uint64_t at = 0;
+    const uint64_t nkeys = (s_last - base) / sg::kFindSpan + 1;
+    if (nkeys <= 16 * spans.size() + 4096) {
+        // many short spans (a pattern that occurs in every tenth span: a sort of 130,000 keys took most of the call): the
+        // span numbers are unique and bounded, so a table indexed by them orders the spans in one pass
+        constexpr uint64_t kNone = ~0ull;
+        std::vector<uint64_t> by_key(nkeys, kNone);
+        for (size_t i = 0; i < spans.size(); ++i) {
+            if (spans[i].key >= nkeys || by_key[spans[i].key] != kNone) return false;  // outside the range, or a span in two pieces
+            by_key[spans[i].key] = i;
+        }
+        for (uint64_t k = 0; k < nkeys; ++k) {
+            if (by_key[k] == kNone) continue;
+            const Span& sp = spans[by_key[k]];
+            std::memcpy(&tmp[at], pos + sp.begin, sp.len * sizeof(uint64_t));
+            at += sp.len;
+        }
+    } else {
+        std::sort(spans.begin(), spans.end(), [](const Span& x, const Span& y) { return x.key < y.key; });
+        for (size_t i = 1; i < spans.size(); ++i)
+            if (spans[i].key == spans[i - 1].key) return false;  // a span in two pieces
+        for (const Span& sp : spans) {
+            std::memcpy(&tmp[at], pos + sp.begin, sp.len * sizeof(uint64_t));
+            at += sp.len;
+        }
+    }
+    std::memcpy(pos, tmp.data(), have * sizeof(uint64_t));
+    return true;
 }
 
 }  // namespace
@@ -1979,6 +2084,113 @@ int smartgpu_psearch_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, co
     g_last_pre_ms = pre / K;
     g_last_run_ms = run / K;
     return SMARTGPU_OK;
+}
+
+/* ---- occurrence positions on a packed text (planes_find) ---------------------------------------------------------- */
+int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                     uint64_t* positions, uint64_t cap, uint64_t* count)
+{
+    const int rc = check_psearch_args(P, m, text, off, n);
+    if (rc != SMARTGPU_OK) return rc;
+    if (!count || (cap && !positions)) { set_error("pfind64: count must not be NULL, positions only with cap = 0"); return SMARTGPU_ERR_ARG; }
+    DeviceCtx* d = device_ctx(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    constexpr size_t kPatBytes = 2 * 4 * sg::kPatWords;
+    if (!batch_reserve(d, kPatBytes, 1)) return SMARTGPU_ERR_NOMEM;
+    uint32_t* host_pat = reinterpret_cast<uint32_t*>(d->pinned);  // (free: every call that fills it ends with a synchronisation)
+    const bool present = pattern_planes(text, P, m, host_pat, host_pat + sg::kPatWords);
+    if (!present || m > n) {  // a byte the text does not hold, or no window fits: no launch
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    const uint64_t starts = n - m + 1;
+    const uint64_t room = cap < starts ? cap : starts;  // no more positions than start positions
+    bool own = false;
+    unsigned long long* out = nullptr;
+    uint64_t room_got = room;
+    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
+    const sg::PlaneArgs a = plane_args(d, text, host_pat, 0, m, off, n);
+    bool ok = (m <= 32 || hipMemcpyAsync(d->arena, host_pat, kPatBytes, hipMemcpyHostToDevice, d->stream) == hipSuccess) &&
+              hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+              sg::launch_planes_find(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
+              hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+              hipStreamSynchronize(d->stream) == hipSuccess;
+    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
+    int r = SMARTGPU_OK;
+    if (!ok) {
+        set_error("pfind64: %s", hipGetErrorString(hipGetLastError()));
+        r = SMARTGPU_ERR_HIP;
+    } else if (total > starts) {  // refused like a poisoned count, never reported
+        set_error("planes_find: cursor %llu exceeds the %llu start positions", total, (unsigned long long)starts);
+        r = SMARTGPU_ERR_HIP;
+    } else if (total && total <= room_got) {
+        if (!copy_positions(d, positions, out, total)) {
+            set_error("pfind64: %s", hipGetErrorString(hipGetLastError()));
+            r = SMARTGPU_ERR_HIP;
+        } else if (!order_spans(positions, total, off, off + n - m)) {
+            set_error("planes_find: the positions are not ascending spans of %llu start positions", (unsigned long long)sg::kFindSpan);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (own) (void)hipFree(out);
+    if (r != SMARTGPU_OK) return r;
+    *count = total;
+    if (total <= cap && total > room_got) {
+        set_error("pfind64: %llu occurrences, room for %llu, but the device has no memory for %llu positions", total, (unsigned long long)cap, (unsigned long long)room);
+        return SMARTGPU_ERR_NOMEM;
+    }
+    if (total > cap) { set_error("pfind64: %llu occurrences, room for %llu", total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    return SMARTGPU_OK;
+}
+
+int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                           uint64_t* positions, uint64_t cap, uint64_t* starts)
+{
+    if (!P || K < 1 || !starts) { set_error("pfind_batch: P/starts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
+    const int rc = check_psearch_args(P[0], m, text, off, n);
+    if (rc != SMARTGPU_OK) return rc;
+    if (cap && !positions) { set_error("pfind_batch: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
+    // pass 1: the K counts (the planes are read twice: a one-pass ordered batch is not built)
+    std::vector<uint64_t> counts(K);
+    const int r1 = psearch_impl(P, m, K, text, off, n, counts.data(), nullptr, nullptr);
+    if (r1 != SMARTGPU_OK) return r1;
+    starts[0] = 0;
+    for (uint32_t k = 0; k < K; ++k) starts[k + 1] = starts[k] + counts[k];
+    const uint64_t total = starts[K];
+    if (total > cap) { set_error("pfind_batch: %llu occurrences, room for %llu", (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    if (total == 0) return SMARTGPU_OK;
+    // pass 2: a find for every pattern that occurs, each with its own cursor and its own slice as base and cap.  The
+    // patterns' planes are where psearch_impl left them: the staging buffer and, for m > 32, the arena.
+    DeviceCtx* d = device_ctx(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const uint32_t* host_pat = reinterpret_cast<const uint32_t*>(d->pinned);
+    bool own = false;
+    unsigned long long* out = find_reserve(d, total, &own);
+    if (!out) return SMARTGPU_ERR_NOMEM;
+    bool ok = hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream) == hipSuccess;
+    for (uint32_t k = 0; k < K && ok; ++k) {
+        if (counts[k] == 0) continue;
+        const sg::PlaneArgs a = plane_args(d, text, host_pat, k, m, off, n);
+        ok = sg::launch_planes_find(a, out + starts[k], counts[k], text->planes, d->num_cus, d->stream) == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(d->pinned_counts, d->batch_counts, static_cast<size_t>(K) * 8, hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+         hipStreamSynchronize(d->stream) == hipSuccess && copy_positions(d, positions, out, total);
+    int r = SMARTGPU_OK;
+    if (!ok) {
+        set_error("pfind_batch: %s", hipGetErrorString(hipGetLastError()));
+        r = SMARTGPU_ERR_HIP;
+    }
+    for (uint32_t k = 0; k < K && r == SMARTGPU_OK; ++k) {
+        if (d->pinned_counts[k] != counts[k]) {  // the two passes disagree: refused, never reported
+            set_error("planes_find: pattern %u: cursor %llu, planes_scan counted %llu", k, d->pinned_counts[k], (unsigned long long)counts[k]);
+            r = SMARTGPU_ERR_HIP;
+        } else if (!order_spans(positions + starts[k], counts[k], off, off + n - m)) {
+            set_error("planes_find: pattern %u: the positions are not ascending spans of %llu start positions", k, (unsigned long long)sg::kFindSpan);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (own) (void)hipFree(out);
+    return r;
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// k_planes.hip — packed texts: planes_pack (byte text -> bit planes, once per text), planes_scan (the matcher on planes)
+// k_planes.hip — packed texts: planes_pack (byte text -> bit planes, once per text), planes_scan (the matcher on planes),
+// planes_find (the same matcher with an output stage: positions)
 // (one translation unit per kernel family: dev_common.hpp; the layout: planes.hpp)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
@@ -208,6 +209,130 @@ hipError_t launch_planes_scan(const PlaneArgs& a, int planes, int num_cus, hipSt
         hipLaunchKernelGGL(planes_scan<2>, dim3(grid), dim3(kPlanesT), 128, stream, a);
     else
         hipLaunchKernelGGL(planes_scan<1>, dim3(grid), dim3(kPlanesT), 128, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// planes_find<PLANES>: planes_scan with an output stage — the surviving start positions are appended to `out` (relative to
+// symbol 0 of the text) and a.count, a 64-bit cursor, receives their number.
+//
+// The loop skeleton below REPEATS planes_scan's on purpose (about 40 lines; the helpers are shared).  Moving the body into
+// one function template <PLANES, FIND> changes planes_scan's instruction stream (940 -> 968 and 1061 -> 1095 instructions
+// cross-compiled for gfx950, same registers), and the counting path is measured and documented as it is: the repeated
+// skeleton is the price of leaving it untouched.  A change to one of the two loops belongs in the other as well.
+//
+// The output stage runs once a chunk is final (after planes_verify when m > 32) and only when a lane of the wave has a
+// survivor: one wave-uniform branch more than planes_scan for every other chunk.  The lanes' counts (popcount of the four M
+// dwords) are prefix-summed inside the wave by shuffles, lane 0 reserves the wave's span of the output with ONE atomicAdd on
+// the cursor, the base comes back to every lane by readfirstlane, and each lane stores its positions, ascending, with
+// ordinary vector stores while slot < cap.  Entries beyond cap are dropped, the cursor counts them all the same.
+// A span — one wave, one chunk row: kFindSpan start positions from the range's first chunk on — is contiguous and ascending
+// in `out`; the spans of a launch cover disjoint position ranges and lie in the order their waves reserved them (the host
+// orders them by their first entry, api.cpp).  No LDS, no scratch.
+// ---------------------------------------------------------------------------
+static_assert(kFindSpan == 64 * 32 * kChunk, "a span of planes_find: one wave's lanes, one chunk each");
+static_assert(kPlanesT % 64 == 0, "every wave's chunk row starts a multiple of 64 chunks behind the range's first: the host's span number");
+
+template <int PLANES>
+__global__ __launch_bounds__(kPlanesT, 8) void planes_find(PlaneArgs a, unsigned long long* __restrict__ out, unsigned long long cap)
+{
+    constexpr uint64_t kPos = 32 * kChunk;  // start positions per chunk
+    const uint64_t c_end = (a.s_end + kPos - 1) / kPos;
+    const uint64_t stride = (uint64_t)gridDim.x * kPlanesT * kUnroll;
+    const uint32_t f1 = a.m < 32 ? a.m : 32u;
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the trip count is the WAVE's (its first chunk decides): every lane stays for the ballots, the verification and the shuffles
+    for (uint64_t cw = a.s_begin / kPos + (uint64_t)blockIdx.x * kPlanesT * kUnroll + 64u * wave; cw < c_end; cw += stride) {
+        PlaneWords t[kUnroll];
+        uint32_t M[kUnroll][kChunk];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint64_t c = cw + (uint64_t)u * kPlanesT + lane;
+            const bool in = c < c_end;
+            const uint64_t dw = in ? c * kChunk : 0;
+            const uint4 va = ld_stream16(reinterpret_cast<const uint8_t*>(a.p0 + dw));
+            t[u].a[0] = va.x; t[u].a[1] = va.y; t[u].a[2] = va.z; t[u].a[3] = va.w;
+            t[u].a[4] = a.p0[dw + kChunk];
+            if (PLANES == 2) {
+                const uint4 vb = ld_stream16(reinterpret_cast<const uint8_t*>(a.p1 + dw));
+                t[u].b[0] = vb.x; t[u].b[1] = vb.y; t[u].b[2] = vb.z; t[u].b[3] = vb.w;
+                t[u].b[4] = a.p1[dw + kChunk];
+            }
+            const bool inner = c * kPos >= a.s_begin && (c + 1) * kPos <= a.s_end;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w)
+                M[u][w] = !in ? 0u : inner ? ~0u : range_mask(c * kPos + 32 * w, a.s_begin, a.s_end);
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint32_t live = 0;
+            for (uint32_t j0 = 0; j0 < f1; j0 += 8) {
+                planes_kill<PLANES>(M[u], t[u], a.x0, a.x1, j0, j0 + 8 < f1 ? j0 + 8 : f1);
+                live = M[u][0] | M[u][1] | M[u][2] | M[u][3];
+                if (!__any(live != 0)) break;
+            }
+            if (a.m > 32) {  // rarely: a lane has live positions after 32 symbols
+                unsigned long long todo = __ballot(live != 0);
+                while (todo) {
+                    const int src = __builtin_ctzll(todo);  // wave-uniform
+                    todo &= todo - 1;
+                    const uint64_t dw = (cw + (uint64_t)u * kPlanesT + (uint32_t)src) * kChunk;
+                    uint32_t R[kChunk];
+#pragma unroll
+                    for (uint32_t w = 0; w < kChunk; ++w) R[w] = __builtin_amdgcn_readlane(M[u][w], src);
+                    planes_verify<PLANES>(R, a, dw);
+                    if (lane == (uint32_t)src) {
+#pragma unroll
+                        for (uint32_t w = 0; w < kChunk; ++w) M[u][w] = R[w];
+                    }
+                }
+                live = M[u][0] | M[u][1] | M[u][2] | M[u][3];
+            }
+            if (!__any(live != 0)) continue;
+            // the output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
+            uint32_t mine = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) mine += __builtin_popcount(M[u][w]);
+            uint32_t incl = mine;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = __shfl_up(incl, d, 64);
+                if (lane >= (uint32_t)d) incl += up;
+            }
+            const uint32_t total = __shfl(incl, 63, 64);
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
+            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                   __builtin_amdgcn_readfirstlane((uint32_t)base);
+            unsigned long long slot = base + (incl - mine);
+            const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) {
+                uint32_t r = M[u][w];
+                while (r) {
+                    const uint32_t i = __builtin_ctz(r);
+                    r &= r - 1;
+                    if (slot < cap) out[slot] = pos + 32 * w + i;
+                    ++slot;
+                }
+            }
+        }
+    }
+}
+
+// Grid and occupancy: launch_planes_scan's.
+hipError_t launch_planes_find(const PlaneArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                              hipStream_t stream)
+{
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    constexpr uint64_t kPos = 32 * kChunk;
+    const uint64_t chunks = (a.s_end + kPos - 1) / kPos - a.s_begin / kPos;
+    const uint64_t want = (chunks + kPlanesT * kUnroll - 1) / (kPlanesT * kUnroll);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)num_cus * kPlanesWgs);
+    if (planes == 2)
+        hipLaunchKernelGGL(planes_find<2>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
+    else
+        hipLaunchKernelGGL(planes_find<1>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
     return hipGetLastError();
 }
 

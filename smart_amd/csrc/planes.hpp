@@ -1,5 +1,5 @@
 // planes.hpp — packed texts (smartgpu_ptext): a text of at most four distinct byte values held as BIT PLANES, and the
-// launch interface of its two kernels (k_planes.hip).  Host-only types, as kernels.hpp.
+// launch interface of its kernels (k_planes.hip).  Host-only types, as kernels.hpp.
 //
 // Plane b holds bit b of every symbol's code (the rank of its byte value among the values the text holds, ascending),
 // 32 symbols per dword: symbol i = bit i % 32 of dword i / 32.  One plane for at most two values, two for three or four.
@@ -24,7 +24,7 @@ static_assert(kPlaneBackPad >= 4 * (SMARTGPU_XSIZE / 32 + 1 + 8) && kPlaneBackPa
 constexpr uint64_t plane_bytes(uint64_t n) { return 4 * ((n + 31) / 32); }                                   // pads excluded
 constexpr uint64_t plane_stride(uint64_t n) { return ((plane_bytes(n) + 255) & ~255ull) + kPlaneBackPad; }    // plane b at b * stride
 
-// What planes_scan receives (by value).
+// What planes_scan and planes_find receive (by value).
 struct PlaneArgs {
     const uint32_t* p0;         // plane 0, dword 0 (flush_hits: the allocation's front pad lies kFrontPad below)
     const uint32_t* p1;         // plane 1 (= p0 for a one-plane text; never read then)
@@ -40,5 +40,14 @@ struct PlaneArgs {
 hipError_t launch_planes_pack(const uint8_t* text, uint64_t n, uint32_t* p0, uint32_t* p1, int planes, const uint8_t values[3],
                               hipStream_t stream);
 hipError_t launch_planes_scan(const PlaneArgs& a, int planes, int num_cus, hipStream_t stream);
+
+// Positions: planes_scan with an output stage.  a.count (pre-zeroed) is the cursor and receives the number of occurrences;
+// out[0 .. min(count, cap)) receives start positions relative to symbol 0 of the text; entries beyond cap are dropped.
+// What lies in `out` is a sequence of SPANS: the survivors among the kFindSpan start positions
+// [s_begin / 128 * 128 + k * kFindSpan, + kFindSpan) for some k, ascending and contiguous; every k at most once, in no
+// particular order.
+constexpr uint64_t kFindSpan = 8192;
+hipError_t launch_planes_find(const PlaneArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                              hipStream_t stream);
 
 }  // namespace sg

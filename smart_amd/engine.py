@@ -119,6 +119,8 @@ def _load(path):
         "smartgpu_ptext_probe_read_ms": (i32, [vp, i32, C.POINTER(C.c_double)]),
         "smartgpu_psearch64": (i32, [vp, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_psearch_batch64": (i32, [vp, u32, u32, vp, u64, u64, vp, C.POINTER(C.c_double)]),
+        "smartgpu_pfind64": (i32, [vp, u32, vp, u64, u64, vp, u64, C.POINTER(u64)]),
+        "smartgpu_pfind_batch64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp]),
     }
     for a in ALGOS:
         sig["smartgpu_%s_search" % a] = (i32, [vp, i32, vp, i32])
@@ -470,6 +472,42 @@ def psearch_batch(patterns, ptext, off=0, n=None):
     if rc != 0:
         raise _err("psearch_batch64 rc=%d" % rc)
     return counts, float(batch.value)
+
+
+def pfind(P, ptext, off=0, n=None, cap=1 << 20):
+    """(positions, count): the ascending start positions (relative to symbol 0) of P in symbols [off, off+n) of a
+    PackedText, and their number — find() on a packed text.  When there are more than `cap`, positions is None and only
+    the count is returned (smartgpu_pfind64 reports SMARTGPU_ERR_NOMEM; retry with cap >= count)."""
+    P = _u8(P)
+    if n is None:
+        n = len(ptext) - off
+    out = np.empty(max(cap, 1), dtype=np.uint64)
+    c = C.c_uint64(0)
+    rc = lib().smartgpu_pfind64(P.ctypes.data, len(P), ptext._h, off, n, out.ctypes.data if cap else None, cap, C.byref(c))
+    if rc == -5 and c.value > cap:
+        return None, int(c.value)
+    if rc != 0:
+        raise _err("pfind64 rc=%d" % rc)
+    return out[:c.value].copy(), int(c.value)
+
+
+def pfind_batch(patterns, ptext, off=0, n=None, cap=1 << 20):
+    """(list of K ascending uint64 arrays, counts) for a pattern set of one length over a PackedText; `cap` is the room for
+    the positions of ALL patterns.  When they are more, the list is None and the counts say how much room a retry needs."""
+    pats, ptrs, m = _pattern_set(patterns)
+    K = len(pats)
+    if n is None:
+        n = len(ptext) - off
+    out = np.empty(max(cap, 1), dtype=np.uint64)
+    starts = np.zeros(K + 1, dtype=np.uint64)
+    rc = lib().smartgpu_pfind_batch64(C.cast(ptrs, C.c_void_p), m, K, ptext._h, off, n, out.ctypes.data if cap else None, cap,
+                                      starts.ctypes.data)
+    counts = np.diff(starts)
+    if rc == -5 and int(starts[K]) > cap:
+        return None, counts
+    if rc != 0:
+        raise _err("pfind_batch64 rc=%d" % rc)
+    return [out[int(starts[k]):int(starts[k + 1])].copy() for k in range(K)], counts
 
 
 def _pattern_set(patterns):

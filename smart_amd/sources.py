@@ -25,7 +25,7 @@ KERNEL_UNIT = {
     "hor_scan": "k_hor", "hor_scan_bp": "k_hor", "hor_scan_gram": "k_horg", "bm_scan_gram": "k_bmg", "bm_scan": "k_bm", "bndm_scan": "k_bndm", "sbndm_scan": "k_bndmx",
     "bndml_scan": "k_bndmx", "so_runs": "k_so", "kmp_runs": "k_kmp", "packed_scan": "k_packed", "packed_find": "k_packed",
     "generate_text": "k_util", "tile_fill": "k_util", "text_alphabet": "k_util", "probe_read": "k_util",
-    "planes_pack": "k_planes", "planes_scan": "k_planes",
+    "planes_pack": "k_planes", "planes_scan": "k_planes", "planes_find": "k_planes",
 }
 
 
