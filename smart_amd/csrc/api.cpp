@@ -25,6 +25,7 @@
 
 #include "kernels.hpp"
 #include "planes.hpp"
+#include "route.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -122,6 +123,30 @@ double now_ms()
     return std::chrono::duration<double, std::milli>(clk::now().time_since_epoch()).count();
 }
 
+// `reps` passes of probe_read over [first, first + bytes) after one warm-up pass, timed by two events of its own: both
+// are released on every path
+int probe_read_ms(const DeviceCtx* d, const uint8_t* first, uint64_t bytes, unsigned long long* sink, int reps, double* ms_per_pass)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const auto timed = [&]() -> int {
+        HIP_TRY(hipEventCreate(&e0), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipEventCreate(&e1), return SMARTGPU_ERR_HIP);
+        sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);  // warm-up
+        hipEventRecord(e0, d->stream);
+        for (int i = 0; i < reps; ++i) sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);
+        hipEventRecord(e1, d->stream);
+        HIP_TRY(hipEventSynchronize(e1), return SMARTGPU_ERR_HIP);
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, e0, e1);
+        *ms_per_pass = ms / reps;
+        return SMARTGPU_OK;
+    };
+    const int rc = timed();
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    return rc;
+}
+
 }  // namespace
 
 struct smartgpu_text {
@@ -140,10 +165,7 @@ struct smartgpu_plan {
     int device = 0;
     int algo = 0;
     uint32_t m = 0;
-    uint32_t halo = 0;
-    uint32_t prefer_packed = 0;  // see build_blob
-    uint32_t sparse = 0;         // see build_blob
-    uint32_t so_off = 0;         // see build_blob
+    sg::PlanWords words;  // see build_blob
     uint8_t* blob = nullptr;               // device: pattern + tables
     unsigned long long* results = nullptr; // device: kResultSlots counters (library-owned)
     unsigned long long* ext_results = nullptr; // caller-owned device buffer, if set
@@ -254,12 +276,9 @@ bool text_no_alphabet(smartgpu_text* t, DeviceCtx* d)
 
 // Build the device blob (pattern + tables) for (algo, P, m) in `blob` (cleared first; a caller that builds many
 // reuses one vector: fresh memory for every blob of a pattern set cost more in page faults than the tables in work).
-void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t m, uint32_t* halo,
-                uint32_t* prefer_packed, uint32_t* sparse, uint32_t* so_off)
+sg::PlanWords build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t m)
 {
-    *prefer_packed = 0;
-    *sparse = 0;
-    *so_off = 0;
+    sg::PlanWords pw;
     blob.clear();
     blob.resize(sg::kPatternBytes, 0);
     std::memcpy(blob.data(), P, m);
@@ -303,13 +322,13 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
     }
     // The opposite case: symbols do not repeat (random text over a large alphabet).  Windows then die on
     // their first comparison and a skip kernel only streams; it runs best with FEWER workgroups per CU
-    // (kTileWgs in kernels.hip, measured).  Patterns with repeating symbols that still run on a tile
+    // (tile_wgs in launch_common.hpp, measured).  Patterns with repeating symbols that still run on a tile
     // kernel (tune(0,1), KR) keep the lanes busy verifying: more workgroups hide that.  How many exactly
-    // depends on m and the kernel: tile_wgs() in kernels.hip.
+    // depends on m and the kernel: tile_wgs() in launch_common.hpp.
     // (An earlier form — >= 80 % of the first min(m,64) symbols distinct — missed rand128 at m = 64,
     // 50 distinct symbols expected: HOR 80 %, BM 76 %, BNDM 71 % there against 84-87 % at m = 32 and 128.)
-    *sparse = m >= 8 && !repeats;
-    *halo = std::min<uint32_t>(m - 1, sg::kHaloMax);
+    pw.sparse = m >= 8 && !repeats;
+    pw.halo = std::min<uint32_t>(m - 1, sg::kHaloMax);
     switch (algo) {
         case SMARTGPU_TUNEDBM:  // tunedbm.c:38-40: the same table with a zero for P[m-1] — the flag bit below
         case SMARTGPU_RAITA:    // raita.c:43: the same table
@@ -332,14 +351,14 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
                 const std::vector<int32_t> sh = sg::qgram_hash_shifts(P, m, hor_q, &after);
                 for (int c = 0; c < 256; ++c)
                     tab[c] = sh[c] == 0 ? static_cast<uint16_t>(0x8000u | after) : static_cast<uint16_t>(sh[c]);
-                *halo |= hor_q << 8;
+                pw.halo |= hor_q << 8;
             }
             append(tab.data(), 512);
             uint8_t tab8[256];  // plain u8 shifts for the bank-private kernel (m <= 255)
             for (int c = 0; c < 256; ++c) tab8[c] = static_cast<uint8_t>(bc[c] > 255 ? 255 : bc[c]);
             append(tab8, 256);
             append_fingerprint();  // packed regime
-            *prefer_packed = repeats;
+            pw.prefer_packed = repeats;
             break;
         }
         case SMARTGPU_BM: {
@@ -362,13 +381,13 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
             // the remaining comparison says: min of gs over the unchecked positions (and gs[0],
             // the shift after a full match).  Used when the kernel parks the window.
             int32_t safe = gs[0];
-            if (m - 1 > *halo)
-                for (uint32_t i = 0; i + 1 < m - *halo; ++i) safe = std::min(safe, gs[i]);
+            if (m - 1 > pw.halo)
+                for (uint32_t i = 0; i + 1 < m - pw.halo; ++i) safe = std::min(safe, gs[i]);
             tab[768 + m] = static_cast<uint16_t>(safe);
             append(tab.data(), tab.size() * 2);
             if (blob.size() % 4) blob.resize((blob.size() + 3) & ~size_t(3), 0);
             append_fingerprint();  // packed regime
-            *prefer_packed = repeats;
+            pw.prefer_packed = repeats;
             break;
         }
         case SMARTGPU_KMP: {
@@ -376,7 +395,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
             std::vector<int16_t> tab(m + 1);
             for (uint32_t i = 0; i <= m; ++i) tab[i] = static_cast<int16_t>(nx[i]);
             append(tab.data(), tab.size() * 2);
-            *halo = m - 1;  // forward halo: the automaton re-scans m-1 bytes
+            pw.halo = m - 1;  // forward halo: the automaton re-scans m-1 bytes
             blob.resize((blob.size() + 15) & ~size_t(15), 0);  // the transition table is 16-byte aligned
             // kmp_runs<., false, COMPACT> (round 4; every text that is not a four-symbol text): the automaton over
             // kmp_compact_window(m) bytes — the pattern, or its 56-byte prefix — with an ABSORBING accept row Z (every transition
@@ -401,7 +420,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
 #else
             if (has4) sg::kmp_runs_tables(P, w4, blob);
 #endif
-            if (has4) *prefer_packed = w4;
+            if (has4) pw.prefer_packed = w4;
 #ifdef SMARTGPU_AB
             {   // kmp_runs1 (A/B build): the automaton of P[0..w), w = min(m, 255); state s is row id(s) = rotl8(s, 2),
                 // the accept state row 255 — or row 4w while the ids 4s do not wrap (w < 64) —, the largest id (its
@@ -436,7 +455,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
                 const uint32_t period = w - static_cast<uint32_t>(nx[w]);
                 append(&period, 4);
                 append_fingerprint();  // packed regime (at kTableOff + 1024*W + 4)
-                *prefer_packed = repeats;
+                pw.prefer_packed = repeats;
                 break;
             }
             [[fallthrough]];  // m <= 32: plain BNDM (bndml.c:44-75)
@@ -465,7 +484,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
                 }
                 bndm_q_wanted = q;
                 while (w % q) q /= 2;  // q | w: a window is read through in whole iterations
-                *halo = q;
+                pw.halo = q;
             }
             if (algo == SMARTGPU_SBNDM) {  // sbndm.c:44-55: the shift after an occurrence = period of P[0..w)
                 const uint32_t w = std::min<uint32_t>(m, 32);
@@ -473,7 +492,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
                 const uint32_t period = w - static_cast<uint32_t>(nx[w]);
                 append(&period, 4);
             }
-            *prefer_packed = repeats;
+            pw.prefer_packed = repeats;
             break;
         }
         case SMARTGPU_EPSM:
@@ -484,7 +503,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
             for (uint32_t i = 0; i < m; ++i) hp = (hp << 1) + P[i];
             append(&hp, 4);
             append_fingerprint();  // packed regime (m < 16), at kTableOff + 4
-            *halo = std::min<uint32_t>(m - 1, 32);  // bytes confirmed in LDS (and the hash's reach) behind a window end
+            pw.halo = std::min<uint32_t>(m - 1, 32);  // bytes confirmed in LDS (and the hash's reach) behind a window end
             break;
         }
         case SMARTGPU_SA: {
@@ -511,7 +530,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
             const uint8_t spare[256] = {0};
             append(spare, 256);
             append_fingerprint();  // packed regime
-            *prefer_packed = repeats;
+            pw.prefer_packed = repeats;
             break;
         }
         case SMARTGPU_QS: {  // same layout as HOR: u16 table, 256 spare bytes, fingerprint
@@ -522,11 +541,11 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
             const uint8_t spare[256] = {0};
             append(spare, 256);
             append_fingerprint();  // packed regime
-            *prefer_packed = repeats;
+            pw.prefer_packed = repeats;
             break;
         }
     }
-    // Patterns that are counted by the Shift-Or runs kernel whatever the algorithm (kernels.hip launch_scan): their
+    // Patterns that are counted by the Shift-Or runs kernel whatever the algorithm (launch.hip route): their
     // plans carry its masks as well.
     //  * Symbols repeat (the rule above; or, for 7 bytes and fewer, some symbol occurs twice): small alphabets,
     //    natural language, rand32.  Round 1 sent these to the packed matcher, which tests two or three fingerprint
@@ -543,7 +562,7 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
     // occurrences byte by byte: m = 8: 61-72 % against so_runs' 74-81 % on every corpus; m = 2: 54 % against 76-78 %.
     // Karp-Rabin its own from 16 bytes on, EPSM its packed matcher (it IS that algorithm).
     if ((algo != SMARTGPU_KMP || m < 9) && algo != SMARTGPU_SO && algo != SMARTGPU_SA && (algo != SMARTGPU_KR || m < 16)) {
-        // * Short patterns (below the algorithm's measured crossover with its own skip loop, kernels.hip packed_max_m):
+        // * Short patterns (below the algorithm's measured crossover with its own skip loop, launch.hip packed_max_m):
         //   the every-byte kernels win there; so_runs and the packed matcher are equal on rand128 (76-77 %), so_runs
         //   ahead on everything else (rand256, rand32, English at m = 2, 4: 78-81 % against 67-76 %).
         bool to_so = (algo == SMARTGPU_KR || algo == SMARTGPU_KMP) ? true : (repeats || repeats_short || m <= sg::short_pattern_max_m(algo)) && algo != SMARTGPU_EPSM;
@@ -566,19 +585,19 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
         // (Boyer-Moore likewise, k_bmg.hip: its good-suffix rule joined with the gram's shift)
         // (two symbols, 16 bytes — a window of two grams —: 0.66-0.69 against so_runs' 0.77: those from 32 bytes on, 0.78-0.81)
         if ((algo == SMARTGPU_HOR || algo == SMARTGPU_BM || algo == SMARTGPU_TUNEDBM) && distinct >= 2 && distinct <= 4) own_holds = m >= (distinct <= 2 ? 32u : 16u);
-        if (algo == SMARTGPU_BNDM || (algo == SMARTGPU_BNDML && m <= 32)) own_holds = *halo == bndm_q_wanted && (*halo >= 8 ? m >= 32 : m >= 16);  // *halo: bndm_scan's q
+        if (algo == SMARTGPU_BNDM || (algo == SMARTGPU_BNDML && m <= 32)) own_holds = pw.halo == bndm_q_wanted && (pw.halo >= 8 ? m >= 32 : m >= 16);  // pw.halo: bndm_scan's q
         // BNDM over two to four symbols, 8+ bytes: on a text of at most four byte values bndm_scan's GRAM form decides every
         // window with one lookup (k_bndm.hip bndm_gram: 0.74-0.8 of the roofline on rand2 / rand4 at any such length; so_runs
         // 0.77).  The plan cannot see the text; a pattern of two to four symbols cut from it says what it most likely is
         // (on any other text the launch falls back to the mask loop — correct, and slow on such a pattern).
         const bool gram_window = (algo == SMARTGPU_BNDM || (algo == SMARTGPU_BNDML && m <= 32)) && m >= 8 && distinct >= 2 && distinct <= 4;
         if (gram_window) {
-            *halo |= sg::kBndmGramWindow;
+            pw.halo |= sg::kBndmGramWindow;
             to_so = false;
-            *prefer_packed = 0;
+            pw.prefer_packed = 0;
         } else if (own_holds && m > sg::short_pattern_max_m(algo)) {
             to_so = false;
-            *prefer_packed = 0;
+            pw.prefer_packed = 0;
         } else if (!to_so && m >= 8) {  // (8 bytes of distinct symbols estimate 16/8^4 = 0.004: below that the histogram says nothing)
             uint32_t cnt[256] = {0};
             for (uint32_t i = 0; i < m; ++i) ++cnt[P[i]];
@@ -594,49 +613,42 @@ void build_blob(std::vector<uint8_t>& blob, int algo, const uint8_t* P, uint32_t
         }
         if (to_so) {
             blob.resize((blob.size() + 15) & ~size_t(15), 0);
-            *so_off = static_cast<uint32_t>(blob.size());
+            pw.so_off = static_cast<uint32_t>(blob.size());
             const std::vector<uint32_t> S = sg::shift_or_masks(P, m);
             append(S.data(), 1024);
         }
     }
     blob.resize((blob.size() + 255) & ~size_t(255), 0);
+    return pw;
 }
 
-std::vector<uint8_t> build_blob(int algo, const uint8_t* P, uint32_t m, uint32_t* halo,
-                                uint32_t* prefer_packed, uint32_t* sparse, uint32_t* so_off)
+// The pattern checks of every entry point: algorithm id, applicability, length.  length_first: smartgpu_plan_create's order
+// (a pattern that is both too short for the algorithm and not a pattern at all — m = 0, P = NULL — is reported as the latter).
+int check_pattern(int algo, const uint8_t* P, uint32_t m, bool length_first = false)
 {
-    std::vector<uint8_t> blob;
-    build_blob(blob, algo, P, m, halo, prefer_packed, sparse, so_off);
-    return blob;
+    if (algo < 0 || algo >= SMARTGPU_NUM_ALGOS) { set_error("unknown algorithm id %d", algo); return SMARTGPU_ERR_ARG; }
+    const bool na = m < min_pattern(algo);
+    if ((!na || length_first) && (!P || m < 1 || m > SMARTGPU_XSIZE)) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return SMARTGPU_ERR_ARG; }
+    if (na) { set_error("%s: not applicable for m < %u", kAlgoNames[algo], min_pattern(algo)); return SMARTGPU_NA; }
+    return SMARTGPU_OK;
 }
 
 int check_search_args(int algo, const uint8_t* P, uint32_t m, const smartgpu_text* text,
                       uint64_t off, uint64_t n)
 {
-    if (algo < 0 || algo >= SMARTGPU_NUM_ALGOS) { set_error("unknown algorithm id %d", algo); return SMARTGPU_ERR_ARG; }
-    if (m < min_pattern(algo)) { set_error("%s: not applicable for m < %u", kAlgoNames[algo], min_pattern(algo)); return SMARTGPU_NA; }
-    if (!P || m < 1 || m > SMARTGPU_XSIZE) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return SMARTGPU_ERR_ARG; }
+    const int rc = check_pattern(algo, P, m);
+    if (rc != SMARTGPU_OK) return rc;
     if (!text) { set_error("text handle is NULL"); return SMARTGPU_ERR_ARG; }
     if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the text (%llu bytes)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
     return SMARTGPU_OK;
 }
 
-sg::ScanArgs make_args(const smartgpu_plan* p, const smartgpu_text* text, uint64_t off, uint64_t n,
-                       int slot)
+// what a scan receives: a plan's words, its tables on the device and its count slot, over n bytes of the text from `off`
+sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob, unsigned long long* count, const smartgpu_text* text,
+                       uint64_t off, uint64_t n)
 {
-    sg::ScanArgs a;
-    a.text = text->data();
-    a.s_begin = off;
-    a.s_end = (n >= p->m) ? off + n - p->m + 1 : off;  // no window fits: empty range
-    a.m = p->m;
-    a.halo = p->halo;
-    a.fp_off = 0;
-    a.prefer_packed = p->prefer_packed;
-    a.sparse = p->sparse;
-    a.so_off = p->so_off;
-    a.blob = p->blob;
-    a.count = p->slot_ptr(slot);
-    return a;
+    const uint64_t s_end = (n >= m) ? off + n - m + 1 : off;  // no window fits: empty range
+    return sg::ScanArgs{text->data(), off, s_end, m, pw.halo, /* fp_off: launch_scan */ 0, pw.prefer_packed, pw.sparse, pw.so_off, blob, count};
 }
 
 }  // namespace
@@ -781,9 +793,7 @@ int smartgpu_text_read(const smartgpu_text* t, uint64_t off, uint64_t len, void*
 /* ---- plans ------------------------------------------------------------ */
 smartgpu_plan* smartgpu_plan_create(int algo, const uint8_t* P, uint32_t m, int device)
 {
-    if (algo < 0 || algo >= SMARTGPU_NUM_ALGOS) { set_error("unknown algorithm id %d", algo); return nullptr; }
-    if (!P || m < 1 || m > SMARTGPU_XSIZE) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return nullptr; }
-    if (m < min_pattern(algo)) { set_error("%s: not applicable for m < %u", kAlgoNames[algo], min_pattern(algo)); return nullptr; }
+    if (check_pattern(algo, P, m, true) != SMARTGPU_OK) return nullptr;
     DeviceCtx* d = device_ctx(device);
     if (!d) return nullptr;
     const double t0 = now_ms();
@@ -791,7 +801,8 @@ smartgpu_plan* smartgpu_plan_create(int algo, const uint8_t* P, uint32_t m, int 
     p->device = device;
     p->algo = algo;
     p->m = m;
-    const std::vector<uint8_t> blob = build_blob(algo, P, m, &p->halo, &p->prefer_packed, &p->sparse, &p->so_off);
+    std::vector<uint8_t> blob;
+    p->words = build_blob(blob, algo, P, m);
     bool ok = hipMalloc(reinterpret_cast<void**>(&p->blob), blob.size()) == hipSuccess &&
               hipMalloc(reinterpret_cast<void**>(&p->results), sizeof(unsigned long long) * sg::kResultSlots) == hipSuccess;
     if (ok) {
@@ -839,7 +850,7 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
         }
         HIP_TRY(hipEventRecord(p->ev0[slot], d->stream), return SMARTGPU_ERR_HIP);
     }
-    const sg::ScanArgs a = make_args(p, text, off, n, slot);
+    const sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(slot), text, off, n);
     HIP_TRY(sg::launch_scan(p->algo, a, d->num_cus, d->stream, text->codes()), return SMARTGPU_ERR_HIP);
     if (timed) HIP_TRY(hipEventRecord(p->ev1[slot], d->stream), return SMARTGPU_ERR_HIP);
     return SMARTGPU_OK;
@@ -868,18 +879,18 @@ int smartgpu_plan_result(smartgpu_plan* p, int slot, uint64_t* count, double* ke
 
 const char* smartgpu_plan_kernel_name(const smartgpu_plan* p)
 {
-    return p ? sg::scan_kernel_name(p->algo, p->m, p->prefer_packed != 0, p->so_off != 0, p->halo) : nullptr;
+    return p ? sg::scan_kernel_name(p->algo, p->m, p->words.prefer_packed != 0, p->words.so_off != 0, p->words.halo) : nullptr;
 }
 
 const char* smartgpu_kernel_for(int algo, const uint8_t* P, uint32_t m)
 {
-    if (algo < 0 || algo >= SMARTGPU_NUM_ALGOS || !P || m < 1 || m > SMARTGPU_XSIZE || m < min_pattern(algo)) {
+    if (check_pattern(algo, P, m) != SMARTGPU_OK) {
         set_error("kernel_for: algorithm %d / pattern length %u not applicable", algo, m);
         return nullptr;
     }
-    uint32_t halo = 0, prefer_packed = 0, sparse = 0, so_off = 0;
-    (void)build_blob(algo, P, m, &halo, &prefer_packed, &sparse, &so_off);
-    return sg::scan_kernel_name(algo, m, prefer_packed != 0, so_off != 0, halo);
+    std::vector<uint8_t> blob;
+    const sg::PlanWords pw = build_blob(blob, algo, P, m);
+    return sg::scan_kernel_name(algo, m, pw.prefer_packed != 0, pw.so_off != 0, pw.halo);
 }
 
 void* smartgpu_plan_result_device_ptr(smartgpu_plan* p) { return p ? p->slot_ptr(0) : nullptr; }
@@ -929,21 +940,9 @@ int smartgpu_probe_read_ms(const smartgpu_text* t, int reps, double* ms_per_pass
     if (!d) return SMARTGPU_ERR_HIP;
     unsigned long long* sink = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sink), 8), return SMARTGPU_ERR_HIP);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipEventCreate(&e1), return SMARTGPU_ERR_HIP);
-    sg::launch_probe_read(t->data(), t->n, sink, d->num_cus, d->stream);  // warm-up
-    hipEventRecord(e0, d->stream);
-    for (int i = 0; i < reps; ++i) sg::launch_probe_read(t->data(), t->n, sink, d->num_cus, d->stream);
-    hipEventRecord(e1, d->stream);
-    HIP_TRY(hipEventSynchronize(e1), return SMARTGPU_ERR_HIP);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *ms_per_pass = ms / reps;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
+    const int rc = probe_read_ms(d, t->data(), t->n, sink, reps, ms_per_pass);
     hipFree(sink);
-    return SMARTGPU_OK;
+    return rc;
 }
 
 int smartgpu_tune(int key, int value)
@@ -1018,7 +1017,7 @@ bool batch_reserve(DeviceCtx* d, size_t blob_bytes, size_t k)
     return true;
 }
 
-struct BatchPlan { uint32_t halo, prefer_packed, sparse, so_off; size_t off; };
+struct BatchPlan { sg::PlanWords words; size_t off; };  // off: the blob inside the arena
 // the staging buffer of a set of K patterns: [table blobs ...][K argument records][K launch-order indices]
 size_t batch_tail_offset(const DeviceCtx* d, uint32_t K)
 {
@@ -1042,7 +1041,7 @@ int batch_upload(const std::vector<DeviceCtx*>& ds, int algo, const uint8_t* con
     plans.resize(K);
     // the blobs of one algorithm and one length are equally long (multiples of 256): size the arena from the first
     if (!P[0]) { set_error("pattern 0 is NULL"); return SMARTGPU_ERR_ARG; }
-    build_blob(blob, algo, P[0], m, &plans[0].halo, &plans[0].prefer_packed, &plans[0].sparse, &plans[0].so_off);
+    plans[0].words = build_blob(blob, algo, P[0], m);
     const size_t room = batch_tail_offset(d0, K);  // the tail of the staging buffer holds the set's argument records and launch order
     if (blob.size() > room) { set_error("a table blob of %zu bytes exceeds the staging buffer", blob.size()); return SMARTGPU_ERR_NOMEM; }
     size_t arena_min = 0;
@@ -1073,7 +1072,7 @@ int batch_upload(const std::vector<DeviceCtx*>& ds, int algo, const uint8_t* con
     for (uint32_t k = 0; k < K; ++k) {
         if (!P[k]) { set_error("pattern %u is NULL", k); return SMARTGPU_ERR_ARG; }
         const double t0 = now_ms();
-        if (k) build_blob(blob, algo, P[k], m, &plans[k].halo, &plans[k].prefer_packed, &plans[k].sparse, &plans[k].so_off);
+        if (k) plans[k].words = build_blob(blob, algo, P[k], m);
         if (total + blob.size() + 256 + K * sizeof(sg::BatchItem) > arena_min) {  // rerouted patterns carry masks the first did not
             set_error("batch: the table arena (%zu bytes) is too small for this pattern set", arena_min);
             return SMARTGPU_ERR_NOMEM;
@@ -1092,25 +1091,6 @@ int batch_upload(const std::vector<DeviceCtx*>& ds, int algo, const uint8_t* con
         for (uint32_t k = 0; k < K; ++k) pre_ms[k] = host_ms[k] + up_ms;
     return SMARTGPU_OK;
 }
-
-sg::ScanArgs batch_args(const BatchPlan& bp, const DeviceCtx* d, uint32_t m, const smartgpu_text* text, uint64_t off, uint64_t n,
-                        unsigned long long* slot)
-{
-    sg::ScanArgs a;
-    a.text = text->data();
-    a.s_begin = off;
-    a.s_end = (n >= m) ? off + n - m + 1 : off;
-    a.m = m;
-    a.halo = bp.halo;
-    a.fp_off = 0;
-    a.prefer_packed = bp.prefer_packed;
-    a.sparse = bp.sparse;
-    a.so_off = bp.so_off;
-    a.blob = d->arena + bp.off;
-    a.count = slot;
-    return a;
-}
-
 
 // Enqueue the searches of a pattern set on the device's stream; counts go to d->batch_counts[0..K).
 // Small texts (SMART's stock 1 MiB: a search is 64 workgroups and 3 us, less than its launch costs the host):
@@ -1134,32 +1114,26 @@ int batch_enqueue(DeviceCtx* d, int algo, const std::vector<BatchPlan>& plans, u
     if (n > kOneGridMaxText || K == 1 || each) {
         if (timed) HIP_TRY(hipEventRecord(d->batch_events[0], d->stream), return SMARTGPU_ERR_HIP);
         for (uint32_t k = 0; k < K; ++k) {
-            const sg::ScanArgs a = batch_args(plans[k], d, m, text, off, n, d->batch_counts + k);
+            const sg::ScanArgs a = make_args(plans[k].words, m, d->arena + plans[k].off, d->batch_counts + k, text, off, n);
             HIP_TRY(sg::launch_scan(algo, a, d->num_cus, d->stream, text->codes()), return SMARTGPU_ERR_HIP);
             if (timed) HIP_TRY(hipEventRecord(d->batch_events[k + 1], d->stream), return SMARTGPU_ERR_HIP);
             if (groups_out) groups_out->push_back({k, 1u});
         }
         return SMARTGPU_OK;
     }
-    // one grid per group of patterns whose plans lead to the same kernel and grid
-    // (the key is what launch_scan derives kernel, template arguments and grid from: prefer_packed — for KMP the window
-    // of its table —, the Shift-Or reroute, sparse, and for BNDM / BNDML the q of bndm_scan that travels as halo;
-    // a mixed set ran every BNDM pattern with the first pattern's q)
-    // (... and for Horspool the q of its q-gram table, bits 8.. of halo)
-    const bool halo_is_q = algo == SMARTGPU_BNDM || algo == SMARTGPU_BNDML;
-    auto key = [&](uint32_t k) {
-        const uint32_t pp = algo == SMARTGPU_KMP ? plans[k].prefer_packed : (plans[k].prefer_packed ? 1u : 0u);
-        const uint32_t variant = halo_is_q ? plans[k].halo & 0x1FFu : algo == SMARTGPU_HOR ? (plans[k].halo >> 8) & 0xFFu : 0u;  // BNDM: q and the gram-window mark
-        return (static_cast<uint64_t>(pp) << 20) | (variant << 8) | (plans[k].so_off ? 2u : 0u) | (plans[k].sparse ? 1u : 0u);
-    };
+    // one grid per group of patterns whose plans lead to the same kernel, template arguments and grid: sg::group_key (launch.hip)
+    std::vector<uint64_t> key(K);
     std::vector<uint32_t> order(K);
-    for (uint32_t k = 0; k < K; ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return key(x) < key(y); });
+    for (uint32_t k = 0; k < K; ++k) {
+        key[k] = sg::group_key(algo, m, plans[k].words, text->codes());
+        order[k] = k;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
     // (in the staging buffer's tail: its front may still be on its way to the arena — batch_upload does not wait)
     sg::BatchItem* host_items = reinterpret_cast<sg::BatchItem*>(d->pinned + batch_tail_offset(d, K));
     for (uint32_t i = 0; i < K; ++i) {
         const BatchPlan& bp = plans[order[i]];
-        const sg::ScanArgs pa = sg::prepare_scan_args(algo, batch_args(bp, d, m, text, off, n, d->batch_counts));
+        const sg::ScanArgs pa = sg::prepare_scan_args(algo, make_args(bp.words, m, d->arena, d->batch_counts, text, off, n));
         host_items[i] = sg::BatchItem{bp.off, order[i], pa.halo, pa.fp_off, pa.prefer_packed, pa.sparse, pa.so_off};
     }
     sg::BatchItem* dev_items = reinterpret_cast<sg::BatchItem*>(d->arena + d->arena_bytes - ((static_cast<size_t>(K) * sizeof(sg::BatchItem) + 255) & ~size_t(255)));
@@ -1169,11 +1143,10 @@ int batch_enqueue(DeviceCtx* d, int algo, const std::vector<BatchPlan>& plans, u
     if (timed) HIP_TRY(hipEventRecord(d->batch_events[ev++], d->stream), return SMARTGPU_ERR_HIP);
     for (uint32_t i = 0; i < K;) {
         uint32_t j = i;
-        while (j < K && key(order[j]) == key(order[i])) ++j;
+        while (j < K && key[order[j]] == key[order[i]]) ++j;
         // the set's common arguments: blob = arena base, count = first slot (the items add their own), and the
         // group's plan fields, which choose kernel and grid
-        sg::ScanArgs first = batch_args(plans[order[i]], d, m, text, off, n, d->batch_counts);
-        first.blob = d->arena;
+        const sg::ScanArgs first = make_args(plans[order[i]].words, m, d->arena, d->batch_counts, text, off, n);
         // gridDim.y holds at most 65535: a larger group goes as several grids over slices of its items
         for (uint32_t lo = i; lo < j; lo += kOneGridMaxY)
             HIP_TRY(sg::launch_scan_set(algo, first, dev_items + lo, std::min(kOneGridMaxY, j - lo), d->num_cus, d->stream, text->codes()), return SMARTGPU_ERR_HIP);
@@ -1266,7 +1239,7 @@ int smartgpu_find64(const uint8_t* P, uint32_t m, const smartgpu_text* text, uin
     }
     unsigned long long total = 0;
     if (r == SMARTGPU_OK) {
-        sg::ScanArgs a = make_args(p, text, off, n, 0);
+        sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(0), text, off, n);
         a.fp_off = sg::kTableOff;  // EPSM blob: the fingerprint follows the pattern slot
         bool ok = hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
                   sg::launch_find(a, out, cap, d->num_cus, d->stream) == hipSuccess &&
@@ -1550,9 +1523,8 @@ int smartgpu_msearch_batch64(int algo, const uint8_t* const* P, uint32_t m, uint
     if (!text) { set_error("text handle is NULL"); return SMARTGPU_ERR_ARG; }
     if (!P || K < 1 || !counts || !P[0]) { set_error("batch: P/counts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
     if (K > kBatchMaxPatterns) { set_error("batch: %u patterns in one set (at most %u)", K, kBatchMaxPatterns); return SMARTGPU_ERR_ARG; }
-    if (algo < 0 || algo >= SMARTGPU_NUM_ALGOS) { set_error("unknown algorithm id %d", algo); return SMARTGPU_ERR_ARG; }
-    if (m < min_pattern(algo)) { set_error("%s: not applicable for m < %u", kAlgoNames[algo], min_pattern(algo)); return SMARTGPU_NA; }
-    if (m < 1 || m > SMARTGPU_XSIZE) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return SMARTGPU_ERR_ARG; }
+    const int rc_p = check_pattern(algo, P[0], m);
+    if (rc_p != SMARTGPU_OK) return rc_p;
     const int k = static_cast<int>(text->devices.size());
     // preprocessing: the K tables are built ONCE on the host and copied to the arena of every (distinct) device
     std::vector<BatchPlan> plans;
@@ -2036,21 +2008,8 @@ int smartgpu_ptext_probe_read_ms(const smartgpu_ptext* t, int reps, double* ms_p
     const uint8_t* first = reinterpret_cast<const uint8_t*>(t->plane(0));
     const uint64_t bytes = static_cast<uint64_t>(t->planes - 1) * sg::plane_stride(t->n) + sg::plane_bytes(t->n);
     if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
-    unsigned long long* sink = d->batch_counts;  // probe_read adds to it practically never; every search zeroes its slots first
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipEventCreate(&e1), return SMARTGPU_ERR_HIP);
-    sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);  // warm-up
-    hipEventRecord(e0, d->stream);
-    for (int i = 0; i < reps; ++i) sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);
-    hipEventRecord(e1, d->stream);
-    HIP_TRY(hipEventSynchronize(e1), return SMARTGPU_ERR_HIP);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *ms_per_pass = ms / reps;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    return SMARTGPU_OK;
+    // (the sink: probe_read adds to it practically never; every search zeroes its slots first)
+    return probe_read_ms(d, first, bytes, d->batch_counts, reps, ms_per_pass);
 }
 
 int smartgpu_psearch64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n, uint64_t* count,

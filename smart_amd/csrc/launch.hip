@@ -1,5 +1,6 @@
-// launch.hip — the dispatcher between the C-ABI layer (api.cpp) and the kernel families (k_*.hip): which kernel a
-// plan's fields lead to (launch_scan, scan_kernel_name), the tuning knobs, pattern sets in one grid.  No kernel here.
+// launch.hip — the dispatcher between the C-ABI layer (api.cpp) and the kernel families (k_*.hip): which launcher a plan's
+// words lead to is decided ONCE, in route() (route.hpp) — launch_scan launches it, scan_kernel_name names it, group_key groups
+// the patterns of a set in one grid by it (tests/test_dispatch.py holds them together); the tuning knobs.  No kernel here.
 //
 // Every kernel computes the same function
 //     count(P,T) = |{ s in [s_begin, s_end) : T[s..s+m) == P }|
@@ -31,6 +32,7 @@
 // Earlier designs of the serial kernels (so_scan, kmp_scan, so_runs64, so_runs1, kmp_links_runs,
 // kmp_runs1) live in kernels_ab.inc / k_ab.hip and only in the A/B build (make AB=1, smartgpu_tune).
 #include "launch_common.hpp"
+#include "route.hpp"
 
 #include "../../include/smartgpu.h"
 
@@ -92,45 +94,101 @@ static int hor_regime(uint32_t m, int algo = SMARTGPU_HOR)
     return m <= packed_max_m(algo) ? 3 : 1;  // bank-private kernel: only on request
 }
 
-const char* scan_kernel_name(int algo, uint32_t m, bool prefer_packed, bool so_masks, uint32_t halo)
+// The one decision tree: launch_scan launches what it returns, scan_kernel_name names it, group_key groups by it.
+Route route(int algo, uint32_t m, const PlanWords& w, TextCodes codes)
 {
-#ifdef SMARTGPU_AB
-    const char* const so_name = g_tune[6] == 1 ? "so_scan" : g_tune[6] == 2 ? "so_runs64" : g_tune[6] == 4 ? "so_runs1" : "so_runs";
-    const char* const sa_name = (g_tune[6] == 3 || g_tune[6] == 4) ? "so_runs1" : "so_runs";
-    const char* const kmp_name = (g_tune[3] == 1 && m <= 40) ? "kmp_scan" : g_tune[3] == 2 ? "kmp_links_runs" : g_tune[3] == 3 ? "kmp_runs1" : "kmp_runs";
-    const char* const reroute_name = g_tune[6] == 4 ? "so_runs1" : "so_runs";
-#else
-    const char* const so_name = "so_runs";
-    const char* const sa_name = "so_runs";
-    const char* const kmp_name = "kmp_runs";
-    const char* const reroute_name = "so_runs";
-#endif
-    if (so_masks && g_tune[0] == 0) return reroute_name;
-    const bool pk = prefer_packed && g_tune[0] == 0;
+    // A pattern over two or three symbols, 16 bytes or longer: no byte, pair or dword of it tells a
+    // window from its neighbours, so the skip kernels move one or two bytes at a time and the packed
+    // matcher tests all four fingerprint dwords at every alignment (33-45 % on rand2, all of them).
+    // The branch-free bit-parallel runs kernel does not care what the bytes are (66-70 %): plans of
+    // such patterns carry Shift-Or masks as well (api.cpp build_blob) and count with it.
+    if (w.so_off != 0 && algo != SMARTGPU_SO && algo != SMARTGPU_SA && g_tune[0] == 0) return {Launcher::so_runs, 0};
+    const bool pk = w.prefer_packed && g_tune[0] == 0;
+    // a TEXT of at most four byte values: Horspool and Boyer-Moore on its grams (k_horg.hip, k_bmg.hip) — eight one-bit symbols from
+    // 16 bytes on (two values), four two-bit symbols from 8; a window shorter than two grams cannot be shifted by more than its own
+    // rule allows (m - Q + 1).  tune(2, 4): never (A/B).  Any other text: Horspool's q-gram (hash) table, or the byte tables.
+    const int gram = g_tune[2] == 4 ? 0 : ((codes.one & 0xFFu) != 0xFFu && m >= 16) ? 1 : (codes.shift < 7 && m >= 8) ? 2 : 0;
     switch (algo) {
-        case SMARTGPU_TUNEDBM:
-        case SMARTGPU_HOR: {
-            const int r = pk ? 3 : hor_regime(m);
-            return r == 3 ? "packed_scan" : r == 2 ? "hor_scan_bp" : "hor_scan";
+        case SMARTGPU_TUNEDBM:  // hor_scan<.., 0> is Tuned BM's loop (see the kernel's comment; tunedbm.c:38-62 is Horspool's
+        case SMARTGPU_HOR: {    // shift behind an unrolled skip loop: on grams the same kernel)
+            const int regime = pk ? 3 : hor_regime(m);
+            if (regime == 3) return {Launcher::packed, SMARTGPU_HOR};
+#ifdef SMARTGPU_AB
+            if (regime == 2) return {Launcher::hor_bp, 0};
+#endif
+            if (gram) return {Launcher::hor_gram, gram};
+            return {Launcher::hor, (int)hor_q(w)};  // q: the plan's q-gram table (api.cpp), 0: the byte table
         }
+        case SMARTGPU_KR:
+            // Short patterns, like the skip algorithms': the packed matcher (72-77 %).  Only the low m bits
+            // of the rolled hash can be compared, so one window end in 2^m is confirmed (m = 8: 32 %,
+            // m = 12: 50 % of 8 TB/s), and below 8 the rolling form needs the outgoing byte (15 %).
+            if (m < 16 && g_tune[0] != 1) return {Launcher::packed, SMARTGPU_HOR};
+            return {Launcher::kr, 0};
         case SMARTGPU_HASH3:
         case SMARTGPU_HASH5:
         case SMARTGPU_HASH8:
         case SMARTGPU_RAITA:
-        case SMARTGPU_QS: return (pk || hor_regime(m, algo) == 3) ? "packed_scan" : "hor_scan";
-        case SMARTGPU_SA: return sa_name;
-        case SMARTGPU_KR: return (m < 16 && g_tune[0] != 1) ? "packed_scan" : "hor_scan_bp";
-        case SMARTGPU_BM: return (pk || m == 1 || (m <= packed_max_m(SMARTGPU_BM) && g_tune[0] != 1)) ? "packed_scan" : "bm_scan";
-        case SMARTGPU_KMP: return kmp_name;
-        case SMARTGPU_SO: return so_name;
+        case SMARTGPU_QS:  // the Horspool family on hor_scan's tiles; short patterns: packed regime as HOR
+            if (pk || hor_regime(m, algo) == 3) return {Launcher::packed, SMARTGPU_HOR};
+            return {Launcher::hor_var, algo};
+        case SMARTGPU_BM:
+            // m = 1 always: bm_scan reads the byte before the window's last along with it, and a one-byte
+            // window has none (at a tile's first byte that read would leave the tile region)
+            if (m == 1 || (m <= packed_max_m(SMARTGPU_BM) && g_tune[0] != 1) || pk) return {Launcher::packed, SMARTGPU_BM};
+            if (gram) return {Launcher::bm_gram, gram};
+            return {Launcher::bm, 0};
         case SMARTGPU_BNDML:
-            if (m > 32) return pk ? "packed_scan" : "bndml_scan";
-            [[fallthrough]];
+            if (m > 32) return pk ? Route{Launcher::packed, SMARTGPU_BNDM} : Route{Launcher::bndml, 0};  // multi-word vectors
+            [[fallthrough]];  // m <= 32 is plain BNDM (bndml.c:44-75)
         case SMARTGPU_SBNDM:
         case SMARTGPU_BNDM:
-            if (algo != SMARTGPU_SBNDM && (halo & kBndmGramWindow) && !pk) return "bndm_scan";  // a one-gram window (api.cpp)
-            return (pk || (m <= packed_max_m(SMARTGPU_BNDM) && g_tune[0] != 1)) ? "packed_scan" : algo == SMARTGPU_SBNDM ? "sbndm_scan" : "bndm_scan";
-        case SMARTGPU_EPSM: return "packed_scan";
+            if (algo != SMARTGPU_SBNDM && (w.halo & kBndmGramWindow) && !pk) return {Launcher::bndm, 0};  // a one-gram window (api.cpp): bndm_scan at any length
+            if ((m <= packed_max_m(SMARTGPU_BNDM) && g_tune[0] != 1) || pk) return {Launcher::packed, SMARTGPU_BNDM};
+            return {algo == SMARTGPU_SBNDM ? Launcher::sbndm : Launcher::bndm, 0};
+        case SMARTGPU_SA:  // Shift-And counts in the complemented, Shift-Or form (api.cpp build_blob); its own AND form
+        case SMARTGPU_SO:  // (so_runs1<.., AND = true>, masks after the Shift-Or ones) is in the A/B build: tune(6,3)
+            return {Launcher::so_runs, 0};
+        case SMARTGPU_KMP: return {Launcher::kmp_runs, 0};  // per-lane runs streamed through LDS
+    }
+    return {Launcher::packed, SMARTGPU_EPSM};  // EPSM is the packed matcher
+}
+
+// The Route (so a regime that route() learns to tell apart never shares a grid) below the words themselves: sparse (tile_wgs),
+// KMP's window, BNDM's q and gram mark, Horspool's q — and the packed and reroute flags as they stand, whatever g_tune makes of
+// them, so that a set falls into the same groups under every setting (a mixed set ran every BNDM pattern with the
+// first pattern's q, because the key of that time did not know that halo carries it).
+uint64_t group_key(int algo, uint32_t m, const PlanWords& w, TextCodes codes)
+{
+    const Route r = route(algo, m, w, codes);
+    const uint64_t pp = algo == SMARTGPU_KMP ? w.prefer_packed : (w.prefer_packed ? 1u : 0u);
+    const uint64_t variant = (algo == SMARTGPU_BNDM || algo == SMARTGPU_BNDML) ? bndm_q_and_mark(w) : algo == SMARTGPU_HOR ? hor_q(w) : 0u;
+    return (pp << 40) | (variant << 28) | (w.so_off ? 1ull << 21 : 0) | (w.sparse ? 1ull << 20 : 0) | ((uint64_t)r.to << 12) | (uint64_t)(r.arg & 0xFFF);
+}
+
+const char* scan_kernel_name(int algo, uint32_t m, bool prefer_packed, bool so_masks, uint32_t halo)
+{
+    if (algo < 0 || algo >= SMARTGPU_NUM_ALGOS) return "?";
+    switch (route(algo, m, PlanWords{halo, prefer_packed, 0, so_masks}, TextCodes()).to) {  // (the gram launchers: their base kernel's name)
+        case Launcher::so_runs:
+#ifdef SMARTGPU_AB
+            if (algo == SMARTGPU_SO) return g_tune[6] == 1 ? "so_scan" : g_tune[6] == 2 ? "so_runs64" : g_tune[6] == 4 ? "so_runs1" : "so_runs";
+            if (algo == SMARTGPU_SA) return (g_tune[6] == 3 || g_tune[6] == 4) ? "so_runs1" : "so_runs";
+            return g_tune[6] == 4 ? "so_runs1" : "so_runs";  // the rerouted patterns
+#endif
+            return "so_runs";
+        case Launcher::kmp_runs:
+#ifdef SMARTGPU_AB
+            return (g_tune[3] == 1 && m <= 40) ? "kmp_scan" : g_tune[3] == 2 ? "kmp_links_runs" : g_tune[3] == 3 ? "kmp_runs1" : "kmp_runs";
+#endif
+            return "kmp_runs";
+        case Launcher::packed: return "packed_scan";
+        case Launcher::hor: case Launcher::hor_var: case Launcher::hor_gram: return "hor_scan";
+        case Launcher::hor_bp: case Launcher::kr: return "hor_scan_bp";
+        case Launcher::bm: case Launcher::bm_gram: return "bm_scan";
+        case Launcher::bndm: return "bndm_scan";
+        case Launcher::sbndm: return "sbndm_scan";
+        case Launcher::bndml: return "bndml_scan";
     }
     return "?";
 }
@@ -168,95 +226,44 @@ ScanArgs prepare_scan_args(int algo, ScanArgs a)
 hipError_t launch_scan(int algo, const ScanArgs& a_in, int num_cus, hipStream_t stream, TextCodes codes)
 {
     if (a_in.s_end <= a_in.s_begin) return hipSuccess;
-    const bool rerouted = a_in.so_off != 0 && algo != SMARTGPU_SO && algo != SMARTGPU_SA;  // plans of 2-3-symbol patterns (api.cpp)
-    const ScanArgs a = prepare_scan_args(algo, a_in);
-    const uint32_t m = a.m;
-    // A pattern over two or three symbols, 16 bytes or longer: no byte, pair or dword of it tells a
-    // window from its neighbours, so the skip kernels move one or two bytes at a time and the packed
-    // matcher tests all four fingerprint dwords at every alignment (33-45 % on rand2, all of them).
-    // The branch-free bit-parallel runs kernel does not care what the bytes are (66-70 %): plans of
-    // such patterns carry Shift-Or masks as well (api.cpp build_blob) and count with it.
-    if (rerouted && g_tune[0] == 0) {
+    if (algo < 0 || algo >= SMARTGPU_NUM_ALGOS) return hipErrorInvalidValue;
+    const ScanArgs a = prepare_scan_args(algo, a_in);  // a.fp_off, a.so_off of SO / SA; a.halo without the plan's marks
+    const Route r = route(algo, a.m, PlanWords{a_in.halo, a_in.prefer_packed, a_in.sparse, a_in.so_off}, codes);
+    switch (r.to) {
+        case Launcher::so_runs: {
 #ifdef SMARTGPU_AB
-        if (g_tune[6] == 4) {  // the rerouted patterns on so_runs1 too
-            bool handled = false;
-            const hipError_t e = launch_ab_so(SMARTGPU_HOR, a, num_cus, stream, &handled);
-            if (handled) return e;
-        }
-#endif
-        return launch_so_runs(a, false, num_cus, stream, codes);
-    }
-    const bool pk = a.prefer_packed && g_tune[0] == 0;
-    switch (algo) {
-        case SMARTGPU_TUNEDBM:  // hor_scan<.., 0> is Tuned BM's loop (see the kernel's comment)
-        case SMARTGPU_HOR: {
-            const int regime = pk ? 3 : hor_regime(m);
-            if (regime == 3) return launch_packed(SMARTGPU_HOR, a, num_cus, stream);  // a.fp_off: prepare_scan_args
-#ifdef SMARTGPU_AB
-            if (regime == 2) return launch_hor_bp(a, num_cus, stream);
-#endif
-            // a TEXT of at most four byte values: Horspool on its grams (k_horg.hip) — eight one-bit symbols from 16 bytes on (two
-            // values), four two-bit symbols from 8; a window shorter than two grams cannot be shifted by more than its own rule
-            // allows (m - Q + 1).  tune(2, 4): never (A/B).  Any other text: the plan's q-gram (hash) table, or the byte table.
-            if (g_tune[2] != 4) {  // (Tuned BM — tunedbm.c:38-62 — is Horspool's shift behind an unrolled skip loop: on grams the same kernel)
-                const int gram = ((codes.one & 0xFFu) != 0xFFu && m >= 16) ? 1 : (codes.shift < 7 && m >= 8) ? 2 : 0;
-                if (gram) return launch_hor_gram(a, gram, num_cus, stream);
+            const bool own = algo == SMARTGPU_SO || algo == SMARTGPU_SA;  // else: a rerouted pattern, on so_runs1 too with tune(6,4)
+            if (own || g_tune[6] == 4) {
+                bool handled = false;
+                const hipError_t e = launch_ab_so(own ? algo : SMARTGPU_HOR, a, num_cus, stream, &handled);
+                if (handled) return e;
             }
-            return launch_hor(a, (a_in.halo >> 8) & 0xFFu, num_cus, stream);  // q: the plan's q-gram table (api.cpp), 0: the byte table
-        }
-        case SMARTGPU_KR:
-            // Short patterns, like the skip algorithms': the packed matcher (72-77 %).  Only the low m bits
-            // of the rolled hash can be compared, so one window end in 2^m is confirmed (m = 8: 32 %,
-            // m = 12: 50 % of 8 TB/s), and below 8 the rolling form needs the outgoing byte (15 %).
-            if (m < 16 && g_tune[0] != 1) return launch_packed(SMARTGPU_HOR, a, num_cus, stream);
-            return launch_kr(a, num_cus, stream);
-        case SMARTGPU_HASH3:
-        case SMARTGPU_HASH5:
-        case SMARTGPU_HASH8:
-        case SMARTGPU_RAITA:
-        case SMARTGPU_QS:  // the Horspool family on hor_scan's tiles; short patterns: packed regime as HOR
-            if (pk || hor_regime(m, algo) == 3) return launch_packed(SMARTGPU_HOR, a, num_cus, stream);
-            return launch_hor_var(algo, a, num_cus, stream);
-        case SMARTGPU_BM:
-            // m = 1 always: bm_scan reads the byte before the window's last along with it, and a one-byte
-            // window has none (at a tile's first byte that read would leave the tile region)
-            if (m == 1 || (m <= packed_max_m(SMARTGPU_BM) && g_tune[0] != 1) || pk) return launch_packed(SMARTGPU_BM, a, num_cus, stream);
-            // a TEXT of at most four byte values: Boyer-Moore on its grams (k_bmg.hip), as Horspool above.  tune(2, 4): never (A/B)
-            if (g_tune[2] != 4) {
-                const int gram = ((codes.one & 0xFFu) != 0xFFu && m >= 16) ? 1 : (codes.shift < 7 && m >= 8) ? 2 : 0;
-                if (gram) return launch_bm_gram(a, gram, num_cus, stream);
-            }
-            return launch_bm(a, num_cus, stream);
-        case SMARTGPU_BNDML:
-            if (m > 32) {  // multi-word vectors; m <= 32 is plain BNDM (bndml.c:44-75): falls through
-                if (pk) return launch_packed(SMARTGPU_BNDM, a, num_cus, stream);
-                return launch_bndml(a, num_cus, stream);
-            }
-            [[fallthrough]];
-        case SMARTGPU_SBNDM:
-        case SMARTGPU_BNDM:
-            if (algo != SMARTGPU_SBNDM && (a_in.halo & kBndmGramWindow) && !pk) return launch_bndm(a, num_cus, stream, codes);  // a one-gram window
-            if ((m <= packed_max_m(SMARTGPU_BNDM) && g_tune[0] != 1) || pk) return launch_packed(SMARTGPU_BNDM, a, num_cus, stream);
-            if (algo == SMARTGPU_SBNDM) return launch_sbndm(a, num_cus, stream);
-            return launch_bndm(a, num_cus, stream, codes);
-        case SMARTGPU_SA:  // Shift-And counts in the complemented, Shift-Or form (api.cpp build_blob); its own AND form
-        case SMARTGPU_SO: {  // (so_runs1<.., AND = true>, masks after the Shift-Or ones) is in the A/B build: tune(6,3)
-#ifdef SMARTGPU_AB
-            bool handled = false;
-            const hipError_t e = launch_ab_so(algo, a, num_cus, stream, &handled);
-            if (handled) return e;
 #endif
-            return launch_so_runs(a, false, num_cus, stream, codes);  // a.so_off: prepare_scan_args
+            return launch_so_runs(a, false, num_cus, stream, codes);
         }
-        case SMARTGPU_KMP: {
+        case Launcher::kmp_runs: {
 #ifdef SMARTGPU_AB
             bool handled = false;
             const hipError_t e = launch_ab_kmp(a, num_cus, stream, &handled);
             if (handled) return e;
 #endif
-            return launch_kmp_runs(a, num_cus, stream, codes);  // per-lane runs streamed through LDS
+            return launch_kmp_runs(a, num_cus, stream, codes);
         }
-        case SMARTGPU_EPSM: return launch_packed(SMARTGPU_EPSM, a, num_cus, stream, codes);  // a.fp_off: prepare_scan_args
+        case Launcher::packed: return launch_packed(r.arg, a, num_cus, stream, r.arg == SMARTGPU_EPSM ? codes : TextCodes());  // only EPSM's modes look at the text
+        case Launcher::hor: return launch_hor(a, (uint32_t)r.arg, num_cus, stream);
+        case Launcher::hor_var: return launch_hor_var(r.arg, a, num_cus, stream);
+        case Launcher::hor_gram: return launch_hor_gram(a, r.arg, num_cus, stream);
+        case Launcher::kr: return launch_kr(a, num_cus, stream);
+        case Launcher::bm: return launch_bm(a, num_cus, stream);
+        case Launcher::bm_gram: return launch_bm_gram(a, r.arg, num_cus, stream);
+        case Launcher::bndm: return launch_bndm(a, num_cus, stream, codes);
+        case Launcher::sbndm: return launch_sbndm(a, num_cus, stream);
+        case Launcher::bndml: return launch_bndml(a, num_cus, stream);
+#ifdef SMARTGPU_AB
+        case Launcher::hor_bp: return launch_hor_bp(a, num_cus, stream);
+#else
+        case Launcher::hor_bp: break;  // Horspool on the bank-private tiles: only in the A/B build
+#endif
     }
     return hipErrorInvalidValue;
 }
