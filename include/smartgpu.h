@@ -173,10 +173,19 @@ int smartgpu_find64(const uint8_t *P, uint32_t m, const smartgpu_text *text, uin
 /* Builds the algorithm's tables on the host and places them in HBM of `device`. */
 smartgpu_plan *smartgpu_plan_create(int algo, const uint8_t *P, uint32_t m, int device);
 void smartgpu_plan_free(smartgpu_plan *p);
-/* Enqueues one search of text[off..off+n) on the device's stream and returns
+/* Hands one search of text[off..off+n) to the device's stream and returns
  * without waiting; the count is ADDED to result slot `slot` (0 <= slot < 4096)
  * of the plan (slots start at zero; smartgpu_plan_reset() zeroes them again).
- * With `timed` != 0 the launch is bracketed by HIP events. */
+ * With `timed` != 0 the launch is bracketed by HIP events.
+ * Untimed streaming Horspool / Tuned BM launches over one range of one text with
+ * one pattern length may be held back until smartgpu_coalesce() of them have
+ * gathered and then run as ONE pass over the text (hor_multi_scan); the counts
+ * are the same.  A launch is complete no later than the next
+ * smartgpu_device_sync(), smartgpu_plan_result() or smartgpu_stream_mark() on its
+ * device; every other call that waits for, times, resets or frees what the launch
+ * touches sends it first as well.  A caller who synchronises by other means (the
+ * stream of smartgpu_stream_handle(), which switches this off for its device, or
+ * a device-wide synchronisation of their own) calls smartgpu_coalesce(0). */
 int smartgpu_plan_launch(smartgpu_plan *p, const smartgpu_text *text, uint64_t off, uint64_t n,
                          int slot, int timed);
 /* Waits for the stream and returns the count of `slot` (and, if the launch was
@@ -269,6 +278,14 @@ int smartgpu_probe_read_ms(const smartgpu_text *t, int reps, double *ms_per_pass
  *      compares only
  * Settings whose kernels exist only in the A/B build (libsmartgpu_ab.so) are refused by the product library. */
 int smartgpu_tune(int key, int value);
+
+/* How many queued smartgpu_plan_launch() calls share one pass over the text: 0 = none (every launch is sent at
+ * once), 2..8.  Returns the previous value, SMARTGPU_ERR_ARG for anything else.  Needs no device; what is pending
+ * is sent first. */
+int smartgpu_coalesce(int max_group);
+/* Of the launches on `device` that could share a pass: how many were seen, and how many kernels were sent for them
+ * (equal when nothing was coalesced).  Either pointer may be NULL. */
+int smartgpu_coalesce_stats(int device, uint64_t *launches, uint64_t *passes);
 
 /* Host-side preprocessing exposed for tests (same tables the kernels stage in
  * LDS): writes up to `cap` 32-bit entries, returns the number written or <0.

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "multi.hpp"
 #include "planes.hpp"
 #include "route.hpp"
 #include "tables.hpp"
@@ -651,7 +652,144 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
     return sg::ScanArgs{text->data(), off, s_end, m, pw.halo, /* fp_off: launch_scan */ 0, pw.prefer_packed, pw.sparse, pw.so_off, blob, count};
 }
 
+// ---- searches that share a pass over the text (k_horm.hip: hor_multi_scan) -------------------------------------------
+// A streaming Horspool scan runs at the rate the text can be read, so what is left to save lies BETWEEN searches: K plans
+// launched over the same text read it K times.  smartgpu_plan_launch therefore does not send a launch that would reach
+// launch_hor's streaming branch (route {hor, 0}, a sparse pattern); it queues the finished arguments per device under
+// (text, range, m, halo).  A key that has collected g_coalesce launches is sent at once as ONE hor_multi_scan — the GPU
+// never waits for a flush while full groups exist, and at most g_coalesce - 1 launches per key are ever pending.  Every
+// entry point that waits for, times, orders work on, or frees what is on the device's stream sends what is pending
+// first (flush_queue), in arrival order; a launch that is alone by then goes through launch_scan as it always did.
+// The queue holds device pointers of plans and texts: smartgpu_plan_free, _plan_set_result_buffer and _text_free flush.
+struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; };
+struct QueuedKey {
+    sg::ScanArgs key;  // text, s_begin, s_end, m, halo
+    uint32_t n = 0;
+    QueuedScan scans[sg::kMultiMax];
+    bool holds(const sg::ScanArgs& a) const { return key.text == a.text && key.s_begin == a.s_begin && key.s_end == a.s_end && key.m == a.m && key.halo == a.halo; }
+};
+struct LaunchQueue {
+    std::mutex mu;
+    static constexpr uint32_t kKeys = 8;  // a ninth key sends the oldest
+    uint32_t nkeys = 0;
+    QueuedKey keys[kKeys];  // in arrival order
+    void drop(uint32_t at) { for (--nkeys; at < nkeys; ++at) keys[at] = keys[at + 1]; }
+    bool off = false;             // smartgpu_stream_handle gave the stream out: its holder orders their own work on it
+    uint64_t launches = 0, passes = 0;  // eligible launches seen / kernels sent for them
+};
+LaunchQueue g_queue[kMaxDevices];
+// launches per pass: 0 = off.  8, the most a pass takes, is a choice: the sweep over 2 / 4 / 8 has not been run (profiles/coalesce/RESULTS.md)
+std::atomic<int> g_coalesce{8};
+
+// send one key's launches (q.mu held, the device current)
+hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
+{
+    hipError_t e = hipSuccess;
+    if (k.n == 1) {
+        e = sg::launch_scan(k.scans[0].algo, k.scans[0].a, d->num_cus, d->stream, k.scans[0].codes);
+    } else if (k.n > 1) {
+        sg::MultiArgs ma = {};
+        ma.text = k.key.text;
+        ma.s_begin = k.key.s_begin;
+        ma.s_end = k.key.s_end;
+        ma.m = k.key.m;
+        ma.halo = k.key.halo & 0xFFu;  // as prepare_scan_args: H without the plan's marks
+        ma.np = k.n;
+        for (uint32_t j = 0; j < k.n; ++j) {
+            ma.blob[j] = k.scans[j].a.blob;
+            ma.count[j] = k.scans[j].a.count;
+        }
+        e = sg::g_hor_multi(ma, d->num_cus, d->stream);
+    }
+    if (k.n && e == hipSuccess) ++q.passes;
+    k.n = 0;
+    return e;
+}
+
+// send everything that is pending on the device (which must be current), in arrival order
+hipError_t flush_queue(const DeviceCtx* d)
+{
+    LaunchQueue& q = g_queue[d->device];
+    std::lock_guard<std::mutex> lock(q.mu);
+    hipError_t err = hipSuccess;
+    for (uint32_t i = 0; i < q.nkeys; ++i) {
+        const hipError_t e = send_key(d, q, q.keys[i]);
+        if (e != hipSuccess && err == hipSuccess) err = e;
+    }
+    q.nkeys = 0;
+    return err;
+}
+
+// the same for every device that has been used, whichever is current (smartgpu_tune, smartgpu_coalesce: no device argument)
+void flush_all_queues()
+{
+    int current = -1;
+    for (int i = 0; i < kMaxDevices; ++i) {
+        if (!g_dev[i].ready) continue;
+        {
+            std::lock_guard<std::mutex> lock(g_queue[i].mu);
+            if (g_queue[i].nkeys == 0) continue;
+        }
+        if (current < 0 && hipGetDevice(&current) != hipSuccess) return;
+        if (hipSetDevice(i) == hipSuccess) (void)flush_queue(&g_dev[i]);
+    }
+    if (current >= 0) (void)hipSetDevice(current);
+}
+
+// device_ctx for an entry point that waits for the device's stream or puts work of its own on it
+DeviceCtx* device_ctx_flushed(int device)
+{
+    DeviceCtx* d = device_ctx(device);
+    if (!d) return nullptr;
+    const hipError_t e = flush_queue(d);
+    if (e != hipSuccess) { set_error("a queued launch failed: %s", hipGetErrorString(e)); return nullptr; }
+    return d;
+}
+
+// Queue the launch if it is one that can share a pass.  *queued = false: the caller launches it (after flush_queue).
+hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words, const sg::ScanArgs& a, const sg::TextCodes& codes,
+                        bool timed, bool* queued)
+{
+    *queued = false;
+    if (a.s_end <= a.s_begin || !words.sparse) return hipSuccess;
+    const sg::Route r = sg::route(algo, a.m, words, codes);
+    if (r.to != sg::Launcher::hor || r.arg != 0) return hipSuccess;
+    LaunchQueue& q = g_queue[d->device];
+    std::lock_guard<std::mutex> lock(q.mu);
+    ++q.launches;
+    const int G = g_coalesce.load(std::memory_order_relaxed);
+    if (timed || G < 2 || q.off || !sg::g_hor_multi) {
+        ++q.passes;
+        return hipSuccess;
+    }
+    hipError_t err = hipSuccess;
+    uint32_t at = 0;
+    while (at < q.nkeys && !q.keys[at].holds(a)) ++at;
+    if (at == q.nkeys) {
+        if (q.nkeys == LaunchQueue::kKeys) {
+            err = send_key(d, q, q.keys[0]);
+            q.drop(0);
+        }
+        at = q.nkeys++;
+        q.keys[at].key = a;
+        q.keys[at].n = 0;
+    }
+    QueuedKey& k = q.keys[at];
+    k.scans[k.n++] = QueuedScan{algo, a, codes};
+    if (k.n >= static_cast<uint32_t>(G)) {  // (G <= kMultiMax, the room a key has)
+        const hipError_t e = send_key(d, q, k);
+        if (e != hipSuccess && err == hipSuccess) err = e;
+        q.drop(at);
+    }
+    *queued = true;
+    return err;
+}
+
 }  // namespace
+
+namespace sg {
+hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // multi.hpp: set by k_horm.hip where that unit is linked
+}
 
 extern "C" {
 
@@ -689,7 +827,7 @@ const char* smartgpu_algo_name(int algo)
 
 int smartgpu_device_sync(int device)
 {
-    DeviceCtx* d = device_ctx(device);
+    DeviceCtx* d = device_ctx_flushed(device);
     if (!d) return SMARTGPU_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
     return SMARTGPU_OK;
@@ -765,6 +903,10 @@ void smartgpu_text_free(smartgpu_text* t)
     if (!t) return;
     if (t->base) {
         hipSetDevice(t->device);
+        if (t->device >= 0 && t->device < kMaxDevices && g_dev[t->device].ready) {  // launches over this text may be pending
+            const hipError_t e = flush_queue(&g_dev[t->device]);
+            if (e != hipSuccess) set_error("text_free: a queued launch failed: %s", hipGetErrorString(e));
+        }
         hipFree(t->base);
     }
     delete t;
@@ -783,7 +925,7 @@ int smartgpu_text_alphabet(const smartgpu_text* t, uint32_t bits[8])
 int smartgpu_text_read(const smartgpu_text* t, uint64_t off, uint64_t len, void* host)
 {
     if (!t || !host || off > t->n || len > t->n - off) { set_error("bad text_read range"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(t->device);
+    DeviceCtx* d = device_ctx_flushed(t->device);
     if (!d) return SMARTGPU_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
     HIP_TRY(hipMemcpy(host, t->data() + off, len, hipMemcpyDeviceToHost), return SMARTGPU_ERR_HIP);
@@ -824,6 +966,10 @@ void smartgpu_plan_free(smartgpu_plan* p)
 {
     if (!p) return;
     hipSetDevice(p->device);
+    if (p->device >= 0 && p->device < kMaxDevices && g_dev[p->device].ready) {  // launches of this plan may be pending
+        const hipError_t e = flush_queue(&g_dev[p->device]);
+        if (e != hipSuccess) set_error("plan_free: a queued launch failed: %s", hipGetErrorString(e));
+    }
     for (int i = 0; i < sg::kResultSlots; ++i) {
         if (p->ev0[i]) hipEventDestroy(p->ev0[i]);
         if (p->ev1[i]) hipEventDestroy(p->ev1[i]);
@@ -842,6 +988,11 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
     if (off > text->n || n > text->n - off) { set_error("range outside the text"); return SMARTGPU_ERR_ARG; }
     DeviceCtx* d = device_ctx(p->device);
     if (!d) return SMARTGPU_ERR_HIP;
+    const sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(slot), text, off, n);
+    bool queued = false;
+    HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), timed != 0, &queued), return SMARTGPU_ERR_HIP);
+    if (queued) { p->timed[slot] = false; return SMARTGPU_OK; }
+    HIP_TRY(flush_queue(d), return SMARTGPU_ERR_HIP);  // everything else keeps its place behind what was queued before it
     p->timed[slot] = timed != 0;
     if (timed) {
         if (!p->ev0[slot]) {
@@ -850,7 +1001,6 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
         }
         HIP_TRY(hipEventRecord(p->ev0[slot], d->stream), return SMARTGPU_ERR_HIP);
     }
-    const sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(slot), text, off, n);
     HIP_TRY(sg::launch_scan(p->algo, a, d->num_cus, d->stream, text->codes()), return SMARTGPU_ERR_HIP);
     if (timed) HIP_TRY(hipEventRecord(p->ev1[slot], d->stream), return SMARTGPU_ERR_HIP);
     return SMARTGPU_OK;
@@ -859,7 +1009,7 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
 int smartgpu_plan_result(smartgpu_plan* p, int slot, uint64_t* count, double* kernel_ms)
 {
     if (!p || slot < 0 || slot >= p->num_slots()) { set_error("bad plan/slot"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(p->device);
+    DeviceCtx* d = device_ctx_flushed(p->device);
     if (!d) return SMARTGPU_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(d->pinned_count, p->slot_ptr(slot), sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream),
             return SMARTGPU_ERR_HIP);
@@ -898,7 +1048,7 @@ void* smartgpu_plan_result_device_ptr(smartgpu_plan* p) { return p ? p->slot_ptr
 int smartgpu_plan_reset(smartgpu_plan* p)
 {
     if (!p) { set_error("plan is NULL"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(p->device);
+    DeviceCtx* d = device_ctx_flushed(p->device);
     if (!d) return SMARTGPU_ERR_HIP;
     HIP_TRY(hipMemsetAsync(p->slot_ptr(0), 0, sizeof(unsigned long long) * p->num_slots(), d->stream),
             return SMARTGPU_ERR_HIP);
@@ -908,6 +1058,7 @@ int smartgpu_plan_reset(smartgpu_plan* p)
 int smartgpu_plan_set_result_buffer(smartgpu_plan* p, void* device_u64, int nslots)
 {
     if (!p || (device_u64 && (nslots < 1 || nslots > sg::kResultSlots))) { set_error("bad result buffer"); return SMARTGPU_ERR_ARG; }
+    if (!device_ctx_flushed(p->device)) return SMARTGPU_ERR_HIP;  // pending launches of this plan count into the buffer they were given
     p->ext_results = static_cast<unsigned long long*>(device_u64);
     p->ext_slots = device_u64 ? nslots : 0;
     return SMARTGPU_OK;
@@ -915,7 +1066,7 @@ int smartgpu_plan_set_result_buffer(smartgpu_plan* p, void* device_u64, int nslo
 
 int smartgpu_stream_mark(int device, int which)
 {
-    DeviceCtx* d = device_ctx(device);
+    DeviceCtx* d = device_ctx_flushed(device);
     if (!d || which < 0 || which > 1) return SMARTGPU_ERR_ARG;
     if (!d->mark[which]) HIP_TRY(hipEventCreate(&d->mark[which]), return SMARTGPU_ERR_HIP);
     HIP_TRY(hipEventRecord(d->mark[which], d->stream), return SMARTGPU_ERR_HIP);
@@ -924,7 +1075,7 @@ int smartgpu_stream_mark(int device, int which)
 
 int smartgpu_stream_elapsed_ms(int device, double* ms)
 {
-    DeviceCtx* d = device_ctx(device);
+    DeviceCtx* d = device_ctx_flushed(device);
     if (!d || !ms || !d->mark[0] || !d->mark[1]) { set_error("stream marks not set"); return SMARTGPU_ERR_ARG; }
     HIP_TRY(hipEventSynchronize(d->mark[1]), return SMARTGPU_ERR_HIP);
     float f = 0.f;
@@ -936,7 +1087,7 @@ int smartgpu_stream_elapsed_ms(int device, double* ms)
 int smartgpu_probe_read_ms(const smartgpu_text* t, int reps, double* ms_per_pass)
 {
     if (!t || reps < 1 || !ms_per_pass) { set_error("bad probe arguments"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(t->device);
+    DeviceCtx* d = device_ctx_flushed(t->device);
     if (!d) return SMARTGPU_ERR_HIP;
     unsigned long long* sink = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sink), 8), return SMARTGPU_ERR_HIP);
@@ -952,14 +1103,36 @@ int smartgpu_tune(int key, int value)
         set_error("tune(%d,%d) selects a superseded kernel: only in the A/B build (make -C smart_amd/csrc AB=1 -> libsmartgpu_ab.so)", key, value);
         return SMARTGPU_ERR_ARG;
     }
+    flush_all_queues();  // what is pending was launched under the settings of its time
     sg::g_tune[key] = value;
+    return SMARTGPU_OK;
+}
+
+int smartgpu_coalesce(int max_group)
+{
+    if (max_group != 0 && (max_group < 2 || max_group > sg::kMultiMax)) { set_error("coalesce: a pass takes 2..%d launches (0: off), not %d", sg::kMultiMax, max_group); return SMARTGPU_ERR_ARG; }
+    flush_all_queues();
+    return g_coalesce.exchange(max_group);
+}
+
+int smartgpu_coalesce_stats(int device, uint64_t* launches, uint64_t* passes)
+{
+    if (device < 0 || device >= kMaxDevices) { set_error("device %d out of range", device); return SMARTGPU_ERR_ARG; }
+    std::lock_guard<std::mutex> lock(g_queue[device].mu);
+    if (launches) *launches = g_queue[device].launches;
+    if (passes) *passes = g_queue[device].passes;
     return SMARTGPU_OK;
 }
 
 void* smartgpu_stream_handle(int device)
 {
-    DeviceCtx* d = device_ctx(device);
-    return d ? static_cast<void*>(d->stream) : nullptr;
+    DeviceCtx* d = device_ctx_flushed(device);
+    if (!d) return nullptr;
+    {   // whoever holds the stream orders their own work on it: from here on every launch on this device is sent at once
+        std::lock_guard<std::mutex> lock(g_queue[d->device].mu);
+        g_queue[d->device].off = true;
+    }
+    return static_cast<void*>(d->stream);
 }
 
 /* ---- one-shot searches ------------------------------------------------- */
@@ -1173,7 +1346,7 @@ static int search_batch_impl(int algo, const uint8_t* const* P, uint32_t m, uint
     if (K > kBatchMaxPatterns) { set_error("batch: %u patterns in one set (at most %u)", K, kBatchMaxPatterns); return SMARTGPU_ERR_ARG; }
     const int rc = check_search_args(algo, P[0], m, text, off, n);
     if (rc != SMARTGPU_OK) return rc;
-    DeviceCtx* d = device_ctx(text->device);
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     std::vector<BatchPlan> plans;
     const int up = batch_upload({d}, algo, P, m, K, plans, pre_ms);  // preprocessing phase
@@ -1227,7 +1400,7 @@ int smartgpu_find64(const uint8_t* P, uint32_t m, const smartgpu_text* text, uin
     const int rc = check_search_args(SMARTGPU_EPSM, P, m, text, off, n);
     if (rc != SMARTGPU_OK) return rc;
     if (!count || (cap && !positions)) { set_error("find64: count/positions must not be NULL"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(text->device);
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     smartgpu_plan* p = smartgpu_plan_create(SMARTGPU_EPSM, P, m, text->device);
     if (!p) return SMARTGPU_ERR_HIP;
@@ -1530,7 +1703,7 @@ int smartgpu_msearch_batch64(int algo, const uint8_t* const* P, uint32_t m, uint
     std::vector<BatchPlan> plans;
     std::vector<DeviceCtx*> ctx(k, nullptr), uniq;
     for (int g = 0; g < k; ++g) {
-        ctx[g] = device_ctx(text->devices[g]);
+        ctx[g] = device_ctx_flushed(text->devices[g]);
         if (!ctx[g]) return SMARTGPU_ERR_HIP;
         if (std::find(uniq.begin(), uniq.end(), ctx[g]) == uniq.end()) uniq.push_back(ctx[g]);
     }
@@ -1768,7 +1941,7 @@ sg::PlaneArgs plane_args(const DeviceCtx* d, const smartgpu_ptext* text, const u
 int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                  uint64_t* counts, double* pre_ms, double* run_ms)
 {
-    DeviceCtx* d = device_ctx(text->device);
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     const double t_pre = now_ms();
     constexpr size_t kPatBytes = 2 * 4 * sg::kPatWords;  // one pattern's two planes
@@ -1920,7 +2093,7 @@ smartgpu_ptext* smartgpu_ptext_pack(const smartgpu_text* t)
             ++k;
         }
     if (k > 4) { set_error("the text holds %d distinct byte values: a packed text holds at most 4", k); return nullptr; }
-    DeviceCtx* d = device_ctx(t->device);
+    DeviceCtx* d = device_ctx_flushed(t->device);
     if (!d) return nullptr;
     smartgpu_ptext* p = new smartgpu_ptext;
     p->device = t->device;
@@ -1980,7 +2153,7 @@ int smartgpu_ptext_read(const smartgpu_ptext* t, uint64_t off, uint64_t len, voi
 {
     if (!t || (!host && len) || off > t->n || len > t->n - off) { set_error("bad ptext_read range"); return SMARTGPU_ERR_ARG; }
     if (len == 0) return SMARTGPU_OK;
-    DeviceCtx* d = device_ctx(t->device);
+    DeviceCtx* d = device_ctx_flushed(t->device);
     if (!d) return SMARTGPU_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
     const uint64_t w0 = off / 32, nw = (off + len + 31) / 32 - w0;
@@ -2002,7 +2175,7 @@ int smartgpu_ptext_read(const smartgpu_ptext* t, uint64_t off, uint64_t len, voi
 int smartgpu_ptext_probe_read_ms(const smartgpu_ptext* t, int reps, double* ms_per_pass)
 {
     if (!t || reps < 1 || !ms_per_pass) { set_error("bad probe arguments"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(t->device);
+    DeviceCtx* d = device_ctx_flushed(t->device);
     if (!d) return SMARTGPU_ERR_HIP;
     // the planes and the pad between them: one contiguous region of the allocation
     const uint8_t* first = reinterpret_cast<const uint8_t*>(t->plane(0));
@@ -2052,7 +2225,7 @@ int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, u
     const int rc = check_psearch_args(P, m, text, off, n);
     if (rc != SMARTGPU_OK) return rc;
     if (!count || (cap && !positions)) { set_error("pfind64: count must not be NULL, positions only with cap = 0"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(text->device);
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     constexpr size_t kPatBytes = 2 * 4 * sg::kPatWords;
     if (!batch_reserve(d, kPatBytes, 1)) return SMARTGPU_ERR_NOMEM;
@@ -2120,7 +2293,7 @@ int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, cons
     if (total == 0) return SMARTGPU_OK;
     // pass 2: a find for every pattern that occurs, each with its own cursor and its own slice as base and cap.  The
     // patterns' planes are where psearch_impl left them: the staging buffer and, for m > 32, the arena.
-    DeviceCtx* d = device_ctx(text->device);
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     const uint32_t* host_pat = reinterpret_cast<const uint32_t*>(d->pinned);
     bool own = false;

@@ -96,6 +96,8 @@ def _load(path):
         "smartgpu_stream_elapsed_ms": (i32, [i32, C.POINTER(C.c_double)]),
         "smartgpu_stream_handle": (vp, [i32]),
         "smartgpu_tune": (i32, [i32, i32]),
+        "smartgpu_coalesce": (i32, [i32]),
+        "smartgpu_coalesce_stats": (i32, [i32, C.POINTER(u64), C.POINTER(u64)]),
         "smartgpu_mtext_upload": (vp, [vp, u64, i32, vp]),
         "smartgpu_mtext_generate": (vp, [u64, i32, u64, i32, vp]),
         "smartgpu_mtext_free": (None, [vp]),
@@ -592,6 +594,22 @@ def probe_read_gbs(text, reps=20):
 def tune(key, value):
     if lib().smartgpu_tune(key, value) != 0:
         raise _err("tune")
+
+
+def coalesce(max_group):
+    """How many queued Plan.launch calls share one pass over the text (0: none, 2..8); returns the previous value."""
+    prev = lib().smartgpu_coalesce(max_group)
+    if prev < 0:
+        raise _err("coalesce")
+    return prev
+
+
+def coalesce_stats(device=0):
+    """(launches that could share a pass, kernels sent for them) on `device` so far."""
+    launches, passes = C.c_uint64(0), C.c_uint64(0)
+    if lib().smartgpu_coalesce_stats(device, C.byref(launches), C.byref(passes)) != 0:
+        raise _err("coalesce_stats")
+    return int(launches.value), int(passes.value)
 
 
 def kernel_for(algo, P):
