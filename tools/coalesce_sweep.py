@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""Sweep of the shared pass (hor_multi_scan): launches per pass x workgroups per CU x pattern length on 1 GiB of rand128.
+
+    [SMARTGPU_LIB=smart_amd/csrc/libsmartgpu_<variant>.so] python tools/coalesce_sweep.py [--ms 16,32,256] [--groups 0,2,4,8]
+                                                            [--wgs 0,4,5,6,7] [--plans 24] [--rounds 5] [--out FILE]
+
+Per cell: --plans Horspool plans (patterns cut from the text at bench.py's seeded offsets) are launched between two HIP
+events on the launch stream, --rounds times; the cell is the median round in ms per pattern, with the best and the worst.
+group 0 = smartgpu_coalesce(0): every launch a hor_scan of its own; wgs 0 = the library's default (smartgpu_tune(4, 0)).
+One line per cell, and all cells as JSON in --out.  Every count is compared with the group-0 count of the same pattern."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+SEED, PATTERN_SALT = 0x5EED0001, 0x0A77E2
+
+
+def splitmix64(x):
+    M = (1 << 64) - 1
+    x = (x + 0x9E3779B97F4A7C15) & M
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M
+    return x ^ (x >> 31)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ms", default="16,32,256")
+    ap.add_argument("--groups", default="0,2,4,8")
+    ap.add_argument("--wgs", default="0,4,5,6,7")
+    ap.add_argument("--sigma", type=int, default=128)
+    ap.add_argument("--gib", type=float, default=1.0)
+    ap.add_argument("--plans", type=int, default=24)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    ints = lambda s: [int(x) for x in s.split(",")]  # noqa: E731
+
+    import smart_amd
+    from smart_amd import Plan, Text, engine
+    if smart_amd.device_count() < 1:
+        raise SystemExit("no GPU: " + engine.lib().smartgpu_last_error().decode())
+    n = int(args.gib * (1 << 30))
+    text = Text.generate(SEED, args.sigma, n)
+    engine.probe_read_gbs(text, reps=64)  # clocks
+    default_group = engine.coalesce(8)
+    cells = []
+    print("library %s, default group %d" % (engine.LIB_PATH, default_group))
+    for m in ints(args.ms):
+        pats = []
+        j = 0
+        while len(pats) < args.plans:  # streaming patterns only: the others never share a pass
+            p = text.pattern(splitmix64(PATTERN_SALT + 4096 * j + m) % (n - m), m)
+            j += 1
+            if engine.kernel_for("hor", p) == "hor_scan":
+                pats.append(p)
+        plans = [Plan("hor", p) for p in pats]
+        want = None
+        for group in ints(args.groups):
+            for wgs in ints(args.wgs):
+                if group == 0 and wgs != 0:
+                    continue  # tune key 4 is the shared pass's
+                engine.coalesce(group)
+                engine.tune(4, wgs)
+                for pl in plans:
+                    pl.reset()
+                rounds = []
+                for r in range(args.rounds + 1):  # round 0 warms up
+                    engine.stream_mark(0, 0)
+                    for pl in plans:
+                        pl.launch(text, slot=0)
+                    engine.stream_mark(0, 1)
+                    rounds.append(engine.stream_elapsed_ms(0) / len(plans))
+                engine.device_sync(0)
+                got = [pl.result(0)[0] for pl in plans]
+                if want is None:
+                    want = got
+                ok = got == want and all(c >= args.rounds + 1 and c % (args.rounds + 1) == 0 for c in got)
+                rounds = sorted(rounds[1:])
+                cell = {"m": m, "group": group, "wgs": wgs, "ms": round(rounds[len(rounds) // 2], 5), "best": round(rounds[0], 5),
+                        "worst": round(rounds[-1], 5), "count_ok": ok}
+                cells.append(cell)
+                print("m %-4d group %d wgs %d  %.5f ms per pattern (best %.5f worst %.5f)  %s"
+                      % (m, group, wgs, cell["ms"], cell["best"], cell["worst"], "ok" if ok else "COUNT MISMATCH"), flush=True)
+        for pl in plans:
+            pl.free()
+    engine.tune(4, 0)
+    engine.coalesce(default_group)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"library": engine.LIB_PATH, "cells": cells}, f, indent=1)
+    if not all(c["count_ok"] for c in cells):
+        raise SystemExit("COUNT MISMATCH")
+
+
+if __name__ == "__main__":
+    main()
