@@ -362,6 +362,38 @@ int smartgpu_pfind64(const uint8_t *P, uint32_t m, const smartgpu_ptext *text, u
  * K is bounded as in smartgpu_psearch_batch64. */
 int smartgpu_pfind_batch64(const uint8_t *const *P, uint32_t m, uint32_t K, const smartgpu_ptext *text, uint64_t off, uint64_t n,
                            uint64_t *positions, uint64_t cap, uint64_t *starts);
+/* SET patterns on a packed text: pattern position j accepts a set of the text's values instead of one (IUPAC motifs and
+ * primers such as TATAWAW or GGNCC, restriction sites with N gaps).  The contract is the count by definition with
+ * "T[s+j] == P[j]" replaced by "the code of T[s+j] is a member of sets[j]"; nothing in the reference does this.
+ * sets[j], 0 <= j < m: bit c set = position j accepts the symbol with code c (values[c] of smartgpu_ptext_symbols).
+ * One pass over the planes whatever the sets are (planes_sets_scan, planes_sets_find): a position costs the one
+ * three-input bit operation per plane dword of an exact symbol, with the OR of its members' truth tables, and a position
+ * that accepts every value of the text costs nothing.
+ * The range convention, count width, times, cap / count / SMARTGPU_ERR_NOMEM behaviour and the order of the positions
+ * (ascending, relative to symbol 0) are those of smartgpu_psearch64 / smartgpu_pfind64.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: sets == NULL, m = 0 or m > SMARTGPU_XSIZE, a NULL text,
+ * a range outside the text, count == NULL, positions == NULL with cap > 0, and a set with a bit at or above the text's
+ * number of values (bits 4..7 always are; the message names the position).
+ * No launch: a position with the empty set (count 0, SMARTGPU_OK), m > n (count 0), a pattern of full sets (every start
+ * position of the range; the find writes them when count <= cap).
+ * MEASURED on an MI355X, 1 Gi symbols of rand4 and of rand2, m = 8 .. 256 (profiles/packed/RESULTS.md, "Set patterns"):
+ * a singleton-set pattern is NOT at smartgpu_psearch64's speed, as the instruction count per position had suggested —
+ * planes_sets_scan takes 1.45-1.63 x planes_scan's kernel time (1.26-1.45 x per call), outside the run-to-run spread in
+ * every cell: the scalar switch per position and the larger loop body cost that much.  A motif with g = 1, 2, 3 full-set
+ * positions in one call against its 4^g exact expansions through smartgpu_psearch_batch64 (rand4, m = 16): 2.1 / 7.6 /
+ * 29.9 x faster, counts equal.  Two-member sets at the first eight positions (the early leave's worst case): 2.0-2.1 x
+ * the exact pattern's call on rand4 from m = 16 on.  The rand2 planes are of Infinity-Cache size: possibly flattered.
+ * NOT measured: the find form's speed, texts with long partial matches, texts beyond 1 Gi symbols. */
+int smartgpu_psearch_sets64(const uint8_t *sets, uint32_t m, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                            uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_pfind_sets64(const uint8_t *sets, uint32_t m, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                          uint64_t *positions, uint64_t cap, uint64_t *count);
+/* No device: IUPAC nucleotide letters -> sets over a text's values.  P[0..m): the letters A C G T U R Y S W K M B D H V N
+ * in either case.  Value v of the text (values[0..nvalues), as smartgpu_ptext_symbols returns them) stands for base X when
+ * it is the byte 'X' or 'x'; 'U' / 'u' count as T.  sets[j] = the OR over the text's values that position j's letter
+ * accepts; it may be 0 (then the searches answer 0).  Any other byte in P: SMARTGPU_ERR_ARG, the message names position and
+ * byte; nvalues outside 1..4 or a NULL pointer: SMARTGPU_ERR_ARG.  Nothing is written on refusal. */
+int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char *P, uint32_t m, uint8_t *sets);
 /* smartgpu_probe_read_ms on the planes: the streaming-read time of the bytes a packed search reads (the plane roofline) */
 int smartgpu_ptext_probe_read_ms(const smartgpu_ptext *t, int reps, double *ms_per_pass);
 

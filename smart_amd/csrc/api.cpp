@@ -2070,6 +2070,128 @@ bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t s_last
     return true;
 }
 
+// One find on a packed text, n >= m: the device buffer, `launch(out, room)` — the pattern's staging, the cursor's memset
+// and the kernel, all on the device's stream —, the cursor's read-back, the positions to the host in ascending order.
+// *count always receives the number of occurrences when the device answered; the return codes are smartgpu_pfind64's.
+template <typename Launch>
+int pfind_run(DeviceCtx* d, const char* call, const char* kernel, uint32_t m, uint64_t off, uint64_t n, uint64_t* positions,
+              uint64_t cap, uint64_t* count, unsigned long long* cursor, Launch launch)
+{
+    const uint64_t starts = n - m + 1;
+    const uint64_t room = cap < starts ? cap : starts;  // no more positions than start positions
+    bool own = false;
+    unsigned long long* out = nullptr;
+    uint64_t room_got = room;
+    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
+    bool ok = launch(out, room_got) &&
+              hipMemcpyAsync(d->pinned_counts, cursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+              hipStreamSynchronize(d->stream) == hipSuccess;
+    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
+    int r = SMARTGPU_OK;
+    if (!ok) {
+        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        r = SMARTGPU_ERR_HIP;
+    } else if (total > starts) {  // refused like a poisoned count, never reported
+        set_error("%s: cursor %llu exceeds the %llu start positions", kernel, total, (unsigned long long)starts);
+        r = SMARTGPU_ERR_HIP;
+    } else if (total && total <= room_got) {
+        if (!copy_positions(d, positions, out, total)) {
+            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+            r = SMARTGPU_ERR_HIP;
+        } else if (!order_spans(positions, total, off, off + n - m)) {
+            set_error("%s: the positions are not ascending spans of %llu start positions", kernel, (unsigned long long)sg::kFindSpan);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (own) (void)hipFree(out);
+    if (r != SMARTGPU_OK) return r;
+    *count = total;
+    if (total <= cap && total > room_got) {
+        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu positions", call, total, (unsigned long long)cap, (unsigned long long)room);
+        return SMARTGPU_ERR_NOMEM;
+    }
+    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    return SMARTGPU_OK;
+}
+
+// ---- set patterns on packed texts (planes_sets_scan, planes_sets_find) ----
+}  // namespace
+// WEAK references: a host program that links this file without k_planes.o and stands in for the launchers itself (the
+// dispatch test's driver, which knows the launchers this file had when it was written) still links.  In the library both
+// are defined (k_planes.hip); an undefined one is an error of the call (sets_launchers_linked), never another path.
+namespace sg {
+__attribute__((weak)) hipError_t launch_planes_sets_scan(const PlaneSetArgs& a, int planes, int num_cus, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_planes_sets_find(const PlaneSetArgs& a, unsigned long long* out, unsigned long long cap, int planes,
+                                                         int num_cus, hipStream_t stream);
+}  // namespace sg
+namespace {
+bool sets_launchers_linked()
+{
+    if (&sg::launch_planes_sets_scan && &sg::launch_planes_sets_find) return true;
+    set_error("planes_sets_scan / planes_sets_find are not linked into this program");
+    return false;
+}
+
+constexpr size_t kSetWords = 4 * sg::kPatWords;  // a set pattern's four membership planes
+
+// The set pattern as membership planes: bit j % 32 of Y[c * kPatWords + j / 32] = position j accepts code c.  A position
+// that accepts every value of the text gets ALL its bits (planes.hpp: no instruction).  SMARTGPU_ERR_ARG: a set names a
+// code the text does not hold.  *empty: some position accepts nothing; *full: every position accepts everything.
+int sets_planes(const smartgpu_ptext* t, const uint8_t* sets, uint32_t m, uint32_t* Y, bool* empty, bool* full)
+{
+    const uint32_t all = (1u << t->nvalues) - 1u;
+    std::memset(Y, 0, 4 * kSetWords);
+    *empty = false;
+    *full = true;
+    for (uint32_t j = 0; j < m; ++j) {
+        uint32_t s = sets[j];
+        if (s & ~all) {
+            set_error("set pattern: position %u: set 0x%02x names a code >= %d, the number of values the text holds", j, s, t->nvalues);
+            return SMARTGPU_ERR_ARG;
+        }
+        if (s == 0) *empty = true;
+        if (s == all) s = 0xFu; else *full = false;
+        for (uint32_t c = 0; c < 4; ++c)
+            if (s >> c & 1u) Y[c * sg::kPatWords + (j >> 5)] |= 1u << (j & 31);
+    }
+    return SMARTGPU_OK;
+}
+
+// What the sets kernels receive, n >= m; the pattern's planes go through the staging buffer into the arena when m > 32
+// (stage_sets).  The result slot is d->batch_counts[0].
+sg::PlaneSetArgs plane_set_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* Y, uint32_t m, uint64_t off, uint64_t n)
+{
+    sg::PlaneSetArgs a;
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.s_begin = off;
+    a.s_end = off + n - m + 1;
+    a.m = m;
+    for (uint32_t c = 0; c < 4; ++c) a.y[c] = Y[c * sg::kPatWords];
+    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
+    a.count = d->batch_counts;
+    return a;
+}
+
+bool stage_sets(DeviceCtx* d, const uint32_t* Y, uint32_t m)
+{
+    if (m <= 32) return true;  // the first 32 positions travel as kernel arguments
+    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
+    std::memcpy(d->pinned, Y, 4 * kSetWords);
+    return hipMemcpyAsync(d->arena, d->pinned, 4 * kSetWords, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+}
+
+// the checks of both set calls that need no device; Y: the caller's kSetWords dwords
+int check_psets_args(const char* call, const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                     const uint64_t* count, uint32_t* Y, bool* empty, bool* full)
+{
+    if (!sets) { set_error("%s: sets is NULL", call); return SMARTGPU_ERR_ARG; }
+    const int rc = check_psearch_args(sets, m, text, off, n);
+    if (rc != SMARTGPU_OK) return rc;
+    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
+    return sets_planes(text, sets, m, Y, empty, full);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2235,44 +2357,12 @@ int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, u
         *count = 0;
         return SMARTGPU_OK;
     }
-    const uint64_t starts = n - m + 1;
-    const uint64_t room = cap < starts ? cap : starts;  // no more positions than start positions
-    bool own = false;
-    unsigned long long* out = nullptr;
-    uint64_t room_got = room;
-    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
     const sg::PlaneArgs a = plane_args(d, text, host_pat, 0, m, off, n);
-    bool ok = (m <= 32 || hipMemcpyAsync(d->arena, host_pat, kPatBytes, hipMemcpyHostToDevice, d->stream) == hipSuccess) &&
-              hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-              sg::launch_planes_find(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
-              hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
-              hipStreamSynchronize(d->stream) == hipSuccess;
-    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
-    int r = SMARTGPU_OK;
-    if (!ok) {
-        set_error("pfind64: %s", hipGetErrorString(hipGetLastError()));
-        r = SMARTGPU_ERR_HIP;
-    } else if (total > starts) {  // refused like a poisoned count, never reported
-        set_error("planes_find: cursor %llu exceeds the %llu start positions", total, (unsigned long long)starts);
-        r = SMARTGPU_ERR_HIP;
-    } else if (total && total <= room_got) {
-        if (!copy_positions(d, positions, out, total)) {
-            set_error("pfind64: %s", hipGetErrorString(hipGetLastError()));
-            r = SMARTGPU_ERR_HIP;
-        } else if (!order_spans(positions, total, off, off + n - m)) {
-            set_error("planes_find: the positions are not ascending spans of %llu start positions", (unsigned long long)sg::kFindSpan);
-            r = SMARTGPU_ERR_HIP;
-        }
-    }
-    if (own) (void)hipFree(out);
-    if (r != SMARTGPU_OK) return r;
-    *count = total;
-    if (total <= cap && total > room_got) {
-        set_error("pfind64: %llu occurrences, room for %llu, but the device has no memory for %llu positions", total, (unsigned long long)cap, (unsigned long long)room);
-        return SMARTGPU_ERR_NOMEM;
-    }
-    if (total > cap) { set_error("pfind64: %llu occurrences, room for %llu", total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-    return SMARTGPU_OK;
+    return pfind_run(d, "pfind64", "planes_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
+        return (m <= 32 || hipMemcpyAsync(d->arena, host_pat, kPatBytes, hipMemcpyHostToDevice, d->stream) == hipSuccess) &&
+               hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+               sg::launch_planes_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
+    });
 }
 
 int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
@@ -2323,6 +2413,105 @@ int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, cons
     }
     if (own) (void)hipFree(out);
     return r;
+}
+
+/* ---- set patterns: every pattern position accepts a set of the text's values ---------------------------------------- */
+int smartgpu_psearch_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                            uint64_t* count, double* pre_ms, double* run_ms)
+{
+    uint32_t Y[kSetWords];
+    bool empty = false, full = false;
+    const int rc = check_psets_args("psearch_sets64", sets, m, text, off, n, count, Y, &empty, &full);
+    if (rc != SMARTGPU_OK) return rc;
+    uint64_t c = 0;
+    double pre = 0.0, run = 0.0;
+    if (empty || m > n) {
+        c = 0;  // a position that accepts nothing, or no window fits: no launch
+    } else if (full) {
+        c = n - m + 1;  // every start position of the range: no launch
+    } else {
+        DeviceCtx* d = sets_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+        if (!d) return SMARTGPU_ERR_HIP;
+        const double t_pre = now_ms();
+        if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
+        if (!stage_sets(d, Y, m)) { set_error("psearch_sets64: %s", hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
+        pre = now_ms() - t_pre;
+        const double t0 = now_ms();
+        const sg::PlaneSetArgs a = plane_set_args(d, text, Y, m, off, n);
+        HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(sg::launch_planes_sets_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+        run = now_ms() - t0;
+        // more occurrences than start positions: refused like a poisoned count, never reported
+        if (d->pinned_counts[0] > n - m + 1) { set_error("planes_sets_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
+        c = d->pinned_counts[0];
+    }
+    g_last_pre_ms = pre;
+    g_last_run_ms = run;
+    *count = c;
+    if (pre_ms) *pre_ms = pre;
+    if (run_ms) *run_ms = run;
+    return SMARTGPU_OK;
+}
+
+int smartgpu_pfind_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                          uint64_t* positions, uint64_t cap, uint64_t* count)
+{
+    if (cap && !positions) { set_error("pfind_sets64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
+    uint32_t Y[kSetWords];
+    bool empty = false, full = false;
+    const int rc = check_psets_args("pfind_sets64", sets, m, text, off, n, count, Y, &empty, &full);
+    if (rc != SMARTGPU_OK) return rc;
+    if (empty || m > n) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    if (full) {  // every start position of the range: no launch
+        const uint64_t total = n - m + 1;
+        *count = total;
+        if (total > cap) { set_error("pfind_sets64: %llu occurrences, room for %llu", (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+        for (uint64_t i = 0; i < total; ++i) positions[i] = off + i;
+        return SMARTGPU_OK;
+    }
+    DeviceCtx* d = sets_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
+    const sg::PlaneSetArgs a = plane_set_args(d, text, Y, m, off, n);
+    return pfind_run(d, "pfind_sets64", "planes_sets_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
+        return stage_sets(d, Y, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+               sg::launch_planes_sets_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
+    });
+}
+
+int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)
+{
+    if (!values || (m && (!P || !sets))) { set_error("iupac_sets: NULL argument"); return SMARTGPU_ERR_ARG; }
+    if (nvalues < 1 || nvalues > 4) { set_error("iupac_sets: a packed text holds 1 to 4 distinct byte values, not %d", nvalues); return SMARTGPU_ERR_ARG; }
+    // the bases a letter accepts, bit 0..3 = A C G T
+    static const struct { char letter; uint8_t bases; } kIupac[] = {
+        {'A', 1}, {'C', 2}, {'G', 4}, {'T', 8}, {'U', 8}, {'R', 1 | 4}, {'Y', 2 | 8}, {'S', 2 | 4}, {'W', 1 | 8}, {'K', 4 | 8}, {'M', 1 | 2},
+        {'B', 2 | 4 | 8}, {'D', 1 | 4 | 8}, {'H', 1 | 2 | 8}, {'V', 1 | 2 | 4}, {'N', 15}};
+    int bases_of[256];
+    for (int c = 0; c < 256; ++c) bases_of[c] = -1;
+    for (const auto& e : kIupac) bases_of[(uint8_t)e.letter] = bases_of[(uint8_t)(e.letter | 0x20)] = e.bases;
+    uint8_t base_of_code[4] = {0, 0, 0, 0};  // the base (one bit) value v stands for; 0: none
+    for (int v = 0; v < nvalues; ++v) {
+        const int b = bases_of[values[v]];
+        if (b == 1 || b == 2 || b == 4 || b == 8) base_of_code[v] = static_cast<uint8_t>(b);
+    }
+    for (uint32_t j = 0; j < m; ++j)
+        if (bases_of[(uint8_t)P[j]] < 0) {
+            set_error("iupac_sets: position %u: byte 0x%02x is no IUPAC nucleotide letter", j, (unsigned)(uint8_t)P[j]);
+            return SMARTGPU_ERR_ARG;
+        }
+    for (uint32_t j = 0; j < m; ++j) {
+        uint8_t s = 0;
+        for (int v = 0; v < nvalues; ++v)
+            if (bases_of[(uint8_t)P[j]] & base_of_code[v]) s |= static_cast<uint8_t>(1u << v);
+        sets[j] = s;
+    }
+    return SMARTGPU_OK;
 }
 
 }  // extern "C"

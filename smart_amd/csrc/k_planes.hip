@@ -1,5 +1,6 @@
 // k_planes.hip — packed texts: planes_pack (byte text -> bit planes, once per text), planes_scan (the matcher on planes),
-// planes_find (the same matcher with an output stage: positions)
+// planes_find (the same matcher with an output stage: positions), planes_sets_scan / planes_sets_find (their siblings for
+// patterns whose positions accept a SET of symbols)
 // (one translation unit per kernel family: dev_common.hpp; the layout: planes.hpp)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
@@ -333,6 +334,245 @@ hipError_t launch_planes_find(const PlaneArgs& a, unsigned long long* out, unsig
         hipLaunchKernelGGL(planes_find<2>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
     else
         hipLaunchKernelGGL(planes_find<1>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// planes_sets_scan<PLANES>, planes_sets_find<PLANES>: SET patterns — position j of the pattern accepts a set of codes.
+// They count / list the start positions s in [s_begin, s_end) where the code of T[s + j] is a member of set j for all
+// j < m.  Siblings of planes_scan and planes_find: the same geometry, loads, range masks, early leave and output stage;
+// what differs is the step per pattern position and the verification beyond the 32nd.
+//
+// planes_kill picks one of four truth tables by the symbol's code.  A set's table is the OR of its members' tables, so a
+// position costs the same v_alignbit per plane and ONE v_bitop3 whatever the set is (fewer where the table does not
+// depend on a plane: the compiler drops that plane's v_alignbit), and a position that accepts every code costs nothing.
+// The set of position j — bit j of y[0..3] — is wave-uniform: a scalar switch, one case per table.
+//
+// The two kernels share ONE body (planes_sets_body<PLANES, FIND>, if constexpr): unlike planes_scan, whose instruction
+// stream is documented and measured, neither has a stream to preserve.  planes_scan and planes_find are not touched.
+// ---------------------------------------------------------------------------
+// the table of M & "the code (t1 t0) is a member of s" over M = 0xF0, t0 = 0xCC, t1 = 0xAA
+constexpr uint32_t sets_table(int planes, uint32_t s)
+{
+    return planes == 2 ? ((s & 1u ? 0x10u : 0u) | (s & 2u ? 0x40u : 0u) | (s & 4u ? 0x20u : 0u) | (s & 8u ? 0x80u : 0u))
+                       : ((s & 1u ? 0x30u : 0u) | (s & 2u ? 0xC0u : 0u));
+}
+
+template <int PLANES, uint32_t TABLE>
+static __device__ __forceinline__ void planes_sets_step(uint32_t (&M)[kChunk], const PlaneWords& t, uint32_t j)
+{
+#pragma unroll
+    for (uint32_t w = 0; w < kChunk; ++w) {
+        const uint32_t t0 = __builtin_amdgcn_alignbit(t.a[w + 1], t.a[w], j);
+        const uint32_t t1 = PLANES == 2 ? __builtin_amdgcn_alignbit(t.b[w + 1], t.b[w], j) : 0u;
+        M[w] = __builtin_amdgcn_bitop3_b32(M[w], t0, t1, TABLE);
+    }
+}
+
+// positions [j0, j1) (j1 <= 32) of the pattern's first block, membership bits y[c], against the block's five dwords
+template <int PLANES>
+static __device__ __forceinline__ void planes_sets_kill(uint32_t (&M)[kChunk], const PlaneWords& t, const uint32_t (&y)[4], uint32_t j0, uint32_t j1)
+{
+    for (uint32_t j = j0; j < j1; ++j) {
+        uint32_t s = ((y[0] >> j) & 1u) | ((y[1] >> j) & 1u) << 1;  // wave-uniform
+        if (PLANES == 2) s |= ((y[2] >> j) & 1u) << 2 | ((y[3] >> j) & 1u) << 3;
+#define SG_SETS_CASE(s_) case s_: planes_sets_step<PLANES, sets_table(PLANES, s_)>(M, t, j); break;
+        if (PLANES == 2) {
+            switch (s) {
+                SG_SETS_CASE(1) SG_SETS_CASE(2) SG_SETS_CASE(3) SG_SETS_CASE(4) SG_SETS_CASE(5) SG_SETS_CASE(6) SG_SETS_CASE(7)
+                SG_SETS_CASE(8) SG_SETS_CASE(9) SG_SETS_CASE(10) SG_SETS_CASE(11) SG_SETS_CASE(12) SG_SETS_CASE(13) SG_SETS_CASE(14)
+                case 0: M[0] = M[1] = M[2] = M[3] = 0u; break;  // (the host sends no empty set)
+                default: break;                                  // every code: no instruction
+            }
+        } else {
+            switch (s) {
+                SG_SETS_CASE(1) SG_SETS_CASE(2)
+                case 0: M[0] = M[1] = M[2] = M[3] = 0u; break;
+                default: break;
+            }
+        }
+#undef SG_SETS_CASE
+    }
+}
+
+// planes_verify for sets: lane l takes block k0 + l of the pattern — the membership dwords Y0..Y3[k] (Y0, Y1 on one
+// plane) — and the five text dwords k dwords behind the chunk.  Bit b of `acc` says that the text symbol b behind the live
+// position is accepted by position 32 k + b: the Y dword its code selects, bit by bit — a two-level multiplexer, three
+// v_bitop3 on two planes (four Y dwords and two text dwords are six inputs: two three-input operations cannot take them),
+// one on one plane.  Positions beyond the pattern's end (the last block may be partial, lanes beyond the last block)
+// accept everything: ~bmask is ORed into the Y dwords once per block.  One ballot per live position.
+template <int PLANES>
+static __device__ __forceinline__ void planes_sets_verify(uint32_t (&R)[kChunk], const PlaneSetArgs& a, uint64_t dw)
+{
+    constexpr uint32_t kMux = 0xCA;  // bitop3(sel, one, zero): sel ? one : zero, bit by bit
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t k0 = 1; 32 * k0 < a.m && (R[0] | R[1] | R[2] | R[3]) != 0; k0 += 64) {
+        const bool valid = 32 * (k0 + lane) < a.m;
+        const uint32_t k = valid ? k0 + lane : k0;
+        const uint32_t left = a.m - 32 * k;
+        const uint32_t bmask = !valid ? 0u : left >= 32 ? ~0u : (1u << left) - 1u;
+        uint32_t ta[kChunk + 1], tb[kChunk + 1];
+        __builtin_memcpy(ta, a.p0 + dw + k, 4 * (kChunk + 1));
+        if (PLANES == 2) __builtin_memcpy(tb, a.p1 + dw + k, 4 * (kChunk + 1));
+        const uint32_t y0 = a.pat[k] | ~bmask, y1 = a.pat[kPatWords + k] | ~bmask;
+        const uint32_t y2 = PLANES == 2 ? a.pat[2 * kPatWords + k] | ~bmask : 0u;
+        const uint32_t y3 = PLANES == 2 ? a.pat[3 * kPatWords + k] | ~bmask : 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < kChunk; ++w) {
+            uint32_t r = R[w];
+            while (r) {
+                const uint32_t i = __builtin_ctz(r);
+                r &= r - 1;
+                const uint32_t t0 = __builtin_amdgcn_alignbit(ta[w + 1], ta[w], i);
+                uint32_t acc = __builtin_amdgcn_bitop3_b32(t0, y1, y0, kMux);
+                if (PLANES == 2) {
+                    const uint32_t t1 = __builtin_amdgcn_alignbit(tb[w + 1], tb[w], i);
+                    acc = __builtin_amdgcn_bitop3_b32(t1, __builtin_amdgcn_bitop3_b32(t0, y3, y2, kMux), acc, kMux);
+                }
+                if (__any(acc != ~0u)) R[w] &= ~(1u << i);
+            }
+        }
+    }
+}
+
+// The loop skeleton is planes_scan's (FIND = false) and planes_find's (FIND = true): a change to one of those belongs here
+// as well.  smem: flush_hits' 128 bytes (the scan only).
+template <int PLANES, bool FIND>
+static __device__ __forceinline__ void planes_sets_body(const PlaneSetArgs& a, uint8_t* smem, unsigned long long* __restrict__ out,
+                                                        unsigned long long cap)
+{
+    constexpr uint64_t kPos = 32 * kChunk;  // start positions per chunk
+    const uint64_t c_end = (a.s_end + kPos - 1) / kPos;
+    const uint64_t stride = (uint64_t)gridDim.x * kPlanesT * kUnroll;
+    const uint32_t f1 = a.m < 32 ? a.m : 32u;
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t hits = 0;
+    // the trip count is the WAVE's (its first chunk decides): every lane stays for the ballots, the verification and the shuffles
+    for (uint64_t cw = a.s_begin / kPos + (uint64_t)blockIdx.x * kPlanesT * kUnroll + 64u * wave; cw < c_end; cw += stride) {
+        PlaneWords t[kUnroll];
+        uint32_t M[kUnroll][kChunk];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint64_t c = cw + (uint64_t)u * kPlanesT + lane;
+            const bool in = c < c_end;
+            const uint64_t dw = in ? c * kChunk : 0;
+            const uint4 va = ld_stream16(reinterpret_cast<const uint8_t*>(a.p0 + dw));
+            t[u].a[0] = va.x; t[u].a[1] = va.y; t[u].a[2] = va.z; t[u].a[3] = va.w;
+            t[u].a[4] = a.p0[dw + kChunk];
+            if (PLANES == 2) {
+                const uint4 vb = ld_stream16(reinterpret_cast<const uint8_t*>(a.p1 + dw));
+                t[u].b[0] = vb.x; t[u].b[1] = vb.y; t[u].b[2] = vb.z; t[u].b[3] = vb.w;
+                t[u].b[4] = a.p1[dw + kChunk];
+            }
+            const bool inner = c * kPos >= a.s_begin && (c + 1) * kPos <= a.s_end;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w)
+                M[u][w] = !in ? 0u : inner ? ~0u : range_mask(c * kPos + 32 * w, a.s_begin, a.s_end);
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint32_t live = 0;
+            for (uint32_t j0 = 0; j0 < f1; j0 += 8) {
+                planes_sets_kill<PLANES>(M[u], t[u], a.y, j0, j0 + 8 < f1 ? j0 + 8 : f1);
+                live = M[u][0] | M[u][1] | M[u][2] | M[u][3];
+                if (!__any(live != 0)) break;
+            }
+            if (a.m > 32) {  // a lane has live positions after 32 pattern positions
+                unsigned long long todo = __ballot(live != 0);
+                while (todo) {
+                    const int src = __builtin_ctzll(todo);  // wave-uniform
+                    todo &= todo - 1;
+                    const uint64_t dw = (cw + (uint64_t)u * kPlanesT + (uint32_t)src) * kChunk;
+                    uint32_t R[kChunk];
+#pragma unroll
+                    for (uint32_t w = 0; w < kChunk; ++w) R[w] = __builtin_amdgcn_readlane(M[u][w], src);
+                    planes_sets_verify<PLANES>(R, a, dw);
+                    if (lane == (uint32_t)src) {
+#pragma unroll
+                        for (uint32_t w = 0; w < kChunk; ++w) M[u][w] = R[w];
+                    }
+                }
+                live = M[u][0] | M[u][1] | M[u][2] | M[u][3];
+            }
+            uint32_t mine = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) mine += __builtin_popcount(M[u][w]);
+            if constexpr (!FIND) {
+                hits += mine;
+            } else {
+                if (!__any(live != 0)) continue;
+                // planes_find's output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
+                uint32_t incl = mine;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = __shfl_up(incl, d, 64);
+                    if (lane >= (uint32_t)d) incl += up;
+                }
+                const uint32_t total = __shfl(incl, 63, 64);
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
+                base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                       __builtin_amdgcn_readfirstlane((uint32_t)base);
+                unsigned long long slot = base + (incl - mine);
+                const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
+#pragma unroll
+                for (uint32_t w = 0; w < kChunk; ++w) {
+                    uint32_t r = M[u][w];
+                    while (r) {
+                        const uint32_t i = __builtin_ctz(r);
+                        r &= r - 1;
+                        if (slot < cap) out[slot] = pos + 32 * w + i;
+                        ++slot;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (!FIND) flush_hits(hits, a.count, smem, reinterpret_cast<const uint8_t*>(a.p0));
+}
+
+template <int PLANES>
+__global__ __launch_bounds__(kPlanesT, 8) void planes_sets_scan(PlaneSetArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // 128 bytes: flush_hits
+    planes_sets_body<PLANES, false>(a, smem, nullptr, 0);
+}
+
+template <int PLANES>
+__global__ __launch_bounds__(kPlanesT, 8) void planes_sets_find(PlaneSetArgs a, unsigned long long* __restrict__ out, unsigned long long cap)
+{
+    planes_sets_body<PLANES, true>(a, nullptr, out, cap);
+}
+
+// Grid and occupancy: launch_planes_scan's.
+static uint32_t planes_sets_grid(const PlaneSetArgs& a, int num_cus)
+{
+    constexpr uint64_t kPos = 32 * kChunk;
+    const uint64_t chunks = (a.s_end + kPos - 1) / kPos - a.s_begin / kPos;
+    const uint64_t want = (chunks + kPlanesT * kUnroll - 1) / (kPlanesT * kUnroll);
+    return (uint32_t)std::min<uint64_t>(want, (uint64_t)num_cus * kPlanesWgs);
+}
+
+hipError_t launch_planes_sets_scan(const PlaneSetArgs& a, int planes, int num_cus, hipStream_t stream)
+{
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    const uint32_t grid = planes_sets_grid(a, num_cus);
+    if (planes == 2)
+        hipLaunchKernelGGL(planes_sets_scan<2>, dim3(grid), dim3(kPlanesT), 128, stream, a);
+    else
+        hipLaunchKernelGGL(planes_sets_scan<1>, dim3(grid), dim3(kPlanesT), 128, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_planes_sets_find(const PlaneSetArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                                   hipStream_t stream)
+{
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    const uint32_t grid = planes_sets_grid(a, num_cus);
+    if (planes == 2)
+        hipLaunchKernelGGL(planes_sets_find<2>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
+    else
+        hipLaunchKernelGGL(planes_sets_find<1>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
     return hipGetLastError();
 }
 

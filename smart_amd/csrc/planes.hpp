@@ -50,4 +50,22 @@ constexpr uint64_t kFindSpan = 8192;
 hipError_t launch_planes_find(const PlaneArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
                               hipStream_t stream);
 
+// SET patterns: pattern position j accepts a set of codes instead of one.  What planes_sets_scan and planes_sets_find
+// receive (by value): PlaneArgs with membership bits in place of code bits.  A position that accepts every value of the
+// text has ALL its bits set (of y[0], y[1] on one plane, of y[0..3] on two), whatever codes the text holds: the kernels
+// then spend no instruction on it.  No position is empty (the host answers 0 without a launch).
+struct PlaneSetArgs {
+    const uint32_t* p0;         // as PlaneArgs
+    const uint32_t* p1;
+    uint64_t s_begin, s_end;
+    uint32_t m;
+    uint32_t y[4];              // bit j of y[c]: pattern position j < 32 accepts code c (one plane: y[0], y[1] only)
+    const uint32_t* pat;        // device, m > 32 only: the whole pattern as membership planes, u32 Y0..Y3[kPatWords]
+    unsigned long long* count;  // device result slot (pre-zeroed)
+};
+// Grid, occupancy, range convention and — for the find — the spans of `out`: those of launch_planes_scan / launch_planes_find.
+hipError_t launch_planes_sets_scan(const PlaneSetArgs& a, int planes, int num_cus, hipStream_t stream);
+hipError_t launch_planes_sets_find(const PlaneSetArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                                   hipStream_t stream);
+
 }  // namespace sg

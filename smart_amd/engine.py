@@ -123,6 +123,9 @@ def _load(path):
         "smartgpu_psearch_batch64": (i32, [vp, u32, u32, vp, u64, u64, vp, C.POINTER(C.c_double)]),
         "smartgpu_pfind64": (i32, [vp, u32, vp, u64, u64, vp, u64, C.POINTER(u64)]),
         "smartgpu_pfind_batch64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp]),
+        "smartgpu_psearch_sets64": (i32, [vp, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_pfind_sets64": (i32, [vp, u32, vp, u64, u64, vp, u64, C.POINTER(u64)]),
+        "smartgpu_iupac_sets": (i32, [vp, i32, vp, u32, vp]),
     }
     for a in ALGOS:
         sig["smartgpu_%s_search" % a] = (i32, [vp, i32, vp, i32])
@@ -280,6 +283,10 @@ class PackedText:
         if lib().smartgpu_ptext_read(self._h, off, length, out.ctypes.data) != 0:
             raise _err("ptext_read")
         return out
+
+    def iupac(self, pattern):
+        """The sets of an IUPAC nucleotide pattern over this text's values: iupac_sets(pattern, self.symbols())."""
+        return iupac_sets(pattern, self.symbols())
 
     def probe_read_gbs(self, reps=20):
         """Practical streaming-read rate (GB/s) of the device over the planes: the packed layout's roofline."""
@@ -510,6 +517,52 @@ def pfind_batch(patterns, ptext, off=0, n=None, cap=1 << 20):
     if rc != 0:
         raise _err("pfind_batch64 rc=%d" % rc)
     return [out[int(starts[k]):int(starts[k + 1])].copy() for k in range(K)], counts
+
+
+def psearch_sets(sets, ptext, off=0, n=None):
+    """(count, pre_ms, run_ms) of a SET pattern in symbols [off, off+n) of a PackedText: sets[j] is a byte whose bit c says
+    that position j accepts the symbol ptext.symbols()[c] (smartgpu_psearch_sets64; PackedText.iupac builds such sets)."""
+    sets = _u8(sets)
+    if n is None:
+        n = len(ptext) - off
+    c = C.c_uint64(0)
+    pre = C.c_double(0.0)
+    run = C.c_double(0.0)
+    rc = lib().smartgpu_psearch_sets64(sets.ctypes.data, len(sets), ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
+    if rc != 0:
+        raise _err("psearch_sets64 rc=%d" % rc)
+    return int(c.value), float(pre.value), float(run.value)
+
+
+def pfind_sets(sets, ptext, off=0, n=None, cap=1 << 20):
+    """(positions, count) of a SET pattern (psearch_sets) in symbols [off, off+n) of a PackedText, as pfind returns them:
+    ascending, relative to symbol 0; positions is None when there are more than `cap`."""
+    sets = _u8(sets)
+    if n is None:
+        n = len(ptext) - off
+    out = np.empty(max(cap, 1), dtype=np.uint64)
+    c = C.c_uint64(0)
+    rc = lib().smartgpu_pfind_sets64(sets.ctypes.data, len(sets), ptext._h, off, n, out.ctypes.data if cap else None, cap, C.byref(c))
+    if rc == -5 and c.value > cap:
+        return None, int(c.value)
+    if rc != 0:
+        raise _err("pfind_sets64 rc=%d" % rc)
+    return out[:c.value].copy(), int(c.value)
+
+
+def iupac_sets(pattern, values):
+    """The uint8 sets of an IUPAC nucleotide pattern (A C G T U R Y S W K M B D H V N, either case) over a packed text's
+    `values` (PackedText.symbols()): bit c of sets[j] = position j accepts values[c].  No device needed."""
+    if isinstance(pattern, str):
+        pattern = pattern.encode()
+    P = _u8(pattern)
+    vals = np.zeros(4, dtype=np.uint8)
+    k = len(values)
+    vals[:min(k, 4)] = np.asarray(list(values)[:4], dtype=np.uint8)
+    sets = np.zeros(len(P), dtype=np.uint8)
+    if lib().smartgpu_iupac_sets(vals.ctypes.data, k, P.ctypes.data, len(P), sets.ctypes.data) != 0:
+        raise _err("iupac_sets")
+    return sets
 
 
 def _pattern_set(patterns):

@@ -27,6 +27,7 @@ KERNEL_UNIT = {
     "bndml_scan": "k_bndmx", "so_runs": "k_so", "kmp_runs": "k_kmp", "packed_scan": "k_packed", "packed_find": "k_packed",
     "generate_text": "k_util", "tile_fill": "k_util", "text_alphabet": "k_util", "probe_read": "k_util",
     "planes_pack": "k_planes", "planes_scan": "k_planes", "planes_find": "k_planes",
+    "planes_sets_scan": "k_planes", "planes_sets_find": "k_planes",
 }
 
 
