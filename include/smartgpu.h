@@ -394,6 +394,35 @@ int smartgpu_pfind_sets64(const uint8_t *sets, uint32_t m, const smartgpu_ptext 
  * accepts; it may be 0 (then the searches answer 0).  Any other byte in P: SMARTGPU_ERR_ARG, the message names position and
  * byte; nvalues outside 1..4 or a NULL pointer: SMARTGPU_ERR_ARG.  Nothing is written on refusal. */
 int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char *P, uint32_t m, uint8_t *sets);
+/* MISMATCHES on a packed text: the occurrences of P with at most k mismatches ("where does this 20-mer occur with at most
+ * two substitutions?").  Start position s (off <= s <= off + n - m) is an occurrence when its DISTANCE — the number of
+ * j < m with T[s+j] != P[j], the Hamming distance over bytes — is at most k; nothing in the reference does this.
+ * 0 <= k <= SMARTGPU_PMIS_MAX; k = 0 is smartgpu_psearch64 / smartgpu_pfind64.  k >= m is legal: every start position of
+ * the range is an occurrence, its distance is still reported.  A pattern byte the text does NOT hold is a mismatch in every
+ * window (the exact calls answer 0 for such a pattern; these calls do not): with u such bytes, u > k gives count 0 without
+ * a launch, otherwise the kernels run with the budget k - u, do not compare those positions, and u is part of every
+ * reported distance.  One pass over the planes whatever k is (planes_mis_scan, planes_mis_find): a bit-sliced counter
+ * of 1 / 2 / 3 dwords per 32 start positions for a budget up to 1 / 3 / 7 and a sticky "over budget" dword.
+ * The range convention, count width, times, cap / count / SMARTGPU_ERR_NOMEM behaviour and the order of the positions
+ * (ascending, relative to symbol 0) are those of smartgpu_psearch_sets64 / smartgpu_pfind_sets64.  mismatches may be NULL;
+ * otherwise it has cap entries and mismatches[i] receives the distance of positions[i].
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P == NULL, m = 0 or m > SMARTGPU_XSIZE,
+ * k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0.
+ * No launch: m > n (count 0), more foreign bytes than k (count 0).
+ * NOT offered: set patterns with mismatches, a batch call, insertions and deletions (edit distance), k > 7, byte texts.
+ * MEASURED on an MI355X, 1 Gi symbols (profiles/packed/RESULTS.md, "Mismatches"): on rand4, m = 8 .. 256, planes_mis_scan takes
+ * 1.22-1.26 / 1.25-1.94 / 1.34-2.11 / 1.55-3.56 x planes_scan's kernel time for k = 0 / 1 / 3 / 7 (per call 1.07-1.17 /
+ * 1.07-1.62 / 1.13-1.76 / 1.24-2.76 x), outside the run-to-run spread in every cell.  m = 16: ONE k = 1 call is 14.8 x
+ * faster than the 16 smartgpu_psearch_sets64 calls with one full-set position each that give the same answer (0.119 against
+ * 1.755 ms, counting only, no host union), outside the spread; one k = 2 call 114 x faster than its 120 placements (a
+ * sample timed and scaled).  smartgpu_pfind_mis64 (m = 20, k = 2): 1.26 x a one-N smartgpu_pfind_sets64.  Two-value texts
+ * with k = 7 and m > 32: nearly every wave verifies, 5.9 x the exact call on rand2 (planes of Infinity-Cache size).
+ * NOT measured: kUnroll, occupancy, the early leave's interval, texts beyond 1 Gi symbols. */
+#define SMARTGPU_PMIS_MAX 7
+int smartgpu_psearch_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                           uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_pfind_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                         uint64_t *positions, uint8_t *mismatches, uint64_t cap, uint64_t *count);
 /* smartgpu_probe_read_ms on the planes: the streaming-read time of the bytes a packed search reads (the plane roofline) */
 int smartgpu_ptext_probe_read_ms(const smartgpu_ptext *t, int reps, double *ms_per_pass);
 

@@ -2020,8 +2020,9 @@ bool copy_positions(DeviceCtx* d, uint64_t* dst, const unsigned long long* src, 
 // survivors of its own kFindSpan start positions counted from the range's first chunk, in the order the waves reserved them.
 // So the spans are found in one pass (the span number changes), ordered by it — one entry per span, not per position;
 // s_last is the last start position of the range — and moved only when they are out of order.  All `have` entries must be present (count <= cap).
+// shift: the entries hold their position above `shift` low bits (planes_mis_find: the distance) and are ordered whole.
 // false: the entries are not such spans (refused by the callers, never reported).
-bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t s_last)
+bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t s_last, uint32_t shift = 0)
 {
     static_assert((sg::kFindSpan & (sg::kFindSpan - 1)) == 0, "span number by division");
     const uint64_t base = s_begin / 128 * 128;
@@ -2029,7 +2030,7 @@ bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t s_last
     std::vector<Span> spans;
     bool ascending = true;
     for (uint64_t i = 0; i < have; ++i) {
-        const uint64_t key = (pos[i] - base) / sg::kFindSpan;
+        const uint64_t key = ((pos[i] >> shift) - base) / sg::kFindSpan;
         if (!spans.empty() && spans.back().key == key) {
             if (pos[i] <= pos[i - 1]) return false;  // not what planes_find writes (a retuned kernel whose spans are no longer these?)
             ++spans.back().len;
@@ -2073,9 +2074,10 @@ bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t s_last
 // One find on a packed text, n >= m: the device buffer, `launch(out, room)` — the pattern's staging, the cursor's memset
 // and the kernel, all on the device's stream —, the cursor's read-back, the positions to the host in ascending order.
 // *count always receives the number of occurrences when the device answered; the return codes are smartgpu_pfind64's.
+// shift: order_spans' (the entries reach `positions` as the kernel wrote them).
 template <typename Launch>
 int pfind_run(DeviceCtx* d, const char* call, const char* kernel, uint32_t m, uint64_t off, uint64_t n, uint64_t* positions,
-              uint64_t cap, uint64_t* count, unsigned long long* cursor, Launch launch)
+              uint64_t cap, uint64_t* count, unsigned long long* cursor, Launch launch, uint32_t shift = 0)
 {
     const uint64_t starts = n - m + 1;
     const uint64_t room = cap < starts ? cap : starts;  // no more positions than start positions
@@ -2098,7 +2100,7 @@ int pfind_run(DeviceCtx* d, const char* call, const char* kernel, uint32_t m, ui
         if (!copy_positions(d, positions, out, total)) {
             set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
             r = SMARTGPU_ERR_HIP;
-        } else if (!order_spans(positions, total, off, off + n - m)) {
+        } else if (!order_spans(positions, total, off, off + n - m, shift)) {
             set_error("%s: the positions are not ascending spans of %llu start positions", kernel, (unsigned long long)sg::kFindSpan);
             r = SMARTGPU_ERR_HIP;
         }
@@ -2190,6 +2192,87 @@ int check_psets_args(const char* call, const uint8_t* sets, uint32_t m, const sm
     if (rc != SMARTGPU_OK) return rc;
     if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
     return sets_planes(text, sets, m, Y, empty, full);
+}
+
+// ---- mismatches on packed texts (planes_mis_scan, planes_mis_find) ----
+}  // namespace
+// WEAK references, as launch_planes_sets_* above: a host program that links this file without k_planes.o still links.
+namespace sg {
+__attribute__((weak)) hipError_t launch_planes_mis_scan(const PlaneMisArgs& a, int planes, int num_cus, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_planes_mis_find(const PlaneMisArgs& a, unsigned long long* out, unsigned long long cap, int planes,
+                                                        int num_cus, hipStream_t stream);
+}  // namespace sg
+namespace {
+bool mis_launchers_linked()
+{
+    if (&sg::launch_planes_mis_scan && &sg::launch_planes_mis_find) return true;
+    set_error("planes_mis_scan / planes_mis_find are not linked into this program");
+    return false;
+}
+
+constexpr size_t kMisWords = 3 * sg::kPatWords;  // a pattern's two code planes and its skip plane
+
+// The pattern as planes X0, X1 (pattern_planes) and SKIP: bit j % 32 of X[2 * kPatWords + j / 32] = P[j] is a byte the text
+// does not hold (its code bits are zero).  Returns the number of such positions.
+uint32_t mis_pattern_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint32_t* X)
+{
+    int code_of[256];
+    for (int c = 0; c < 256; ++c) code_of[c] = -1;
+    for (int k = 0; k < t->nvalues; ++k) code_of[t->values[k]] = k;
+    std::memset(X, 0, 4 * kMisWords);
+    uint32_t foreign = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        const int c = code_of[P[j]];
+        if (c < 0) {
+            X[2 * sg::kPatWords + (j >> 5)] |= 1u << (j & 31);
+            ++foreign;
+            continue;
+        }
+        X[j >> 5] |= static_cast<uint32_t>(c & 1) << (j & 31);
+        X[sg::kPatWords + (j >> 5)] |= static_cast<uint32_t>(c >> 1) << (j & 31);
+    }
+    return foreign;
+}
+
+// What the mis kernels receive, n >= m, foreign <= k; the pattern's planes go through the staging buffer into the arena
+// when m > 32 (stage_mis).  The result slot is d->batch_counts[0].
+sg::PlaneMisArgs plane_mis_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* X, uint32_t m, uint32_t k, uint32_t foreign,
+                                uint64_t off, uint64_t n)
+{
+    sg::PlaneMisArgs a;
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.s_begin = off;
+    a.s_end = off + n - m + 1;
+    a.m = m;
+    a.x0 = X[0];
+    a.x1 = X[sg::kPatWords];
+    a.skip = X[2 * sg::kPatWords];
+    a.budget = k - foreign;
+    a.foreign = foreign;
+    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
+    a.count = d->batch_counts;
+    return a;
+}
+
+bool stage_mis(DeviceCtx* d, const uint32_t* X, uint32_t m)
+{
+    if (m <= 32) return true;  // the first 32 positions travel as kernel arguments
+    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
+    std::memcpy(d->pinned, X, 4 * kMisWords);
+    return hipMemcpyAsync(d->arena, d->pinned, 4 * kMisWords, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+}
+
+// the checks of both mis calls that need no device
+int check_pmis_args(const char* call, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                    const uint64_t* count)
+{
+    if (!P) { set_error("%s: P is NULL", call); return SMARTGPU_ERR_ARG; }
+    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u mismatches, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
+    const int rc = check_psearch_args(P, m, text, off, n);
+    if (rc != SMARTGPU_OK) return rc;
+    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
+    return SMARTGPU_OK;
 }
 
 }  // namespace
@@ -2482,6 +2565,72 @@ int smartgpu_pfind_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext*
         return stage_sets(d, Y, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
                sg::launch_planes_sets_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
     });
+}
+
+/* ---- mismatches: occurrences within Hamming distance k ---------------------------------------------------------------- */
+int smartgpu_psearch_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                           uint64_t* count, double* pre_ms, double* run_ms)
+{
+    const int rc = check_pmis_args("psearch_mis64", P, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    uint32_t X[kMisWords];
+    const uint32_t foreign = mis_pattern_planes(text, P, m, X);
+    uint64_t c = 0;
+    double pre = 0.0, run = 0.0;
+    if (foreign <= k && m <= n) {  // otherwise: more foreign bytes than mismatches allowed, or no window fits: no launch
+        DeviceCtx* d = mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+        if (!d) return SMARTGPU_ERR_HIP;
+        const double t_pre = now_ms();
+        if (!batch_reserve(d, 4 * kMisWords, 1)) return SMARTGPU_ERR_NOMEM;
+        if (!stage_mis(d, X, m)) { set_error("psearch_mis64: %s", hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
+        pre = now_ms() - t_pre;
+        const double t0 = now_ms();
+        const sg::PlaneMisArgs a = plane_mis_args(d, text, X, m, k, foreign, off, n);
+        HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(sg::launch_planes_mis_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+        run = now_ms() - t0;
+        // more occurrences than start positions: refused like a poisoned count, never reported
+        if (d->pinned_counts[0] > n - m + 1) { set_error("planes_mis_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
+        c = d->pinned_counts[0];
+    }
+    g_last_pre_ms = pre;
+    g_last_run_ms = run;
+    *count = c;
+    if (pre_ms) *pre_ms = pre;
+    if (run_ms) *run_ms = run;
+    return SMARTGPU_OK;
+}
+
+int smartgpu_pfind_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                         uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
+{
+    if (cap && !positions) { set_error("pfind_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
+    const int rc = check_pmis_args("pfind_mis64", P, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    uint32_t X[kMisWords];
+    const uint32_t foreign = mis_pattern_planes(text, P, m, X);
+    if (foreign > k || m > n) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    DeviceCtx* d = mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, 4 * kMisWords, 1)) return SMARTGPU_ERR_NOMEM;
+    const sg::PlaneMisArgs a = plane_mis_args(d, text, X, m, k, foreign, off, n);
+    const int r = pfind_run(d, "pfind_mis64", "planes_mis_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
+        return stage_mis(d, X, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+               sg::launch_planes_mis_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
+    }, sg::kMisShift);
+    if (r != SMARTGPU_OK) return r;
+    // the entries are position << kMisShift | distance, in ascending order: unpacked in place
+    for (uint64_t i = 0; i < *count; ++i) {
+        const uint64_t e = positions[i];
+        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << sg::kMisShift) - 1u));
+        positions[i] = e >> sg::kMisShift;
+    }
+    return SMARTGPU_OK;
 }
 
 int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)

@@ -176,7 +176,9 @@ static __device__ __attribute__((noinline)) uint32_t epsm_verify(const uint8_t* 
 }
 
 // ALGO only tags the instantiation (rocprofv3 shows packed_scan<256, 4, 5, ..> for
-// EPSM and packed_scan<256, 4, 0, ..> for Horspool's short-pattern regime).
+// EPSM and packed_scan<256, 4, 0, ..> for Horspool's short-pattern regime).  The A/B library, which the measurements
+// load, tags Boyer-Moore and BNDM as well; the product library carries those byte-identical instantiations once, under
+// Horspool's tag (launch_packed_as).
 template <int THREADS, int ROWS, int ALGO, int MODE, int POLICY>
 __global__ __launch_bounds__(THREADS) void packed_scan(ScanArgs a1, uint64_t row_first,
                                                        uint64_t nrows, const BatchItem* __restrict__ batch)
@@ -403,6 +405,11 @@ static hipError_t launch_packed_as(const ScanArgs& a, int num_cus, hipStream_t s
     const TileRange tr = tiles_for(a.s_begin, a.s_end, shuf ? (uint64_t)(kEpsmT / 64) * 1008 : (uint64_t)kEpsmT * 16);
     if (tr.count == 0) return hipSuccess;
     const int rows = 4;  // rows in flight per workgroup step (1 and 2 measured slower, profiles/r01)
+#ifdef SMARTGPU_AB
+    constexpr int kTag = ALGO;
+#else
+    constexpr int kTag = ALGO == SMARTGPU_EPSM ? SMARTGPU_EPSM : SMARTGPU_HOR;  // the same code under one name
+#endif
     uint64_t grid = ((uint64_t)tr.count + rows - 1) / rows;
     // no LDS tile, no barrier in the loop: more, smaller shares balance better — 16 workgroups per
     // CU (two rounds) measured 76-79 % against 73-77 % with 8 on sparse hits and the same on dense
@@ -410,7 +417,7 @@ static hipError_t launch_packed_as(const ScanArgs& a, int num_cus, hipStream_t s
     const uint64_t cap = (uint64_t)num_cus * (g_tune[4] ? g_tune[4] : 16);
     if (grid > cap) grid = cap;
 #define SG_PACKED(M_, P_)                                                                           \
-    hipLaunchKernelGGL((packed_scan<kEpsmT, 4, ALGO, M_, P_>), dim3((uint32_t)grid, g_batch.count), dim3(kEpsmT), 128, \
+    hipLaunchKernelGGL((packed_scan<kEpsmT, 4, kTag, M_, P_>), dim3((uint32_t)grid, g_batch.count), dim3(kEpsmT), 128, \
                        stream, a, tr.first, (uint64_t)tr.count, g_batch.items)
     // D_: the mode's own data path — 5 (one load, the neighbour's bytes by DPP) except for the masked compares of MODE 0
 #ifdef SMARTGPU_AB  // the other load policies: both loads cached (1), one non-temporal load + shuffle (3)

@@ -1,6 +1,6 @@
 // k_planes.hip — packed texts: planes_pack (byte text -> bit planes, once per text), planes_scan (the matcher on planes),
 // planes_find (the same matcher with an output stage: positions), planes_sets_scan / planes_sets_find (their siblings for
-// patterns whose positions accept a SET of symbols)
+// patterns whose positions accept a SET of symbols), planes_mis_scan / planes_mis_find (occurrences with up to k mismatches)
 // (one translation unit per kernel family: dev_common.hpp; the layout: planes.hpp)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
@@ -573,6 +573,289 @@ hipError_t launch_planes_sets_find(const PlaneSetArgs& a, unsigned long long* ou
         hipLaunchKernelGGL(planes_sets_find<2>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
     else
         hipLaunchKernelGGL(planes_sets_find<1>, dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// planes_mis_scan<PLANES, BITS>, planes_mis_find<PLANES, BITS>: occurrences with at most `budget` MISMATCHES — they count /
+// list the start positions s in [s_begin, s_end) whose number of j < m with T[s + j] != P[j] (positions of the skip plane
+// excepted: pattern bytes the text does not hold, counted by the host) is at most a.budget.  Siblings of the sets kernels:
+// the same geometry, loads, range masks, early leave and output stage; what differs is the state per 32 positions.
+//
+// In place of the one dword M of live positions: a BIT-SLICED COUNTER C[0..BITS) — bit i of C[b] is bit b of position i's
+// count — and one sticky dword S, "over budget".  Every counter starts at 2^BITS - 1 - budget, so the carry out of the top
+// bit is exactly "one mismatch more than the budget"; it ORs into S and stays there: a window with hundreds of mismatches
+// wraps its counter bits many times, S is the verdict.  BITS = 1 / 2 / 3 serves budgets up to 1 / 3 / 7 (the launcher
+// picks).  Per pattern symbol and dword: the v_alignbit per plane, then the mismatch dword f(t0, t1) — the complement of
+// planes_kill's table for the symbol's code — is never formed: the counter's lowest stage takes it inside its two v_bitop3
+// (sum C0 ^ f, carry C0 & f), the higher stages ripple (v_xor, v_and; the last: v_xor and one v_bitop3 S | C & carry).
+// 5 / 6 / 8 vector instructions per 32 positions and symbol on two planes against planes_scan's 3.
+// Positions outside the range start with their S bit set.  After every eight symbols the wave leaves when all of its
+// positions are over budget: later than the exact scan, the more so the larger the budget.
+// Symbols from the 32nd on: planes_mis_verify.  The find's entries are pos << 3 | distance: monotone in pos, so the spans
+// are ordered on the host as planes_find's (api.cpp order_spans, with a shift).
+// kUnroll: planes_scan's (2 chunks per trip).  Occupancy: planes_scan's 8 workgroups per CU (39-63 VGPRs) — except BITS = 3
+// on TWO planes, which keeps 3 * kChunk * kUnroll counter dwords beside both planes' words and does not fit 64 VGPRs
+// without scratch (67 / 69 for scan / find): it is bounded for 128 and launched at 7 workgroups per CU.  Neither choice is swept.  planes_scan,
+// planes_find and planes_sets_* are not touched.
+// ---------------------------------------------------------------------------
+template <int PLANES, int BITS, uint32_t F>  // F: the table of "mismatch" over t0 = 0xCC, t1 = 0xAA
+static __device__ __forceinline__ void planes_mis_step(uint32_t (&C)[BITS][kChunk], uint32_t (&S)[kChunk], const PlaneWords& t, uint32_t j)
+{
+#pragma unroll
+    for (uint32_t w = 0; w < kChunk; ++w) {
+        const uint32_t t0 = __builtin_amdgcn_alignbit(t.a[w + 1], t.a[w], j);
+        const uint32_t t1 = PLANES == 2 ? __builtin_amdgcn_alignbit(t.b[w + 1], t.b[w], j) : 0u;
+        uint32_t carry = __builtin_amdgcn_bitop3_b32(C[0][w], t0, t1, 0xF0u & F);
+        C[0][w] = __builtin_amdgcn_bitop3_b32(C[0][w], t0, t1, 0xF0u ^ F);
+        if constexpr (BITS == 1) {
+            S[w] |= carry;
+        } else {
+#pragma unroll
+            for (int b = 1; b < BITS - 1; ++b) {
+                const uint32_t c = C[b][w];
+                C[b][w] = c ^ carry;
+                carry &= c;
+            }
+            const uint32_t c = C[BITS - 1][w];
+            C[BITS - 1][w] = c ^ carry;
+            S[w] = __builtin_amdgcn_bitop3_b32(S[w], c, carry, 0xF8);  // S | c & carry
+        }
+    }
+}
+
+// symbols [j0, j1) (j1 <= 32) of the pattern's first block, bits x0 / x1, skip: positions that are not compared
+template <int PLANES, int BITS>
+static __device__ __forceinline__ void planes_mis_add(uint32_t (&C)[BITS][kChunk], uint32_t (&S)[kChunk], const PlaneWords& t, uint32_t x0,
+                                                      uint32_t x1, uint32_t skip, uint32_t j0, uint32_t j1)
+{
+    for (uint32_t j = j0; j < j1; ++j) {
+        if ((skip >> j) & 1u) continue;                                                     // wave-uniform
+        const uint32_t c = ((x0 >> j) & 1u) | (PLANES == 2 ? ((x1 >> j) & 1u) << 1 : 0u);  // wave-uniform
+        if (PLANES == 2) {
+            if (c == 0) planes_mis_step<PLANES, BITS, 0xEE>(C, S, t, j);       // t0 | t1
+            else if (c == 1) planes_mis_step<PLANES, BITS, 0xBB>(C, S, t, j);  // ~t0 | t1
+            else if (c == 2) planes_mis_step<PLANES, BITS, 0xDD>(C, S, t, j);  // t0 | ~t1
+            else planes_mis_step<PLANES, BITS, 0x77>(C, S, t, j);              // ~t0 | ~t1
+        } else {
+            if (c == 0) planes_mis_step<PLANES, BITS, 0xCC>(C, S, t, j);       // t0
+            else planes_mis_step<PLANES, BITS, 0x33>(C, S, t, j);              // ~t0
+        }
+    }
+}
+
+// planes_verify with a count: the whole wave works on ONE lane's live positions (R, and their counters Cs: wave-uniform,
+// scalar).  Lane l takes block k0 + l of the pattern — x0 / x1 and the skip plane from memory, the five text dwords k dwords
+// behind the chunk — and popcounts its mismatch dword (skipped positions, the part of the last block beyond m and lanes
+// beyond the last block masked off).  The wave SUMS the lanes' counts: they are at most 32, so six ballots, one per bit of
+// the count, and six scalar popcounts give the sum wave-uniform with no shuffle.  It is added to the position's counter; a
+// counter beyond 2^BITS - 1 is over budget, otherwise the new value goes back into the counter bits: the find reports it.
+template <int PLANES, int BITS>
+static __device__ __forceinline__ void planes_mis_verify(uint32_t (&R)[kChunk], uint32_t (&Cs)[BITS][kChunk], const PlaneMisArgs& a, uint64_t dw)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t k0 = 1; 32 * k0 < a.m && (R[0] | R[1] | R[2] | R[3]) != 0; k0 += 64) {
+        const bool valid = 32 * (k0 + lane) < a.m;
+        const uint32_t k = valid ? k0 + lane : k0;
+        const uint32_t left = a.m - 32 * k;
+        const uint32_t bmask = !valid ? 0u : left >= 32 ? ~0u : (1u << left) - 1u;  // the pattern's last block may be partial
+        uint32_t ta[kChunk + 1], tb[kChunk + 1];
+        __builtin_memcpy(ta, a.p0 + dw + k, 4 * (kChunk + 1));
+        if (PLANES == 2) __builtin_memcpy(tb, a.p1 + dw + k, 4 * (kChunk + 1));
+        const uint32_t x0 = a.pat[k], x1 = PLANES == 2 ? a.pat[kPatWords + k] : 0u;
+        const uint32_t cmp = bmask & ~a.pat[2 * kPatWords + k];
+#pragma unroll
+        for (uint32_t w = 0; w < kChunk; ++w) {
+            uint32_t r = R[w];
+            while (r) {
+                const uint32_t i = __builtin_ctz(r);
+                r &= r - 1;
+                uint32_t d = __builtin_amdgcn_alignbit(ta[w + 1], ta[w], i) ^ x0;
+                if (PLANES == 2) d |= __builtin_amdgcn_alignbit(tb[w + 1], tb[w], i) ^ x1;
+                const uint32_t cnt = __builtin_popcount(d & cmp);
+                uint32_t cur = 0;
+#pragma unroll
+                for (int b = 0; b < 6; ++b) cur += (uint32_t)__builtin_popcountll(__ballot((cnt >> b) & 1u)) << b;
+#pragma unroll
+                for (int b = 0; b < BITS; ++b) cur += ((Cs[b][w] >> i) & 1u) << b;
+                if (cur > (1u << BITS) - 1u) {
+                    R[w] &= ~(1u << i);
+                } else {
+#pragma unroll
+                    for (int b = 0; b < BITS; ++b) Cs[b][w] = (Cs[b][w] & ~(1u << i)) | (((cur >> b) & 1u) << i);
+                }
+            }
+        }
+    }
+}
+
+// The loop skeleton is planes_sets_body's: a change to one belongs in the other.  smem: flush_hits' 128 bytes (the scan only).
+template <int PLANES, int BITS, bool FIND>
+static __device__ __forceinline__ void planes_mis_body(const PlaneMisArgs& a, uint8_t* smem, unsigned long long* __restrict__ out,
+                                                       unsigned long long cap)
+{
+    constexpr uint64_t kPos = 32 * kChunk;  // start positions per chunk
+    const uint64_t c_end = (a.s_end + kPos - 1) / kPos;
+    const uint64_t stride = (uint64_t)gridDim.x * kPlanesT * kUnroll;
+    const uint32_t f1 = a.m < 32 ? a.m : 32u;
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t start = (1u << BITS) - 1u - a.budget;  // every counter's first value: the carry out of bit BITS - 1 is "over budget"
+    uint32_t hits = 0;
+    // the trip count is the WAVE's (its first chunk decides): every lane stays for the ballots, the verification and the shuffles
+    for (uint64_t cw = a.s_begin / kPos + (uint64_t)blockIdx.x * kPlanesT * kUnroll + 64u * wave; cw < c_end; cw += stride) {
+        PlaneWords t[kUnroll];
+        uint32_t C[kUnroll][BITS][kChunk], S[kUnroll][kChunk];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint64_t c = cw + (uint64_t)u * kPlanesT + lane;
+            const bool in = c < c_end;
+            const uint64_t dw = in ? c * kChunk : 0;
+            const uint4 va = ld_stream16(reinterpret_cast<const uint8_t*>(a.p0 + dw));
+            t[u].a[0] = va.x; t[u].a[1] = va.y; t[u].a[2] = va.z; t[u].a[3] = va.w;
+            t[u].a[4] = a.p0[dw + kChunk];
+            if (PLANES == 2) {
+                const uint4 vb = ld_stream16(reinterpret_cast<const uint8_t*>(a.p1 + dw));
+                t[u].b[0] = vb.x; t[u].b[1] = vb.y; t[u].b[2] = vb.z; t[u].b[3] = vb.w;
+                t[u].b[4] = a.p1[dw + kChunk];
+            }
+            const bool inner = c * kPos >= a.s_begin && (c + 1) * kPos <= a.s_end;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) {
+                S[u][w] = !in ? ~0u : inner ? 0u : ~range_mask(c * kPos + 32 * w, a.s_begin, a.s_end);
+#pragma unroll
+                for (int b = 0; b < BITS; ++b) C[u][b][w] = (start >> b) & 1u ? ~0u : 0u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint32_t live = ~(S[u][0] & S[u][1] & S[u][2] & S[u][3]);
+            for (uint32_t j0 = 0; j0 < f1; j0 += 8) {
+                planes_mis_add<PLANES, BITS>(C[u], S[u], t[u], a.x0, a.x1, a.skip, j0, j0 + 8 < f1 ? j0 + 8 : f1);
+                live = ~(S[u][0] & S[u][1] & S[u][2] & S[u][3]);
+                if (!__any(live != 0)) break;
+            }
+            if (a.m > 32) {  // a lane has positions within the budget after 32 symbols
+                unsigned long long todo = __ballot(live != 0);
+                while (todo) {
+                    const int src = __builtin_ctzll(todo);  // wave-uniform
+                    todo &= todo - 1;
+                    const uint64_t dw = (cw + (uint64_t)u * kPlanesT + (uint32_t)src) * kChunk;
+                    uint32_t R[kChunk], Cs[BITS][kChunk];
+#pragma unroll
+                    for (uint32_t w = 0; w < kChunk; ++w) {
+                        R[w] = ~__builtin_amdgcn_readlane(S[u][w], src);
+#pragma unroll
+                        for (int b = 0; b < BITS; ++b) Cs[b][w] = __builtin_amdgcn_readlane(C[u][b][w], src);
+                    }
+                    planes_mis_verify<PLANES, BITS>(R, Cs, a, dw);
+                    if (lane == (uint32_t)src) {
+#pragma unroll
+                        for (uint32_t w = 0; w < kChunk; ++w) {
+                            S[u][w] = ~R[w];
+#pragma unroll
+                            for (int b = 0; b < BITS; ++b) C[u][b][w] = Cs[b][w];
+                        }
+                    }
+                }
+                live = ~(S[u][0] & S[u][1] & S[u][2] & S[u][3]);
+            }
+            uint32_t mine = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) mine += __builtin_popcount(~S[u][w]);
+            if constexpr (!FIND) {
+                hits += mine;
+            } else {
+                if (!__any(live != 0)) continue;
+                // planes_find's output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
+                uint32_t incl = mine;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = __shfl_up(incl, d, 64);
+                    if (lane >= (uint32_t)d) incl += up;
+                }
+                const uint32_t total = __shfl(incl, 63, 64);
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
+                base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                       __builtin_amdgcn_readfirstlane((uint32_t)base);
+                unsigned long long slot = base + (incl - mine);
+                const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
+                const uint32_t bias = a.foreign - start;  // distance = counter - start + the positions the host counted
+#pragma unroll
+                for (uint32_t w = 0; w < kChunk; ++w) {
+                    uint32_t r = ~S[u][w];
+                    while (r) {
+                        const uint32_t i = __builtin_ctz(r);
+                        r &= r - 1;
+                        uint32_t dist = bias;
+#pragma unroll
+                        for (int b = 0; b < BITS; ++b) dist += ((C[u][b][w] >> i) & 1u) << b;
+                        if (slot < cap) out[slot] = (pos + 32 * w + i) << kMisShift | dist;
+                        ++slot;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (!FIND) flush_hits(hits, a.count, smem, reinterpret_cast<const uint8_t*>(a.p0));
+}
+
+// waves per SIMD the register allocation is bounded for, and workgroups per CU of the launch (see above)
+template <int PLANES, int BITS> constexpr int kMisWaves = PLANES == 2 && BITS == 3 ? 4 : 8;
+constexpr int mis_wgs(int planes, int bits) { return planes == 2 && bits == 3 ? 7 : kPlanesWgs; }
+
+template <int PLANES, int BITS>
+__global__ __launch_bounds__(kPlanesT, (kMisWaves<PLANES, BITS>)) void planes_mis_scan(PlaneMisArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // 128 bytes: flush_hits
+    planes_mis_body<PLANES, BITS, false>(a, smem, nullptr, 0);
+}
+
+template <int PLANES, int BITS>
+__global__ __launch_bounds__(kPlanesT, (kMisWaves<PLANES, BITS>)) void planes_mis_find(PlaneMisArgs a, unsigned long long* __restrict__ out, unsigned long long cap)
+{
+    planes_mis_body<PLANES, BITS, true>(a, nullptr, out, cap);
+}
+
+// Grid: launch_planes_scan's with mis_wgs workgroups per CU.  BITS from the budget: 1 / 2 / 3 for at most 1 / 3 / 7.
+static uint32_t planes_mis_grid(const PlaneMisArgs& a, int planes, int num_cus, int bits)
+{
+    constexpr uint64_t kPos = 32 * kChunk;
+    const uint64_t chunks = (a.s_end + kPos - 1) / kPos - a.s_begin / kPos;
+    const uint64_t want = (chunks + kPlanesT * kUnroll - 1) / (kPlanesT * kUnroll);
+    return (uint32_t)std::min<uint64_t>(want, (uint64_t)num_cus * mis_wgs(planes, bits));
+}
+
+hipError_t launch_planes_mis_scan(const PlaneMisArgs& a, int planes, int num_cus, hipStream_t stream)
+{
+    if (a.budget > SMARTGPU_PMIS_MAX) return hipErrorInvalidValue;
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    const int bits = a.budget <= 1 ? 1 : a.budget <= 3 ? 2 : 3;
+    const uint32_t grid = planes_mis_grid(a, planes, num_cus, bits);
+#define SG_MIS_SCAN(p_, b_) hipLaunchKernelGGL((planes_mis_scan<p_, b_>), dim3(grid), dim3(kPlanesT), 128, stream, a)
+    if (planes == 2) {
+        if (bits == 1) SG_MIS_SCAN(2, 1); else if (bits == 2) SG_MIS_SCAN(2, 2); else SG_MIS_SCAN(2, 3);
+    } else {
+        if (bits == 1) SG_MIS_SCAN(1, 1); else if (bits == 2) SG_MIS_SCAN(1, 2); else SG_MIS_SCAN(1, 3);
+    }
+#undef SG_MIS_SCAN
+    return hipGetLastError();
+}
+
+hipError_t launch_planes_mis_find(const PlaneMisArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                                  hipStream_t stream)
+{
+    if (a.budget > SMARTGPU_PMIS_MAX) return hipErrorInvalidValue;
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    const int bits = a.budget <= 1 ? 1 : a.budget <= 3 ? 2 : 3;
+    const uint32_t grid = planes_mis_grid(a, planes, num_cus, bits);
+#define SG_MIS_FIND(p_, b_) hipLaunchKernelGGL((planes_mis_find<p_, b_>), dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap)
+    if (planes == 2) {
+        if (bits == 1) SG_MIS_FIND(2, 1); else if (bits == 2) SG_MIS_FIND(2, 2); else SG_MIS_FIND(2, 3);
+    } else {
+        if (bits == 1) SG_MIS_FIND(1, 1); else if (bits == 2) SG_MIS_FIND(1, 2); else SG_MIS_FIND(1, 3);
+    }
+#undef SG_MIS_FIND
     return hipGetLastError();
 }
 

@@ -68,4 +68,28 @@ hipError_t launch_planes_sets_scan(const PlaneSetArgs& a, int planes, int num_cu
 hipError_t launch_planes_sets_find(const PlaneSetArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
                                    hipStream_t stream);
 
+// MISMATCHES: occurrences with at most `budget` positions j where T[s + j] != P[j].  What planes_mis_scan and planes_mis_find
+// receive (by value): PlaneArgs with a third plane of the pattern, the SKIP plane — positions that are not compared (pattern
+// bytes the text does not hold: a mismatch in every window, counted by the host, which lowers the budget by their number and
+// passes it as `foreign`; their code bits are zero).
+struct PlaneMisArgs {
+    const uint32_t* p0;         // as PlaneArgs
+    const uint32_t* p1;
+    uint64_t s_begin, s_end;
+    uint32_t m;
+    uint32_t x0, x1;            // bits 0 / 1 of the codes of the pattern's first 32 symbols
+    uint32_t skip;              // bit j: pattern position j < 32 is not compared
+    uint32_t budget;            // mismatches allowed at the compared positions, <= SMARTGPU_PMIS_MAX
+    uint32_t foreign;           // added to every distance the find reports (budget + foreign <= SMARTGPU_PMIS_MAX)
+    const uint32_t* pat;        // device, m > 32 only: u32 X0[kPatWords], X1[kPatWords], SKIP[kPatWords]
+    unsigned long long* count;  // device result slot (pre-zeroed)
+};
+// Grid, occupancy and range convention: launch_planes_scan's.  The find's entries are (position << kMisShift) | distance,
+// distance = mismatches at the compared positions + foreign; their spans are planes_find's, taken on the position.
+constexpr uint32_t kMisShift = 3;
+static_assert(SMARTGPU_PMIS_MAX < (1u << kMisShift), "a distance fits below the position");
+hipError_t launch_planes_mis_scan(const PlaneMisArgs& a, int planes, int num_cus, hipStream_t stream);
+hipError_t launch_planes_mis_find(const PlaneMisArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                                  hipStream_t stream);
+
 }  // namespace sg

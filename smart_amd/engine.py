@@ -126,6 +126,8 @@ def _load(path):
         "smartgpu_psearch_sets64": (i32, [vp, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_sets64": (i32, [vp, u32, vp, u64, u64, vp, u64, C.POINTER(u64)]),
         "smartgpu_iupac_sets": (i32, [vp, i32, vp, u32, vp]),
+        "smartgpu_psearch_mis64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_pfind_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
     }
     for a in ALGOS:
         sig["smartgpu_%s_search" % a] = (i32, [vp, i32, vp, i32])
@@ -548,6 +550,41 @@ def pfind_sets(sets, ptext, off=0, n=None, cap=1 << 20):
     if rc != 0:
         raise _err("pfind_sets64 rc=%d" % rc)
     return out[:c.value].copy(), int(c.value)
+
+
+def psearch_mis(P, ptext, k, off=0, n=None):
+    """(count, pre_ms, run_ms) of the start positions in symbols [off, off+n) of a PackedText where P occurs with at most k
+    mismatches (Hamming distance over bytes; 0 <= k <= 7; smartgpu_psearch_mis64).  A byte of P the text does not
+    hold is a mismatch in every window."""
+    P = _u8(P)
+    if n is None:
+        n = len(ptext) - off
+    c = C.c_uint64(0)
+    pre = C.c_double(0.0)
+    run = C.c_double(0.0)
+    rc = lib().smartgpu_psearch_mis64(P.ctypes.data, len(P), k, ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
+    if rc != 0:
+        raise _err("psearch_mis64 rc=%d" % rc)
+    return int(c.value), float(pre.value), float(run.value)
+
+
+def pfind_mis(P, ptext, k, off=0, n=None, cap=1 << 20):
+    """(positions, mismatches, count) of P with at most k mismatches (psearch_mis) in symbols [off, off+n) of a PackedText:
+    the ascending start positions (uint64, relative to symbol 0), the distance of each (uint8) and their number;
+    (None, None, count) when there are more than `cap`."""
+    P = _u8(P)
+    if n is None:
+        n = len(ptext) - off
+    out = np.empty(max(cap, 1), dtype=np.uint64)
+    mis = np.empty(max(cap, 1), dtype=np.uint8)
+    c = C.c_uint64(0)
+    rc = lib().smartgpu_pfind_mis64(P.ctypes.data, len(P), k, ptext._h, off, n, out.ctypes.data if cap else None,
+                                    mis.ctypes.data if cap else None, cap, C.byref(c))
+    if rc == -5 and c.value > cap:
+        return None, None, int(c.value)
+    if rc != 0:
+        raise _err("pfind_mis64 rc=%d" % rc)
+    return out[:c.value].copy(), mis[:c.value].copy(), int(c.value)
 
 
 def iupac_sets(pattern, values):

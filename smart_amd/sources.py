@@ -28,6 +28,7 @@ KERNEL_UNIT = {
     "generate_text": "k_util", "tile_fill": "k_util", "text_alphabet": "k_util", "probe_read": "k_util",
     "planes_pack": "k_planes", "planes_scan": "k_planes", "planes_find": "k_planes",
     "planes_sets_scan": "k_planes", "planes_sets_find": "k_planes",
+    "planes_mis_scan": "k_planes", "planes_mis_find": "k_planes",
 }
 
 
