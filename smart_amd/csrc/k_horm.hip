@@ -6,25 +6,19 @@
 
 namespace sg {
 
-// Loop states per lane (1, 2 or 4 "chains"): a lane walks ALL its patterns in one loop over (pattern, window end) — see
-// the kernel — and a chain is one such walk over a contiguous share of the pass's patterns.  The chains of a lane are
-// independent chains of dependent LDS reads (text byte, table entry, add) stepped in one loop body: more of them shorten
-// the dependent chain and issue a few more steps (a share that ends early idles).  The default is the measured one
-// (profiles/coalesce/RESULTS.md); a macro, as tools/build_variant.sh builds the variants for an A/B.
-#ifndef SMARTGPU_HORM_CHAINS
-#define SMARTGPU_HORM_CHAINS 1
-#endif
-
 // ---------------------------------------------------------------------------
 // hor_scan<.., VAR 0> (k_hor.hip) with the tile staged ONCE for np <= NP patterns: searches of one text that are queued
 // together (api.cpp) share the fetch and HBM bytes per pattern fall by np.  Same tiles on absolute offsets indexed by
 // window end, same back halo, same prefetch one tile ahead, same swizzle, same range clamps.
-// LDS: u64 blob[8] | u64 count[8] | u64 hits[8] | np x (u16 tab[256] | pattern tail P[m-1-H..m-1]) | text [tile0-H16, tile0+TB)
-// The walk: eight walks of a staged tile cost more than its fetch, so a pass is bound by the walk, and a wave's walk
-// lasts as long as its slowest lane's.  A lane therefore holds (pattern g, window end e, table offset) and, when a shift
-// takes e past its 64-byte segment, moves on to the next pattern IN THE SAME ITERATION; the loop ends when every lane has
-// been through all patterns.  The wave waits for the lane with the longest SUM over the patterns (as hor_flat and bm_scan
-// wait for the longest sum over a lane's state), not for the sum over the patterns of the slowest lane of each.
+// LDS: u64 blob[8] | u64 count[8] | u64 hits[8] | u32 gram[kGramSlots] | np x pattern tail P[m-1-H..m-1] | text [tile0-H16, tile0+TB)
+// The walk: a Horspool walk per pattern asks np times, one pattern at a time, whether a pattern ends near a window end,
+// and np such walks of a staged tile cost more than its fetch.  ONE walk per lane asks it for all patterns at once:
+// the workgroup builds, in its prologue, the skip table of multi.hpp from the pattern bytes in the blobs — indexed by
+// the window's last two bytes, the least shift any pattern of the pass allows and the patterns whose last gram falls
+// into the slot (LDS atomics: min for the shifts, a barrier, or for the pattern bits).  np x (m - 2) grams hardly fill
+// kGramSlots slots, so nearly every step moves the window end by m - 1 and a lane leaves its 64-byte segment after
+// about 64 / (m - 1) steps whatever np is.  A step: two byte reads (tile_at permutes dwords, the two bytes of a gram
+// may lie in different ones), the slot, the entry; compare for every pattern bit; add the shift.
 // The arrays of MultiArgs are indexed with compile-time constants only, once, in the prologue that copies the pointers
 // to LDS (a run-time index into the arguments makes the compiler select between addresses and load through flat_load);
 // a pattern's pointer is read from LDS as a number and cast to GLOBAL memory.  The kernel is as long as hor_scan
@@ -35,8 +29,9 @@ namespace sg {
 // to its pattern's LDS counter, and at the end the workgroup adds every non-zero counter to that pattern's result slot.
 // Not through the staging slots of flush_hits: those assume ONE flush per grid, and here a grid flushes np sums.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kHormHead = 3 * 8 * kMultiMax;  // the three u64 arrays in front of the tables
-static_assert(kHormHead % 64 == 0, "the tables and the tile stay 16-byte aligned");
+constexpr uint32_t kHormHead = 3 * 8 * kMultiMax;  // the three u64 arrays in front of the skip table
+constexpr uint32_t kHormGram = 4 * kGramSlots;    // the skip table
+static_assert(kHormHead % 64 == 0 && kHormGram % 64 == 0, "the tails and the tile stay 16-byte aligned");
 
 // a pointer into global memory from the number an LDS slot holds (per lane: lanes may ask for different patterns)
 __device__ __forceinline__ const uint8_t* horm_global(unsigned long long v)
@@ -83,17 +78,17 @@ template <int THREADS, int L, int NP>
 __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t tile_first, uint32_t ntiles)
 {
     constexpr int TB = THREADS * L;
-    constexpr int C = SMARTGPU_HORM_CHAINS;
-    static_assert(NP <= kMultiMax && (C == 1 || C == 2 || C == 4), "one, two or four chains");
+    static_assert(NP <= kMultiMax && NP <= 16, "a pattern bit per pattern in an entry's high half");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t m = a.m, H = a.halo, H16 = round16(H), np = a.np;
     const bool in_memory = m - 1 > H;  // windows are completed in HBM
-    const uint32_t slot = 512 + round16(H + 1);  // one pattern's tab + ptail; ptail[H-k] == P[m-1-k]
+    const uint32_t tslot = round16(H + 1);  // one pattern's tail; ptail[H-k] == P[m-1-k]
     unsigned long long* blobs = reinterpret_cast<unsigned long long*>(smem);
     unsigned long long* counts = blobs + kMultiMax;
     unsigned long long* sums = counts + kMultiMax;
-    uint8_t* tabs = smem + kHormHead;
-    uint8_t* txt = tabs + np * slot;  // txt[H16 + x] == T[tile0 + x]
+    uint32_t* gram = reinterpret_cast<uint32_t*>(smem + kHormHead);
+    uint8_t* tails = smem + kHormHead + kHormGram;
+    uint8_t* txt = tails + np * tslot;  // txt[H16 + x] == T[tile0 + x]
 
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -103,16 +98,28 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
             sums[i] = 0;
         }
     }
+    const uint32_t dflt = gram_default(m);
+    for (uint32_t j = threadIdx.x; j < kGramSlots; j += THREADS) gram[j] = dflt;
     __syncthreads();
     for (uint32_t i = 0; i < np; ++i) {
         const uint8_t* blob = horm_global(horm_first(blobs[i]));
-        uint16_t* tab = reinterpret_cast<uint16_t*>(tabs + i * slot);
-        uint8_t* ptail = tabs + i * slot + 512;
-        for (uint32_t j = threadIdx.x; j < 256; j += THREADS) tab[j] = reinterpret_cast<const uint16_t*>(blob + kTableOff)[j];
+        uint8_t* ptail = tails + i * tslot;
         for (uint32_t j = threadIdx.x; j <= H; j += THREADS) ptail[j] = blob[m - 1 - H + j];
     }
-    // chain c walks the patterns [c * share, (c + 1) * share) below np: none for a chain past the last pattern
-    const uint32_t share = (np + C - 1) / C;
+    // shifts: thread x takes position gram_first(m) + x % kGramCap of pattern x / kGramCap (at most kGramCap - 1
+    // positions of a pattern shift by less than the default)
+    for (uint32_t x = threadIdx.x; x < np * kGramCap; x += THREADS) {
+        const uint32_t i = gram_first(m) + x % kGramCap;
+        if (i + 3 <= m) {
+            const uint8_t* blob = horm_global(blobs[x / kGramCap]);
+            atomicMin(gram + gram_slot(blob[i], blob[i + 1]), gram_shift(m, i));
+        }
+    }
+    __syncthreads();  // every shift is in before a pattern bit makes an entry larger
+    if (threadIdx.x < np) {
+        const uint8_t* blob = horm_global(blobs[threadIdx.x]);
+        atomicOr(gram + gram_slot(blob[m - 2], blob[m - 1]), gram_entry_pattern_bit(threadIdx.x));
+    }
 
     const uint64_t e_begin = a.s_begin + m - 1, e_end = a.s_end + m - 1;
     const uint64_t t_end = tile_first + ntiles;
@@ -149,56 +156,32 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
         const bool any = lo < hi;
         const uint32_t e0 = any ? (uint32_t)(lo - tile0) + H16 : H16;
         const uint32_t ehi = any ? (uint32_t)(hi - tile0) + H16 : H16;
-        // the staged tile, walked for all patterns in one loop: per chain the pattern g (up to gend), its window end e
-        // and the offset of its table
-        uint32_t g[C], gend[C], e[C], tb[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            gend[c] = min((c + 1) * share, np);
-            g[c] = any ? min(c * share, np) : gend[c];
-            e[c] = e0;
-            tb[c] = g[c] * slot;
-        }
         bool parked = false;  // first candidate of this tile awaiting the wave-wide compare, and its pattern
         uint32_t parked_g = 0;
         const uint8_t* parked_at = a.text;
-        for (;;) {
-            bool more = false;
-#pragma unroll
-            for (int c = 0; c < C; ++c) more |= g[c] < gend[c];
-            if (!more) break;
-            uint32_t ent[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c)  // (a finished chain reads some byte of the tile and some entry behind its last table)
-                ent[c] = reinterpret_cast<const uint16_t*>(tabs + tb[c])[txt[tile_at(e[c])]];
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if (C > 1 && g[c] >= gend[c]) continue;
-                if ((ent[c] & 0x8000u) != 0) {
-                    const uint8_t* ptail = tabs + tb[c] + 512;
-                    uint32_t k = 1;  // bytes matched so far, right to left
-                    while (k <= H && ptail[H - k] == txt[tile_at(e[c] - k)]) ++k;
-                    bool ok = k == H + 1;
-                    if (in_memory && ok) {  // the rest of the window is not in LDS
-                        const uint8_t* rest = a.text + tile0 + (e[c] - H16) - (m - 1);
-                        if (!parked) {
-                            parked = true;
-                            parked_at = rest;
-                            parked_g = g[c];
-                            ok = false;  // counted after the loop
-                        } else {
-                            ok = global_equal(rest, horm_global(blobs[g[c]]), m - 1 - H);
-                        }
+        // the staged tile, walked once for all patterns (a lane without a window end has e0 == ehi)
+        for (uint32_t e = e0; e < ehi;) {
+            const uint32_t ent = gram[gram_slot(txt[tile_at(e - 1)], txt[tile_at(e)])];  // e >= H16 >= 16: e - 1 is in the halo at least
+            for (uint32_t cand = gram_entry_patterns(ent); cand != 0; cand &= cand - 1) {
+                const uint32_t g = __builtin_ctz(cand);
+                const uint8_t* ptail = tails + g * tslot;
+                uint32_t k = 0;  // bytes matched so far, right to left (the slot promises none of them)
+                while (k <= H && ptail[H - k] == txt[tile_at(e - k)]) ++k;
+                bool ok = k == H + 1;
+                if (in_memory && ok) {  // the rest of the window is not in LDS
+                    const uint8_t* rest = a.text + tile0 + (e - H16) - (m - 1);
+                    if (!parked) {
+                        parked = true;
+                        parked_at = rest;
+                        parked_g = g;
+                        ok = false;  // counted after the loop
+                    } else {
+                        ok = global_equal(rest, horm_global(blobs[g]), m - 1 - H);
                     }
-                    if (ok) atomicAdd(sums + g[c], 1ull);
                 }
-                e[c] += ent[c] & 0x7FFFu;
-                if (e[c] >= ehi) {  // on to the next pattern, no iteration spent
-                    g[c] += 1;
-                    e[c] = e0;
-                    tb[c] += slot;
-                }
+                if (ok) atomicAdd(sums + g, 1ull);
             }
+            e += gram_entry_shift(ent);
         }
         if (in_memory && horm_wave_verify(parked, parked_at, horm_global(blobs[parked_g]), m - 1 - H)) atomicAdd(sums + parked_g, 1ull);
     }
@@ -212,15 +195,15 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
 }
 
 // ---------------------------------------------------------------------------
-// launcher: the grid and the tile's LDS as launch_hor's streaming branch, plus the tables of np patterns
+// launcher: the grid and the tile's LDS as launch_hor's streaming branch, plus the skip table and the tails of np patterns
 // ---------------------------------------------------------------------------
 hipError_t launch_hor_multi(const MultiArgs& a, int num_cus, hipStream_t stream)
 {
-    if (a.np < 1 || a.np > (uint32_t)kMultiMax || a.m < 1 || a.halo > kHaloMax || a.halo > a.m - 1) return hipErrorInvalidValue;
+    if (a.np < 1 || a.np > (uint32_t)kMultiMax || a.m < 3 || a.halo < 1 || a.halo > kHaloMax || a.halo > a.m - 1) return hipErrorInvalidValue;  // (a gram and the byte before a lane's first window end exist)
     const uint32_t m = a.m, H = a.halo;
     const TileRange tr = tiles_for(a.s_begin + m - 1, a.s_end + m - 1, (uint64_t)kHorT * kHorL);
     if (tr.count == 0) return hipSuccess;
-    const size_t lds = kHormHead + (size_t)a.np * (512 + r16(H + 1)) + ((r16(H) + (size_t)kHorT * kHorL + 16 + 63) & ~(size_t)63);  // whole 64-byte blocks: tile_at() permutes inside them
+    const size_t lds = kHormHead + kHormGram + (size_t)a.np * r16(H + 1) + ((r16(H) + (size_t)kHorT * kHorL + 16 + 63) & ~(size_t)63);  // whole 64-byte blocks: tile_at() permutes inside them
     // workgroups per CU as a solo launch of one of these patterns (tile_wgs: they are all sparse); smartgpu_tune(4, .) applies
     ScanArgs one = {};
     one.m = m;
