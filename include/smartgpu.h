@@ -409,7 +409,8 @@ int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char *P, uin
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P == NULL, m = 0 or m > SMARTGPU_XSIZE,
  * k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0.
  * No launch: m > n (count 0), more foreign bytes than k (count 0).
- * NOT offered: set patterns with mismatches, a batch call, insertions and deletions (edit distance), k > 7, byte texts.
+ * NOT offered: a batch call, insertions and deletions (edit distance), k > 7, byte texts.  (Set patterns with mismatches:
+ * smartgpu_psearch_sets_mis64 below.)
  * MEASURED on an MI355X, 1 Gi symbols (profiles/packed/RESULTS.md, "Mismatches"): on rand4, m = 8 .. 256, planes_mis_scan takes
  * 1.22-1.26 / 1.25-1.94 / 1.34-2.11 / 1.55-3.56 x planes_scan's kernel time for k = 0 / 1 / 3 / 7 (per call 1.07-1.17 /
  * 1.07-1.62 / 1.13-1.76 / 1.24-2.76 x), outside the run-to-run spread in every cell.  m = 16: ONE k = 1 call is 14.8 x
@@ -423,6 +424,40 @@ int smartgpu_psearch_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smart
                            uint64_t *count, double *pre_ms, double *run_ms);
 int smartgpu_pfind_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
                          uint64_t *positions, uint8_t *mismatches, uint64_t cap, uint64_t *count);
+/* SET patterns with MISMATCHES on a packed text ("where does the degenerate primer GGNCCWRTATAWAW bind with at most two
+ * mismatches?").  Start position s (off <= s <= off + n - m) is an occurrence when its DISTANCE — the number of j < m for
+ * which the code of T[s+j] is NOT a member of sets[j] — is at most k; sets[j] as in smartgpu_psearch_sets64.  That is the
+ * minimum over the pattern's exact expansions of the Hamming distance: a window may lie within k of several expansions, so
+ * the counts of smartgpu_psearch_mis64 over the expansions overlap and cannot be added.  Nothing in the reference does this.
+ * 0 <= k <= SMARTGPU_PMIS_MAX.  With k = 0 the answers are those of smartgpu_psearch_sets64 / smartgpu_pfind_sets64, with
+ * singleton sets those of smartgpu_psearch_mis64 / smartgpu_pfind_mis64, distances included.  k >= m is legal: every start
+ * position of the range is an occurrence, its distance is still reported.
+ * A position with the FULL set (every value the text holds) is never a mismatch and costs the kernels no instruction.  A
+ * position with the EMPTY set is a mismatch in every window (smartgpu_psearch_sets64 answers 0 for such a pattern; these
+ * calls do NOT): with u such positions, u > k gives count 0 without a launch, otherwise the kernels run with the budget
+ * k - u, do not compare those positions, and u is part of every reported distance.
+ * One pass over the planes whatever the sets and k are (planes_sets_mis_scan, planes_sets_mis_find): smartgpu_psearch_mis64's
+ * bit-sliced counter fed with the complement of the set's membership truth table — a set position costs what an exact
+ * symbol costs there.
+ * The range convention, count width, times, cap / count / SMARTGPU_ERR_NOMEM behaviour (cap == 0 with NULL buffers is a
+ * count), mismatches == NULL and the order of the positions are those of smartgpu_psearch_mis64 / smartgpu_pfind_mis64.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: sets == NULL, k > SMARTGPU_PMIS_MAX, m = 0 or
+ * m > SMARTGPU_XSIZE, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0, and a set with a
+ * bit at or above the text's number of values (bits 4..7 always are; the message names the position).
+ * No launch: m > n (count 0), more empty sets than k (count 0).
+ * NOT offered: a batch call, insertions and deletions (edit distance), k > 7, byte texts.
+ * NOT measured: everything — no timing of these calls has been taken (tools/sets_mis_probe.py takes the three comparisons:
+ * singleton sets against smartgpu_psearch_mis64, k = 0 against smartgpu_psearch_sets64, one find against the finds over
+ * the pattern's exact expansions); the occupancy choices are smartgpu_psearch_mis64's, taken over unmeasured. */
+int smartgpu_psearch_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                                uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_pfind_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                              uint64_t *positions, uint8_t *mismatches, uint64_t cap, uint64_t *count);
+/* No device: the reverse complement of an IUPAC nucleotide pattern — a primer is searched on both strands.  P[0..m): the
+ * letters smartgpu_iupac_sets accepts; out[j] = the complement of P[m-1-j]: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and
+ * N stay; U reads as T (its complement is A; no U is ever written).  Case is preserved.  out has m bytes (no terminator is
+ * written) and may be P itself.  Any other byte: SMARTGPU_ERR_ARG, the message names position and byte, nothing is written. */
+int smartgpu_iupac_revcomp(const char *P, uint32_t m, char *out);
 /* smartgpu_probe_read_ms on the planes: the streaming-read time of the bytes a packed search reads (the plane roofline) */
 int smartgpu_ptext_probe_read_ms(const smartgpu_ptext *t, int reps, double *ms_per_pass);
 

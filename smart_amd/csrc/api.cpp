@@ -2275,6 +2275,74 @@ int check_pmis_args(const char* call, const uint8_t* P, uint32_t m, uint32_t k, 
     return SMARTGPU_OK;
 }
 
+// ---- set patterns with mismatches on packed texts (planes_sets_mis_scan, planes_sets_mis_find) ----
+}  // namespace
+// WEAK references, as launch_planes_sets_* above: a host program that links this file without k_planes.o still links.
+namespace sg {
+__attribute__((weak)) hipError_t launch_planes_sets_mis_scan(const PlaneSetMisArgs& a, int planes, int num_cus, hipStream_t stream);
+__attribute__((weak)) hipError_t launch_planes_sets_mis_find(const PlaneSetMisArgs& a, unsigned long long* out, unsigned long long cap,
+                                                             int planes, int num_cus, hipStream_t stream);
+}  // namespace sg
+namespace {
+bool sets_mis_launchers_linked()
+{
+    if (&sg::launch_planes_sets_mis_scan && &sg::launch_planes_sets_mis_find) return true;
+    set_error("planes_sets_mis_scan / planes_sets_mis_find are not linked into this program");
+    return false;
+}
+
+// The set pattern as membership planes (sets_planes' layout) for the mis kernels: a position that accepts every value of
+// the text AND a position with the empty set get ALL their bits — the first is never a mismatch, the second is one in
+// every window and is counted here, not on the device.  *foreign: the number of empty-set positions.
+// SMARTGPU_ERR_ARG: a set names a code the text does not hold.
+int sets_mis_planes(const smartgpu_ptext* t, const uint8_t* sets, uint32_t m, uint32_t* Y, uint32_t* foreign)
+{
+    const uint32_t all = (1u << t->nvalues) - 1u;
+    std::memset(Y, 0, 4 * kSetWords);
+    *foreign = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        uint32_t s = sets[j];
+        if (s & ~all) {
+            set_error("set pattern: position %u: set 0x%02x names a code >= %d, the number of values the text holds", j, s, t->nvalues);
+            return SMARTGPU_ERR_ARG;
+        }
+        if (s == 0) ++*foreign;
+        if (s == 0 || s == all) s = 0xFu;
+        for (uint32_t c = 0; c < 4; ++c)
+            if (s >> c & 1u) Y[c * sg::kPatWords + (j >> 5)] |= 1u << (j & 31);
+    }
+    return SMARTGPU_OK;
+}
+
+// What the sets-mis kernels receive, n >= m, foreign <= k; the pattern's planes go through the staging buffer into the arena
+// when m > 32 (stage_sets).  The result slot is d->batch_counts[0].
+sg::PlaneSetMisArgs plane_set_mis_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* Y, uint32_t m, uint32_t k,
+                                       uint32_t foreign, uint64_t off, uint64_t n)
+{
+    sg::PlaneSetMisArgs a;
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.s_begin = off;
+    a.s_end = off + n - m + 1;
+    a.m = m;
+    for (uint32_t c = 0; c < 4; ++c) a.y[c] = Y[c * sg::kPatWords];
+    a.budget = k - foreign;
+    a.foreign = foreign;
+    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
+    a.count = d->batch_counts;
+    return a;
+}
+
+// the checks of both sets-mis calls that need no device, in check_pmis_args' order, then the sets; Y: the caller's kSetWords dwords
+int check_psets_mis_args(const char* call, const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                         const uint64_t* count, uint32_t* Y, uint32_t* foreign)
+{
+    if (!sets) { set_error("%s: sets is NULL", call); return SMARTGPU_ERR_ARG; }
+    const int rc = check_pmis_args(call, sets, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    return sets_mis_planes(text, sets, m, Y, foreign);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2633,6 +2701,72 @@ int smartgpu_pfind_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgp
     return SMARTGPU_OK;
 }
 
+/* ---- set patterns with mismatches: at most k positions whose symbol is no member of the position's set ---------------- */
+int smartgpu_psearch_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                                uint64_t* count, double* pre_ms, double* run_ms)
+{
+    uint32_t Y[kSetWords];
+    uint32_t foreign = 0;
+    const int rc = check_psets_mis_args("psearch_sets_mis64", sets, m, k, text, off, n, count, Y, &foreign);
+    if (rc != SMARTGPU_OK) return rc;
+    uint64_t c = 0;
+    double pre = 0.0, run = 0.0;
+    if (foreign <= k && m <= n) {  // otherwise: more empty sets than mismatches allowed, or no window fits: no launch
+        DeviceCtx* d = sets_mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+        if (!d) return SMARTGPU_ERR_HIP;
+        const double t_pre = now_ms();
+        if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
+        if (!stage_sets(d, Y, m)) { set_error("psearch_sets_mis64: %s", hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
+        pre = now_ms() - t_pre;
+        const double t0 = now_ms();
+        const sg::PlaneSetMisArgs a = plane_set_mis_args(d, text, Y, m, k, foreign, off, n);
+        HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(sg::launch_planes_sets_mis_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+        run = now_ms() - t0;
+        // more occurrences than start positions: refused like a poisoned count, never reported
+        if (d->pinned_counts[0] > n - m + 1) { set_error("planes_sets_mis_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
+        c = d->pinned_counts[0];
+    }
+    g_last_pre_ms = pre;
+    g_last_run_ms = run;
+    *count = c;
+    if (pre_ms) *pre_ms = pre;
+    if (run_ms) *run_ms = run;
+    return SMARTGPU_OK;
+}
+
+int smartgpu_pfind_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                              uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
+{
+    if (cap && !positions) { set_error("pfind_sets_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
+    uint32_t Y[kSetWords];
+    uint32_t foreign = 0;
+    const int rc = check_psets_mis_args("pfind_sets_mis64", sets, m, k, text, off, n, count, Y, &foreign);
+    if (rc != SMARTGPU_OK) return rc;
+    if (foreign > k || m > n) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    DeviceCtx* d = sets_mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
+    const sg::PlaneSetMisArgs a = plane_set_mis_args(d, text, Y, m, k, foreign, off, n);
+    const int r = pfind_run(d, "pfind_sets_mis64", "planes_sets_mis_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
+        return stage_sets(d, Y, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+               sg::launch_planes_sets_mis_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
+    }, sg::kMisShift);
+    if (r != SMARTGPU_OK) return r;
+    // the entries are position << kMisShift | distance, in ascending order: unpacked in place
+    for (uint64_t i = 0; i < *count; ++i) {
+        const uint64_t e = positions[i];
+        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << sg::kMisShift) - 1u));
+        positions[i] = e >> sg::kMisShift;
+    }
+    return SMARTGPU_OK;
+}
+
 int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)
 {
     if (!values || (m && (!P || !sets))) { set_error("iupac_sets: NULL argument"); return SMARTGPU_ERR_ARG; }
@@ -2659,6 +2793,35 @@ int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uin
         for (int v = 0; v < nvalues; ++v)
             if (bases_of[(uint8_t)P[j]] & base_of_code[v]) s |= static_cast<uint8_t>(1u << v);
         sets[j] = s;
+    }
+    return SMARTGPU_OK;
+}
+
+int smartgpu_iupac_revcomp(const char* P, uint32_t m, char* out)
+{
+    if (m && (!P || !out)) { set_error("iupac_revcomp: NULL argument"); return SMARTGPU_ERR_ARG; }
+    // the complement of every letter smartgpu_iupac_sets accepts; U reads as T
+    static const char kPairs[][2] = {{'A', 'T'}, {'T', 'A'}, {'U', 'A'}, {'C', 'G'}, {'G', 'C'}, {'R', 'Y'}, {'Y', 'R'}, {'K', 'M'}, {'M', 'K'},
+                                     {'B', 'V'}, {'V', 'B'}, {'D', 'H'}, {'H', 'D'}, {'S', 'S'}, {'W', 'W'}, {'N', 'N'}};
+    char comp[256] = {0};
+    for (const auto& e : kPairs) {
+        comp[(uint8_t)e[0]] = e[1];
+        comp[(uint8_t)(e[0] | 0x20)] = static_cast<char>(e[1] | 0x20);  // case is preserved
+    }
+    for (uint32_t j = 0; j < m; ++j)
+        if (!comp[(uint8_t)P[j]]) {
+            set_error("iupac_revcomp: position %u: byte 0x%02x is no IUPAC nucleotide letter", j, (unsigned)(uint8_t)P[j]);
+            return SMARTGPU_ERR_ARG;
+        }
+    if (out == P) {  // in place: swap the ends
+        for (uint32_t i = 0, j = m; i < j; ++i) {
+            --j;
+            const char lo = comp[(uint8_t)P[i]], hi = comp[(uint8_t)P[j]];
+            out[i] = hi;
+            out[j] = lo;
+        }
+    } else {
+        for (uint32_t j = 0; j < m; ++j) out[j] = comp[(uint8_t)P[m - 1 - j]];
     }
     return SMARTGPU_OK;
 }

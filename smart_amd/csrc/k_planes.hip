@@ -1,6 +1,7 @@
 // k_planes.hip — packed texts: planes_pack (byte text -> bit planes, once per text), planes_scan (the matcher on planes),
 // planes_find (the same matcher with an output stage: positions), planes_sets_scan / planes_sets_find (their siblings for
-// patterns whose positions accept a SET of symbols), planes_mis_scan / planes_mis_find (occurrences with up to k mismatches)
+// patterns whose positions accept a SET of symbols), planes_mis_scan / planes_mis_find (occurrences with up to k mismatches),
+// planes_sets_mis_scan / planes_sets_mis_find (set patterns with up to k mismatches)
 // (one translation unit per kernel family: dev_common.hpp; the layout: planes.hpp)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
@@ -856,6 +857,276 @@ hipError_t launch_planes_mis_find(const PlaneMisArgs& a, unsigned long long* out
         if (bits == 1) SG_MIS_FIND(1, 1); else if (bits == 2) SG_MIS_FIND(1, 2); else SG_MIS_FIND(1, 3);
     }
 #undef SG_MIS_FIND
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// planes_sets_mis_scan<PLANES, BITS>, planes_sets_mis_find<PLANES, BITS>: SET patterns with at most `budget` MISMATCHES —
+// they count / list the start positions s in [s_begin, s_end) whose number of j < m with "the code of T[s + j] is NOT a
+// member of set j" is at most a.budget.  The combination of the two families above: planes_mis_*'s geometry, loads, range
+// masks in S, counter (start value 2^BITS - 1 - budget, sticky S), early leave after every eight positions, output stage
+// (entries pos << kMisShift | distance) and choice of BITS; planes_sets_*'s wave-uniform set per position (bit j of
+// y[0..3]: a scalar switch).  The mismatch table of a set is the complement of its membership table — 0xFF ^ the OR of its
+// members' tables over t0 = 0xCC, t1 = 0xAA — and goes into planes_mis_step as it is: a set position costs what an exact
+// symbol costs there, a position that accepts every code costs nothing.  There is no skip plane: positions the host does
+// not compare (empty sets, a mismatch in every window: counted by the host as `foreign`, the budget lowered by them) arrive
+// as "accepts every code".  An empty set that did arrive would be a mismatch everywhere (table 0xFF; beyond the 32nd
+// position an all-zero membership bit): the kernels are total, the host merely never spends the launch's budget on it.
+// Positions from the 32nd on: planes_sets_mis_verify.
+// Occupancy: planes_mis_*'s choices, taken over UNMEASURED for these kernels — 8 workgroups per CU, except BITS = 3 on two
+// planes, bounded for 128 VGPRs and launched at 7 workgroups per CU (cross-compiled for gfx950 it takes 60 / 62 VGPRs for
+// scan / find, the others 39-56: it would fit eight waves, the bound is kept as its sibling's until it is measured).  Every
+// instantiation has ScratchSize 0 and no static LDS.  planes_scan, planes_find, planes_sets_* and planes_mis_* are not touched.
+// ---------------------------------------------------------------------------
+// the table of "the code (t1 t0) is NOT a member of s" over t0 = 0xCC, t1 = 0xAA
+constexpr uint32_t sets_mis_table(int planes, uint32_t s)
+{
+    return 0xFFu ^ (planes == 2 ? ((s & 1u ? 0x11u : 0u) | (s & 2u ? 0x44u : 0u) | (s & 4u ? 0x22u : 0u) | (s & 8u ? 0x88u : 0u))
+                                : ((s & 1u ? 0x33u : 0u) | (s & 2u ? 0xCCu : 0u)));
+}
+static_assert(sets_mis_table(2, 1) == 0xEE && sets_mis_table(2, 2) == 0xBB && sets_mis_table(2, 4) == 0xDD && sets_mis_table(2, 8) == 0x77 &&
+              sets_mis_table(1, 1) == 0xCC && sets_mis_table(1, 2) == 0x33, "singleton sets: planes_mis_add's tables");
+
+// positions [j0, j1) (j1 <= 32) of the pattern's first block, membership bits y[c]
+template <int PLANES, int BITS>
+static __device__ __forceinline__ void planes_sets_mis_add(uint32_t (&C)[BITS][kChunk], uint32_t (&S)[kChunk], const PlaneWords& t,
+                                                           const uint32_t (&y)[4], uint32_t j0, uint32_t j1)
+{
+    for (uint32_t j = j0; j < j1; ++j) {
+        uint32_t s = ((y[0] >> j) & 1u) | ((y[1] >> j) & 1u) << 1;  // wave-uniform
+        if (PLANES == 2) s |= ((y[2] >> j) & 1u) << 2 | ((y[3] >> j) & 1u) << 3;
+#define SG_SETS_MIS_CASE(s_) case s_: planes_mis_step<PLANES, BITS, sets_mis_table(PLANES, s_)>(C, S, t, j); break;
+        if (PLANES == 2) {
+            switch (s) {
+                SG_SETS_MIS_CASE(0) SG_SETS_MIS_CASE(1) SG_SETS_MIS_CASE(2) SG_SETS_MIS_CASE(3) SG_SETS_MIS_CASE(4) SG_SETS_MIS_CASE(5)
+                SG_SETS_MIS_CASE(6) SG_SETS_MIS_CASE(7) SG_SETS_MIS_CASE(8) SG_SETS_MIS_CASE(9) SG_SETS_MIS_CASE(10) SG_SETS_MIS_CASE(11)
+                SG_SETS_MIS_CASE(12) SG_SETS_MIS_CASE(13) SG_SETS_MIS_CASE(14)
+                default: break;  // every code: no instruction
+            }
+        } else {
+            switch (s) {
+                SG_SETS_MIS_CASE(0) SG_SETS_MIS_CASE(1) SG_SETS_MIS_CASE(2)
+                default: break;
+            }
+        }
+#undef SG_SETS_MIS_CASE
+    }
+}
+
+// planes_mis_verify for sets: the whole wave works on ONE lane's positions within the budget (R, and their counters Cs:
+// wave-uniform).  Lane l takes block k0 + l of the pattern — the membership dwords Y0..Y3[k] (Y0, Y1 on one plane), ~bmask
+// ORed in: positions beyond the pattern's end and lanes beyond the last block accept everything, as the positions the host
+// does not compare do by their all-ones bits — forms the "accepted" dword with planes_sets_verify's multiplexer and
+// popcounts its complement.  The wave sums the lanes' counts (at most 32 each) by six ballots, as planes_mis_verify.
+template <int PLANES, int BITS>
+static __device__ __forceinline__ void planes_sets_mis_verify(uint32_t (&R)[kChunk], uint32_t (&Cs)[BITS][kChunk], const PlaneSetMisArgs& a,
+                                                              uint64_t dw)
+{
+    constexpr uint32_t kMux = 0xCA;  // bitop3(sel, one, zero): sel ? one : zero, bit by bit
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t k0 = 1; 32 * k0 < a.m && (R[0] | R[1] | R[2] | R[3]) != 0; k0 += 64) {
+        const bool valid = 32 * (k0 + lane) < a.m;
+        const uint32_t k = valid ? k0 + lane : k0;
+        const uint32_t left = a.m - 32 * k;
+        const uint32_t bmask = !valid ? 0u : left >= 32 ? ~0u : (1u << left) - 1u;  // the pattern's last block may be partial
+        uint32_t ta[kChunk + 1], tb[kChunk + 1];
+        __builtin_memcpy(ta, a.p0 + dw + k, 4 * (kChunk + 1));
+        if (PLANES == 2) __builtin_memcpy(tb, a.p1 + dw + k, 4 * (kChunk + 1));
+        const uint32_t y0 = a.pat[k] | ~bmask, y1 = a.pat[kPatWords + k] | ~bmask;
+        const uint32_t y2 = PLANES == 2 ? a.pat[2 * kPatWords + k] | ~bmask : 0u;
+        const uint32_t y3 = PLANES == 2 ? a.pat[3 * kPatWords + k] | ~bmask : 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < kChunk; ++w) {
+            uint32_t r = R[w];
+            while (r) {
+                const uint32_t i = __builtin_ctz(r);
+                r &= r - 1;
+                const uint32_t t0 = __builtin_amdgcn_alignbit(ta[w + 1], ta[w], i);
+                uint32_t acc = __builtin_amdgcn_bitop3_b32(t0, y1, y0, kMux);
+                if (PLANES == 2) {
+                    const uint32_t t1 = __builtin_amdgcn_alignbit(tb[w + 1], tb[w], i);
+                    acc = __builtin_amdgcn_bitop3_b32(t1, __builtin_amdgcn_bitop3_b32(t0, y3, y2, kMux), acc, kMux);
+                }
+                const uint32_t cnt = __builtin_popcount(~acc);
+                uint32_t cur = 0;
+#pragma unroll
+                for (int b = 0; b < 6; ++b) cur += (uint32_t)__builtin_popcountll(__ballot((cnt >> b) & 1u)) << b;
+#pragma unroll
+                for (int b = 0; b < BITS; ++b) cur += ((Cs[b][w] >> i) & 1u) << b;
+                if (cur > (1u << BITS) - 1u) {
+                    R[w] &= ~(1u << i);
+                } else {
+#pragma unroll
+                    for (int b = 0; b < BITS; ++b) Cs[b][w] = (Cs[b][w] & ~(1u << i)) | (((cur >> b) & 1u) << i);
+                }
+            }
+        }
+    }
+}
+
+// The loop skeleton is planes_mis_body's: a change to one belongs in the other.  smem: flush_hits' 128 bytes (the scan only).
+template <int PLANES, int BITS, bool FIND>
+static __device__ __forceinline__ void planes_sets_mis_body(const PlaneSetMisArgs& a, uint8_t* smem, unsigned long long* __restrict__ out,
+                                                            unsigned long long cap)
+{
+    constexpr uint64_t kPos = 32 * kChunk;  // start positions per chunk
+    const uint64_t c_end = (a.s_end + kPos - 1) / kPos;
+    const uint64_t stride = (uint64_t)gridDim.x * kPlanesT * kUnroll;
+    const uint32_t f1 = a.m < 32 ? a.m : 32u;
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t start = (1u << BITS) - 1u - a.budget;  // every counter's first value: the carry out of bit BITS - 1 is "over budget"
+    uint32_t hits = 0;
+    // the trip count is the WAVE's (its first chunk decides): every lane stays for the ballots, the verification and the shuffles
+    for (uint64_t cw = a.s_begin / kPos + (uint64_t)blockIdx.x * kPlanesT * kUnroll + 64u * wave; cw < c_end; cw += stride) {
+        PlaneWords t[kUnroll];
+        uint32_t C[kUnroll][BITS][kChunk], S[kUnroll][kChunk];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint64_t c = cw + (uint64_t)u * kPlanesT + lane;
+            const bool in = c < c_end;
+            const uint64_t dw = in ? c * kChunk : 0;
+            const uint4 va = ld_stream16(reinterpret_cast<const uint8_t*>(a.p0 + dw));
+            t[u].a[0] = va.x; t[u].a[1] = va.y; t[u].a[2] = va.z; t[u].a[3] = va.w;
+            t[u].a[4] = a.p0[dw + kChunk];
+            if (PLANES == 2) {
+                const uint4 vb = ld_stream16(reinterpret_cast<const uint8_t*>(a.p1 + dw));
+                t[u].b[0] = vb.x; t[u].b[1] = vb.y; t[u].b[2] = vb.z; t[u].b[3] = vb.w;
+                t[u].b[4] = a.p1[dw + kChunk];
+            }
+            const bool inner = c * kPos >= a.s_begin && (c + 1) * kPos <= a.s_end;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) {
+                S[u][w] = !in ? ~0u : inner ? 0u : ~range_mask(c * kPos + 32 * w, a.s_begin, a.s_end);
+#pragma unroll
+                for (int b = 0; b < BITS; ++b) C[u][b][w] = (start >> b) & 1u ? ~0u : 0u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint32_t live = ~(S[u][0] & S[u][1] & S[u][2] & S[u][3]);
+            for (uint32_t j0 = 0; j0 < f1; j0 += 8) {
+                planes_sets_mis_add<PLANES, BITS>(C[u], S[u], t[u], a.y, j0, j0 + 8 < f1 ? j0 + 8 : f1);
+                live = ~(S[u][0] & S[u][1] & S[u][2] & S[u][3]);
+                if (!__any(live != 0)) break;
+            }
+            if (a.m > 32) {  // a lane has positions within the budget after 32 pattern positions
+                unsigned long long todo = __ballot(live != 0);
+                while (todo) {
+                    const int src = __builtin_ctzll(todo);  // wave-uniform
+                    todo &= todo - 1;
+                    const uint64_t dw = (cw + (uint64_t)u * kPlanesT + (uint32_t)src) * kChunk;
+                    uint32_t R[kChunk], Cs[BITS][kChunk];
+#pragma unroll
+                    for (uint32_t w = 0; w < kChunk; ++w) {
+                        R[w] = ~__builtin_amdgcn_readlane(S[u][w], src);
+#pragma unroll
+                        for (int b = 0; b < BITS; ++b) Cs[b][w] = __builtin_amdgcn_readlane(C[u][b][w], src);
+                    }
+                    planes_sets_mis_verify<PLANES, BITS>(R, Cs, a, dw);
+                    if (lane == (uint32_t)src) {
+#pragma unroll
+                        for (uint32_t w = 0; w < kChunk; ++w) {
+                            S[u][w] = ~R[w];
+#pragma unroll
+                            for (int b = 0; b < BITS; ++b) C[u][b][w] = Cs[b][w];
+                        }
+                    }
+                }
+                live = ~(S[u][0] & S[u][1] & S[u][2] & S[u][3]);
+            }
+            uint32_t mine = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kChunk; ++w) mine += __builtin_popcount(~S[u][w]);
+            if constexpr (!FIND) {
+                hits += mine;
+            } else {
+                if (!__any(live != 0)) continue;
+                // planes_find's output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
+                uint32_t incl = mine;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = __shfl_up(incl, d, 64);
+                    if (lane >= (uint32_t)d) incl += up;
+                }
+                const uint32_t total = __shfl(incl, 63, 64);
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
+                base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+                       __builtin_amdgcn_readfirstlane((uint32_t)base);
+                unsigned long long slot = base + (incl - mine);
+                const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
+                const uint32_t bias = a.foreign - start;  // distance = counter - start + the positions the host counted
+#pragma unroll
+                for (uint32_t w = 0; w < kChunk; ++w) {
+                    uint32_t r = ~S[u][w];
+                    while (r) {
+                        const uint32_t i = __builtin_ctz(r);
+                        r &= r - 1;
+                        uint32_t dist = bias;
+#pragma unroll
+                        for (int b = 0; b < BITS; ++b) dist += ((C[u][b][w] >> i) & 1u) << b;
+                        if (slot < cap) out[slot] = (pos + 32 * w + i) << kMisShift | dist;
+                        ++slot;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (!FIND) flush_hits(hits, a.count, smem, reinterpret_cast<const uint8_t*>(a.p0));
+}
+
+template <int PLANES, int BITS>
+__global__ __launch_bounds__(kPlanesT, (kMisWaves<PLANES, BITS>)) void planes_sets_mis_scan(PlaneSetMisArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // 128 bytes: flush_hits
+    planes_sets_mis_body<PLANES, BITS, false>(a, smem, nullptr, 0);
+}
+
+template <int PLANES, int BITS>
+__global__ __launch_bounds__(kPlanesT, (kMisWaves<PLANES, BITS>)) void planes_sets_mis_find(PlaneSetMisArgs a, unsigned long long* __restrict__ out, unsigned long long cap)
+{
+    planes_sets_mis_body<PLANES, BITS, true>(a, nullptr, out, cap);
+}
+
+// Grid and BITS: launch_planes_mis_scan's.
+static uint32_t planes_sets_mis_grid(const PlaneSetMisArgs& a, int planes, int num_cus, int bits)
+{
+    constexpr uint64_t kPos = 32 * kChunk;
+    const uint64_t chunks = (a.s_end + kPos - 1) / kPos - a.s_begin / kPos;
+    const uint64_t want = (chunks + kPlanesT * kUnroll - 1) / (kPlanesT * kUnroll);
+    return (uint32_t)std::min<uint64_t>(want, (uint64_t)num_cus * mis_wgs(planes, bits));
+}
+
+hipError_t launch_planes_sets_mis_scan(const PlaneSetMisArgs& a, int planes, int num_cus, hipStream_t stream)
+{
+    if (a.budget > SMARTGPU_PMIS_MAX) return hipErrorInvalidValue;
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    const int bits = a.budget <= 1 ? 1 : a.budget <= 3 ? 2 : 3;
+    const uint32_t grid = planes_sets_mis_grid(a, planes, num_cus, bits);
+#define SG_SETS_MIS_SCAN(p_, b_) hipLaunchKernelGGL((planes_sets_mis_scan<p_, b_>), dim3(grid), dim3(kPlanesT), 128, stream, a)
+    if (planes == 2) {
+        if (bits == 1) SG_SETS_MIS_SCAN(2, 1); else if (bits == 2) SG_SETS_MIS_SCAN(2, 2); else SG_SETS_MIS_SCAN(2, 3);
+    } else {
+        if (bits == 1) SG_SETS_MIS_SCAN(1, 1); else if (bits == 2) SG_SETS_MIS_SCAN(1, 2); else SG_SETS_MIS_SCAN(1, 3);
+    }
+#undef SG_SETS_MIS_SCAN
+    return hipGetLastError();
+}
+
+hipError_t launch_planes_sets_mis_find(const PlaneSetMisArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                                       hipStream_t stream)
+{
+    if (a.budget > SMARTGPU_PMIS_MAX) return hipErrorInvalidValue;
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    const int bits = a.budget <= 1 ? 1 : a.budget <= 3 ? 2 : 3;
+    const uint32_t grid = planes_sets_mis_grid(a, planes, num_cus, bits);
+#define SG_SETS_MIS_FIND(p_, b_) hipLaunchKernelGGL((planes_sets_mis_find<p_, b_>), dim3(grid), dim3(kPlanesT), 0, stream, a, out, cap)
+    if (planes == 2) {
+        if (bits == 1) SG_SETS_MIS_FIND(2, 1); else if (bits == 2) SG_SETS_MIS_FIND(2, 2); else SG_SETS_MIS_FIND(2, 3);
+    } else {
+        if (bits == 1) SG_SETS_MIS_FIND(1, 1); else if (bits == 2) SG_SETS_MIS_FIND(1, 2); else SG_SETS_MIS_FIND(1, 3);
+    }
+#undef SG_SETS_MIS_FIND
     return hipGetLastError();
 }
 

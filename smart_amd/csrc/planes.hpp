@@ -92,4 +92,25 @@ hipError_t launch_planes_mis_scan(const PlaneMisArgs& a, int planes, int num_cus
 hipError_t launch_planes_mis_find(const PlaneMisArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
                                   hipStream_t stream);
 
+// SET patterns with MISMATCHES: occurrences with at most `budget` positions j where the code of T[s + j] is not a member of
+// set j.  What planes_sets_mis_scan and planes_sets_mis_find receive (by value): PlaneSetArgs with PlaneMisArgs' budget and
+// foreign.  There is no skip plane: a position that is not compared (an empty set: a mismatch in every window, counted by the
+// host, which lowers the budget by their number and passes it as `foreign`) has ALL its bits set, as a position that accepts
+// every value of the text has — neither costs an instruction nor is counted on the device.
+struct PlaneSetMisArgs {
+    const uint32_t* p0;         // as PlaneArgs
+    const uint32_t* p1;
+    uint64_t s_begin, s_end;
+    uint32_t m;
+    uint32_t y[4];              // as PlaneSetArgs
+    uint32_t budget;            // non-members allowed at the compared positions, <= SMARTGPU_PMIS_MAX
+    uint32_t foreign;           // added to every distance the find reports (budget + foreign <= SMARTGPU_PMIS_MAX)
+    const uint32_t* pat;        // device, m > 32 only: u32 Y0..Y3[kPatWords]
+    unsigned long long* count;  // device result slot (pre-zeroed)
+};
+// Grid, occupancy, range convention and the find's entries: those of launch_planes_mis_scan / launch_planes_mis_find.
+hipError_t launch_planes_sets_mis_scan(const PlaneSetMisArgs& a, int planes, int num_cus, hipStream_t stream);
+hipError_t launch_planes_sets_mis_find(const PlaneSetMisArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
+                                       hipStream_t stream);
+
 }  // namespace sg

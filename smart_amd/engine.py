@@ -128,6 +128,9 @@ def _load(path):
         "smartgpu_iupac_sets": (i32, [vp, i32, vp, u32, vp]),
         "smartgpu_psearch_mis64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_psearch_sets_mis64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_pfind_sets_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
     }
     for a in ALGOS:
         sig["smartgpu_%s_search" % a] = (i32, [vp, i32, vp, i32])
@@ -585,6 +588,51 @@ def pfind_mis(P, ptext, k, off=0, n=None, cap=1 << 20):
     if rc != 0:
         raise _err("pfind_mis64 rc=%d" % rc)
     return out[:c.value].copy(), mis[:c.value].copy(), int(c.value)
+
+
+def psearch_sets_mis(sets, ptext, k, off=0, n=None):
+    """(count, pre_ms, run_ms) of the start positions in symbols [off, off+n) of a PackedText where a SET pattern
+    (psearch_sets) occurs with at most k mismatches — positions whose symbol is no member of the position's set; 0 <= k <= 7
+    (smartgpu_psearch_sets_mis64).  A position with the empty set is a mismatch in every window."""
+    sets = _u8(sets)
+    if n is None:
+        n = len(ptext) - off
+    c = C.c_uint64(0)
+    pre = C.c_double(0.0)
+    run = C.c_double(0.0)
+    rc = lib().smartgpu_psearch_sets_mis64(sets.ctypes.data, len(sets), k, ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
+    if rc != 0:
+        raise _err("psearch_sets_mis64 rc=%d" % rc)
+    return int(c.value), float(pre.value), float(run.value)
+
+
+def pfind_sets_mis(sets, ptext, k, off=0, n=None, cap=1 << 20):
+    """(positions, mismatches, count) of a SET pattern with at most k mismatches (psearch_sets_mis) in symbols [off, off+n)
+    of a PackedText, as pfind_mis returns them; (None, None, count) when there are more than `cap`."""
+    sets = _u8(sets)
+    if n is None:
+        n = len(ptext) - off
+    out = np.empty(max(cap, 1), dtype=np.uint64)
+    mis = np.empty(max(cap, 1), dtype=np.uint8)
+    c = C.c_uint64(0)
+    rc = lib().smartgpu_pfind_sets_mis64(sets.ctypes.data, len(sets), k, ptext._h, off, n, out.ctypes.data if cap else None,
+                                         mis.ctypes.data if cap else None, cap, C.byref(c))
+    if rc == -5 and c.value > cap:
+        return None, None, int(c.value)
+    if rc != 0:
+        raise _err("pfind_sets_mis64 rc=%d" % rc)
+    return out[:c.value].copy(), mis[:c.value].copy(), int(c.value)
+
+
+def iupac_revcomp(pattern):
+    """The reverse complement of an IUPAC nucleotide pattern (the letters iupac_sets accepts, case preserved, U read as T):
+    str for a str, bytes otherwise (smartgpu_iupac_revcomp).  No device needed."""
+    is_str = isinstance(pattern, str)
+    P = _u8(pattern.encode() if is_str else pattern)
+    out = np.zeros(len(P), dtype=np.uint8)
+    if lib().smartgpu_iupac_revcomp(P.ctypes.data, len(P), out.ctypes.data) != 0:
+        raise _err("iupac_revcomp")
+    return out.tobytes().decode() if is_str else out.tobytes()
 
 
 def iupac_sets(pattern, values):

@@ -29,6 +29,7 @@ KERNEL_UNIT = {
     "planes_pack": "k_planes", "planes_scan": "k_planes", "planes_find": "k_planes",
     "planes_sets_scan": "k_planes", "planes_sets_find": "k_planes",
     "planes_mis_scan": "k_planes", "planes_mis_find": "k_planes",
+    "planes_sets_mis_scan": "k_planes", "planes_sets_mis_find": "k_planes",
 }
 
 
