@@ -26,6 +26,7 @@
 #include "kernels.hpp"
 #include "multi.hpp"
 #include "planes.hpp"
+#include "planes_host.hpp"
 #include "route.hpp"
 #include "tables.hpp"
 
@@ -1893,24 +1894,6 @@ struct smartgpu_ptext {
 
 namespace {
 
-// The pattern as planes: X[0][w], X[1][w] = bits 0 / 1 of the codes of symbols 32 w .. 32 w + 31.  false: a pattern byte
-// the text does not hold (no occurrence).
-bool pattern_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint32_t* X0, uint32_t* X1)
-{
-    int code_of[256];
-    for (int c = 0; c < 256; ++c) code_of[c] = -1;
-    for (int k = 0; k < t->nvalues; ++k) code_of[t->values[k]] = k;
-    std::memset(X0, 0, 4 * sg::kPatWords);
-    std::memset(X1, 0, 4 * sg::kPatWords);
-    for (uint32_t j = 0; j < m; ++j) {
-        const int c = code_of[P[j]];
-        if (c < 0) return false;
-        X0[j >> 5] |= static_cast<uint32_t>(c & 1) << (j & 31);
-        X1[j >> 5] |= static_cast<uint32_t>(c >> 1) << (j & 31);
-    }
-    return true;
-}
-
 int check_psearch_args(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n)
 {
     if (!P || m < 1 || m > SMARTGPU_XSIZE) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return SMARTGPU_ERR_ARG; }
@@ -1919,20 +1902,29 @@ int check_psearch_args(const uint8_t* P, uint32_t m, const smartgpu_ptext* text,
     return SMARTGPU_OK;
 }
 
-// What the kernels receive for pattern k of a set staged at host_pat (pattern_planes) and, for m > 32, in the device's arena;
-// n >= m.  The result slot is d->batch_counts[k].
-sg::PlaneArgs plane_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* host_pat, uint32_t k, uint32_t m, uint64_t off, uint64_t n)
+// The head every packed kernel's arguments share (PlaneArgs, PlaneSetArgs, PlaneMisArgs, PlaneSetMisArgs), n >= m: the planes,
+// the start positions, the pattern's planes in the device's arena (read when m > 32 only) and result slot d->batch_counts[k].
+template <typename Args>
+void plane_head(Args& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint64_t off, uint64_t n, uint32_t k = 0)
 {
-    sg::PlaneArgs a;
     a.p0 = text->plane(0);
     a.p1 = text->plane(text->planes - 1);
     a.s_begin = off;
     a.s_end = off + n - m + 1;
     a.m = m;
+    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
+    a.count = d->batch_counts + k;
+}
+
+// What the kernels receive for pattern k of a set staged at host_pat (encode_pattern, 2 * kPatWords dwords per pattern)
+// and, for m > 32, at the same stride in the device's arena.
+sg::PlaneArgs plane_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* host_pat, uint32_t k, uint32_t m, uint64_t off, uint64_t n)
+{
+    sg::PlaneArgs a;
+    plane_head(a, d, text, m, off, n, k);
     a.x0 = host_pat[2 * sg::kPatWords * k];
     a.x1 = host_pat[2 * sg::kPatWords * k + sg::kPatWords];
-    a.pat = reinterpret_cast<const uint32_t*>(d->arena) + 2 * sg::kPatWords * k;
-    a.count = d->batch_counts + k;
+    a.pat += 2 * sg::kPatWords * k;
     return a;
 }
 
@@ -1952,7 +1944,8 @@ int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu
     std::vector<uint8_t> present(K, 0);
     for (uint32_t k = 0; k < K; ++k) {
         if (!P[k]) { set_error("pattern %u is NULL", k); return SMARTGPU_ERR_ARG; }
-        present[k] = pattern_planes(text, P[k], m, host_pat + 2 * sg::kPatWords * k, host_pat + 2 * sg::kPatWords * k + sg::kPatWords);
+        uint32_t* X = host_pat + 2 * sg::kPatWords * k;
+        present[k] = sg::encode_pattern(text->values, text->nvalues, P[k], m, X, X + sg::kPatWords, nullptr) == 0;
     }
     const bool fits = n >= m;  // m > n: no window fits, count 0
     if (m > 32 && fits)
@@ -2016,77 +2009,74 @@ bool copy_positions(DeviceCtx* d, uint64_t* dst, const unsigned long long* src, 
     return true;
 }
 
-// planes_find's output in ascending order.  It is a sequence of spans (planes.hpp): each ascending and contiguous, each the
-// survivors of its own kFindSpan start positions counted from the range's first chunk, in the order the waves reserved them.
-// So the spans are found in one pass (the span number changes), ordered by it — one entry per span, not per position;
-// s_last is the last start position of the range — and moved only when they are out of order.  All `have` entries must be present (count <= cap).
-// shift: the entries hold their position above `shift` low bits (planes_mis_find: the distance) and are ordered whole.
-// false: the entries are not such spans (refused by the callers, never reported).
-bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t s_last, uint32_t shift = 0)
+// ---- one host path for the count and the find calls on packed texts (set patterns, mismatches, both: planes.hpp) ----
+
+// The pattern's planes (`bytes` at `words`) through the staging buffer into the device's arena, for m > 32 only: the first
+// 32 positions travel as kernel arguments.
+bool stage_pattern(DeviceCtx* d, const uint32_t* words, size_t bytes, uint32_t m)
 {
-    static_assert((sg::kFindSpan & (sg::kFindSpan - 1)) == 0, "span number by division");
-    const uint64_t base = s_begin / 128 * 128;
-    struct Span { uint64_t key, begin, len; };
-    std::vector<Span> spans;
-    bool ascending = true;
-    for (uint64_t i = 0; i < have; ++i) {
-        const uint64_t key = ((pos[i] >> shift) - base) / sg::kFindSpan;
-        if (!spans.empty() && spans.back().key == key) {
-            if (pos[i] <= pos[i - 1]) return false;  // not what planes_find writes (a retuned kernel whose spans are no longer these?)
-            ++spans.back().len;
-            continue;
-        }
-        if (!spans.empty() && key < spans.back().key) ascending = false;
-        spans.push_back({key, i, 1});
-    }
-    if (ascending) return true;
-    std::vector<uint64_t> tmp(have);
-    uint64_t at = 0;
-    const uint64_t nkeys = (s_last - base) / sg::kFindSpan + 1;
-    if (nkeys <= 16 * spans.size() + 4096) {
-        // many short spans (a pattern that occurs in every tenth span: a sort of 130,000 keys took most of the call): the
-        // span numbers are unique and bounded, so a table indexed by them orders the spans in one pass
-        constexpr uint64_t kNone = ~0ull;
-        std::vector<uint64_t> by_key(nkeys, kNone);
-        for (size_t i = 0; i < spans.size(); ++i) {
-            if (spans[i].key >= nkeys || by_key[spans[i].key] != kNone) return false;  // outside the range, or a span in two pieces
-            by_key[spans[i].key] = i;
-        }
-        for (uint64_t k = 0; k < nkeys; ++k) {
-            if (by_key[k] == kNone) continue;
-            const Span& sp = spans[by_key[k]];
-            std::memcpy(&tmp[at], pos + sp.begin, sp.len * sizeof(uint64_t));
-            at += sp.len;
-        }
-    } else {
-        std::sort(spans.begin(), spans.end(), [](const Span& x, const Span& y) { return x.key < y.key; });
-        for (size_t i = 1; i < spans.size(); ++i)
-            if (spans[i].key == spans[i - 1].key) return false;  // a span in two pieces
-        for (const Span& sp : spans) {
-            std::memcpy(&tmp[at], pos + sp.begin, sp.len * sizeof(uint64_t));
-            at += sp.len;
-        }
-    }
-    std::memcpy(pos, tmp.data(), have * sizeof(uint64_t));
-    return true;
+    if (m <= 32) return true;
+    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
+    std::memcpy(d->pinned, words, bytes);
+    return hipMemcpyAsync(d->arena, d->pinned, bytes, hipMemcpyHostToDevice, d->stream) == hipSuccess;
 }
 
-// One find on a packed text, n >= m: the device buffer, `launch(out, room)` — the pattern's staging, the cursor's memset
-// and the kernel, all on the device's stream —, the cursor's read-back, the positions to the host in ascending order.
+// What a count call answers: the times for smartgpu_last_times, the count and the times for the caller.
+int pcount_done(uint64_t c, double pre, double run, uint64_t* count, double* pre_ms, double* run_ms)
+{
+    g_last_pre_ms = pre;
+    g_last_run_ms = run;
+    if (count) *count = c;
+    if (pre_ms) *pre_ms = pre;
+    if (run_ms) *run_ms = run;
+    return SMARTGPU_OK;
+}
+
+// One count on a packed text, n >= m: `a` holds the kind's own fields, `words` the pattern's planes.  pre: the device's
+// buffers and the staging; run: the slot's memset, the kernel, the read-back.
+template <typename Args>
+int pcount_run(const char* call, const char* kernel, hipError_t (*launch)(const Args&, int, int, hipStream_t), Args a, const smartgpu_ptext* text,
+               const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
+{
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const double t_pre = now_ms();
+    if (!batch_reserve(d, bytes, 1)) return SMARTGPU_ERR_NOMEM;
+    if (!stage_pattern(d, words, bytes, m)) { set_error("%s: %s", call, hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
+    const double pre = now_ms() - t_pre;
+    const double t0 = now_ms();
+    plane_head(a, d, text, m, off, n);
+    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(launch(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+    const double run = now_ms() - t0;
+    // more occurrences than start positions: refused like a poisoned count, never reported
+    if (d->pinned_counts[0] > n - m + 1) { set_error("%s: count %llu exceeds the %llu start positions", kernel, (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
+    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
+}
+
+// One find on a packed text, n >= m, on a device whose arena has room for the pattern (batch_reserve): the positions'
+// device buffer, the pattern's staging, the cursor's memset and the kernel — `a` holds the kind's own fields —, the
+// cursor's read-back, the positions to the host in ascending order.
 // *count always receives the number of occurrences when the device answered; the return codes are smartgpu_pfind64's.
 // shift: order_spans' (the entries reach `positions` as the kernel wrote them).
-template <typename Launch>
-int pfind_run(DeviceCtx* d, const char* call, const char* kernel, uint32_t m, uint64_t off, uint64_t n, uint64_t* positions,
-              uint64_t cap, uint64_t* count, unsigned long long* cursor, Launch launch, uint32_t shift = 0)
+template <typename Args>
+int pfind_run(DeviceCtx* d, const char* call, const char* kernel,
+              hipError_t (*launch)(const Args&, unsigned long long*, unsigned long long, int, int, hipStream_t), Args a, const smartgpu_ptext* text,
+              const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* positions, uint64_t cap, uint64_t* count,
+              uint32_t shift = 0)
 {
+    plane_head(a, d, text, m, off, n);
     const uint64_t starts = n - m + 1;
     const uint64_t room = cap < starts ? cap : starts;  // no more positions than start positions
     bool own = false;
     unsigned long long* out = nullptr;
     uint64_t room_got = room;
     if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
-    bool ok = launch(out, room_got) &&
-              hipMemcpyAsync(d->pinned_counts, cursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+    bool ok = stage_pattern(d, words, bytes, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+              launch(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
+              hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
               hipStreamSynchronize(d->stream) == hipSuccess;
     const unsigned long long total = ok ? d->pinned_counts[0] : 0;
     int r = SMARTGPU_OK;
@@ -2100,7 +2090,7 @@ int pfind_run(DeviceCtx* d, const char* call, const char* kernel, uint32_t m, ui
         if (!copy_positions(d, positions, out, total)) {
             set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
             r = SMARTGPU_ERR_HIP;
-        } else if (!order_spans(positions, total, off, off + n - m, shift)) {
+        } else if (!sg::order_spans(positions, total, off, off + n - m, shift)) {
             set_error("%s: the positions are not ascending spans of %llu start positions", kernel, (unsigned long long)sg::kFindSpan);
             r = SMARTGPU_ERR_HIP;
         }
@@ -2116,158 +2106,21 @@ int pfind_run(DeviceCtx* d, const char* call, const char* kernel, uint32_t m, ui
     return SMARTGPU_OK;
 }
 
-// ---- set patterns on packed texts (planes_sets_scan, planes_sets_find) ----
-}  // namespace
-// WEAK references: a host program that links this file without k_planes.o and stands in for the launchers itself (the
-// dispatch test's driver, which knows the launchers this file had when it was written) still links.  In the library both
-// are defined (k_planes.hip); an undefined one is an error of the call (sets_launchers_linked), never another path.
-namespace sg {
-__attribute__((weak)) hipError_t launch_planes_sets_scan(const PlaneSetArgs& a, int planes, int num_cus, hipStream_t stream);
-__attribute__((weak)) hipError_t launch_planes_sets_find(const PlaneSetArgs& a, unsigned long long* out, unsigned long long cap, int planes,
-                                                         int num_cus, hipStream_t stream);
-}  // namespace sg
-namespace {
-bool sets_launchers_linked()
+// The entries of a find with mismatches, position << kMisShift | distance in ascending order, unpacked in place.
+void unpack_mis(uint64_t* positions, uint8_t* mismatches, uint64_t count)
 {
-    if (&sg::launch_planes_sets_scan && &sg::launch_planes_sets_find) return true;
-    set_error("planes_sets_scan / planes_sets_find are not linked into this program");
-    return false;
-}
-
-constexpr size_t kSetWords = 4 * sg::kPatWords;  // a set pattern's four membership planes
-
-// The set pattern as membership planes: bit j % 32 of Y[c * kPatWords + j / 32] = position j accepts code c.  A position
-// that accepts every value of the text gets ALL its bits (planes.hpp: no instruction).  SMARTGPU_ERR_ARG: a set names a
-// code the text does not hold.  *empty: some position accepts nothing; *full: every position accepts everything.
-int sets_planes(const smartgpu_ptext* t, const uint8_t* sets, uint32_t m, uint32_t* Y, bool* empty, bool* full)
-{
-    const uint32_t all = (1u << t->nvalues) - 1u;
-    std::memset(Y, 0, 4 * kSetWords);
-    *empty = false;
-    *full = true;
-    for (uint32_t j = 0; j < m; ++j) {
-        uint32_t s = sets[j];
-        if (s & ~all) {
-            set_error("set pattern: position %u: set 0x%02x names a code >= %d, the number of values the text holds", j, s, t->nvalues);
-            return SMARTGPU_ERR_ARG;
-        }
-        if (s == 0) *empty = true;
-        if (s == all) s = 0xFu; else *full = false;
-        for (uint32_t c = 0; c < 4; ++c)
-            if (s >> c & 1u) Y[c * sg::kPatWords + (j >> 5)] |= 1u << (j & 31);
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint64_t e = positions[i];
+        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << sg::kMisShift) - 1u));
+        positions[i] = e >> sg::kMisShift;
     }
-    return SMARTGPU_OK;
 }
 
-// What the sets kernels receive, n >= m; the pattern's planes go through the staging buffer into the arena when m > 32
-// (stage_sets).  The result slot is d->batch_counts[0].
-sg::PlaneSetArgs plane_set_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* Y, uint32_t m, uint64_t off, uint64_t n)
+// The checks of the set, mis and sets-mis calls that need no device; `what` names the pattern argument, k = 0 without mismatches.
+int check_pext_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off,
+                    uint64_t n, const uint64_t* count)
 {
-    sg::PlaneSetArgs a;
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.s_begin = off;
-    a.s_end = off + n - m + 1;
-    a.m = m;
-    for (uint32_t c = 0; c < 4; ++c) a.y[c] = Y[c * sg::kPatWords];
-    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
-    a.count = d->batch_counts;
-    return a;
-}
-
-bool stage_sets(DeviceCtx* d, const uint32_t* Y, uint32_t m)
-{
-    if (m <= 32) return true;  // the first 32 positions travel as kernel arguments
-    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
-    std::memcpy(d->pinned, Y, 4 * kSetWords);
-    return hipMemcpyAsync(d->arena, d->pinned, 4 * kSetWords, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
-
-// the checks of both set calls that need no device; Y: the caller's kSetWords dwords
-int check_psets_args(const char* call, const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                     const uint64_t* count, uint32_t* Y, bool* empty, bool* full)
-{
-    if (!sets) { set_error("%s: sets is NULL", call); return SMARTGPU_ERR_ARG; }
-    const int rc = check_psearch_args(sets, m, text, off, n);
-    if (rc != SMARTGPU_OK) return rc;
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return sets_planes(text, sets, m, Y, empty, full);
-}
-
-// ---- mismatches on packed texts (planes_mis_scan, planes_mis_find) ----
-}  // namespace
-// WEAK references, as launch_planes_sets_* above: a host program that links this file without k_planes.o still links.
-namespace sg {
-__attribute__((weak)) hipError_t launch_planes_mis_scan(const PlaneMisArgs& a, int planes, int num_cus, hipStream_t stream);
-__attribute__((weak)) hipError_t launch_planes_mis_find(const PlaneMisArgs& a, unsigned long long* out, unsigned long long cap, int planes,
-                                                        int num_cus, hipStream_t stream);
-}  // namespace sg
-namespace {
-bool mis_launchers_linked()
-{
-    if (&sg::launch_planes_mis_scan && &sg::launch_planes_mis_find) return true;
-    set_error("planes_mis_scan / planes_mis_find are not linked into this program");
-    return false;
-}
-
-constexpr size_t kMisWords = 3 * sg::kPatWords;  // a pattern's two code planes and its skip plane
-
-// The pattern as planes X0, X1 (pattern_planes) and SKIP: bit j % 32 of X[2 * kPatWords + j / 32] = P[j] is a byte the text
-// does not hold (its code bits are zero).  Returns the number of such positions.
-uint32_t mis_pattern_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint32_t* X)
-{
-    int code_of[256];
-    for (int c = 0; c < 256; ++c) code_of[c] = -1;
-    for (int k = 0; k < t->nvalues; ++k) code_of[t->values[k]] = k;
-    std::memset(X, 0, 4 * kMisWords);
-    uint32_t foreign = 0;
-    for (uint32_t j = 0; j < m; ++j) {
-        const int c = code_of[P[j]];
-        if (c < 0) {
-            X[2 * sg::kPatWords + (j >> 5)] |= 1u << (j & 31);
-            ++foreign;
-            continue;
-        }
-        X[j >> 5] |= static_cast<uint32_t>(c & 1) << (j & 31);
-        X[sg::kPatWords + (j >> 5)] |= static_cast<uint32_t>(c >> 1) << (j & 31);
-    }
-    return foreign;
-}
-
-// What the mis kernels receive, n >= m, foreign <= k; the pattern's planes go through the staging buffer into the arena
-// when m > 32 (stage_mis).  The result slot is d->batch_counts[0].
-sg::PlaneMisArgs plane_mis_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* X, uint32_t m, uint32_t k, uint32_t foreign,
-                                uint64_t off, uint64_t n)
-{
-    sg::PlaneMisArgs a;
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.s_begin = off;
-    a.s_end = off + n - m + 1;
-    a.m = m;
-    a.x0 = X[0];
-    a.x1 = X[sg::kPatWords];
-    a.skip = X[2 * sg::kPatWords];
-    a.budget = k - foreign;
-    a.foreign = foreign;
-    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
-    a.count = d->batch_counts;
-    return a;
-}
-
-bool stage_mis(DeviceCtx* d, const uint32_t* X, uint32_t m)
-{
-    if (m <= 32) return true;  // the first 32 positions travel as kernel arguments
-    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
-    std::memcpy(d->pinned, X, 4 * kMisWords);
-    return hipMemcpyAsync(d->arena, d->pinned, 4 * kMisWords, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
-
-// the checks of both mis calls that need no device
-int check_pmis_args(const char* call, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                    const uint64_t* count)
-{
-    if (!P) { set_error("%s: P is NULL", call); return SMARTGPU_ERR_ARG; }
+    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
     if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u mismatches, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
     const int rc = check_psearch_args(P, m, text, off, n);
     if (rc != SMARTGPU_OK) return rc;
@@ -2275,72 +2128,32 @@ int check_pmis_args(const char* call, const uint8_t* P, uint32_t m, uint32_t k, 
     return SMARTGPU_OK;
 }
 
-// ---- set patterns with mismatches on packed texts (planes_sets_mis_scan, planes_sets_mis_find) ----
-}  // namespace
-// WEAK references, as launch_planes_sets_* above: a host program that links this file without k_planes.o still links.
-namespace sg {
-__attribute__((weak)) hipError_t launch_planes_sets_mis_scan(const PlaneSetMisArgs& a, int planes, int num_cus, hipStream_t stream);
-__attribute__((weak)) hipError_t launch_planes_sets_mis_find(const PlaneSetMisArgs& a, unsigned long long* out, unsigned long long cap,
-                                                             int planes, int num_cus, hipStream_t stream);
-}  // namespace sg
-namespace {
-bool sets_mis_launchers_linked()
+// encode_sets for a checked call.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
+int sets_planes(const smartgpu_ptext* t, const uint8_t* sets, uint32_t m, bool fill_empty, uint32_t* Y, uint32_t* empty, bool* full)
 {
-    if (&sg::launch_planes_sets_mis_scan && &sg::launch_planes_sets_mis_find) return true;
-    set_error("planes_sets_mis_scan / planes_sets_mis_find are not linked into this program");
-    return false;
+    const int bad = sg::encode_sets(t->nvalues, sets, m, fill_empty, Y, empty, full);
+    if (bad < 0) return SMARTGPU_OK;
+    set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, sets[bad], t->nvalues);
+    return SMARTGPU_ERR_ARG;
 }
 
-// The set pattern as membership planes (sets_planes' layout) for the mis kernels: a position that accepts every value of
-// the text AND a position with the empty set get ALL their bits — the first is never a mismatch, the second is one in
-// every window and is counted here, not on the device.  *foreign: the number of empty-set positions.
-// SMARTGPU_ERR_ARG: a set names a code the text does not hold.
-int sets_mis_planes(const smartgpu_ptext* t, const uint8_t* sets, uint32_t m, uint32_t* Y, uint32_t* foreign)
+// a.y of PlaneSetArgs and PlaneSetMisArgs: the first dword of each membership plane
+template <typename Args>
+void set_words(Args& a, const uint32_t* Y)
 {
-    const uint32_t all = (1u << t->nvalues) - 1u;
-    std::memset(Y, 0, 4 * kSetWords);
-    *foreign = 0;
-    for (uint32_t j = 0; j < m; ++j) {
-        uint32_t s = sets[j];
-        if (s & ~all) {
-            set_error("set pattern: position %u: set 0x%02x names a code >= %d, the number of values the text holds", j, s, t->nvalues);
-            return SMARTGPU_ERR_ARG;
-        }
-        if (s == 0) ++*foreign;
-        if (s == 0 || s == all) s = 0xFu;
-        for (uint32_t c = 0; c < 4; ++c)
-            if (s >> c & 1u) Y[c * sg::kPatWords + (j >> 5)] |= 1u << (j & 31);
-    }
-    return SMARTGPU_OK;
-}
-
-// What the sets-mis kernels receive, n >= m, foreign <= k; the pattern's planes go through the staging buffer into the arena
-// when m > 32 (stage_sets).  The result slot is d->batch_counts[0].
-sg::PlaneSetMisArgs plane_set_mis_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* Y, uint32_t m, uint32_t k,
-                                       uint32_t foreign, uint64_t off, uint64_t n)
-{
-    sg::PlaneSetMisArgs a;
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.s_begin = off;
-    a.s_end = off + n - m + 1;
-    a.m = m;
     for (uint32_t c = 0; c < 4; ++c) a.y[c] = Y[c * sg::kPatWords];
-    a.budget = k - foreign;
-    a.foreign = foreign;
-    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
-    a.count = d->batch_counts;
-    return a;
 }
 
-// the checks of both sets-mis calls that need no device, in check_pmis_args' order, then the sets; Y: the caller's kSetWords dwords
-int check_psets_mis_args(const char* call, const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                         const uint64_t* count, uint32_t* Y, uint32_t* foreign)
+constexpr size_t kMisWords = 3 * sg::kPatWords;  // a pattern's two code planes and its skip plane
+
+// The pattern as X0, X1, SKIP in X[kMisWords] and a.x0, a.x1, a.skip.  Returns the number of foreign positions.
+uint32_t mis_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint32_t* X, sg::PlaneMisArgs* a)
 {
-    if (!sets) { set_error("%s: sets is NULL", call); return SMARTGPU_ERR_ARG; }
-    const int rc = check_pmis_args(call, sets, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    return sets_mis_planes(text, sets, m, Y, foreign);
+    const uint32_t foreign = sg::encode_pattern(t->values, t->nvalues, P, m, X, X + sg::kPatWords, X + 2 * sg::kPatWords);
+    a->x0 = X[0];
+    a->x1 = X[sg::kPatWords];
+    a->skip = X[2 * sg::kPatWords];
+    return foreign;
 }
 
 }  // namespace
@@ -2468,12 +2281,7 @@ int smartgpu_psearch64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text,
     double pre = 0.0, run = 0.0;
     const int r = psearch_impl(set, m, 1, text, off, n, &c, &pre, &run);
     if (r != SMARTGPU_OK) return r;
-    g_last_pre_ms = pre;
-    g_last_run_ms = run;
-    if (count) *count = c;
-    if (pre_ms) *pre_ms = pre;
-    if (run_ms) *run_ms = run;
-    return SMARTGPU_OK;
+    return pcount_done(c, pre, run, count, pre_ms, run_ms);
 }
 
 int smartgpu_psearch_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
@@ -2500,20 +2308,16 @@ int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, u
     if (!count || (cap && !positions)) { set_error("pfind64: count must not be NULL, positions only with cap = 0"); return SMARTGPU_ERR_ARG; }
     DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
-    constexpr size_t kPatBytes = 2 * 4 * sg::kPatWords;
-    if (!batch_reserve(d, kPatBytes, 1)) return SMARTGPU_ERR_NOMEM;
-    uint32_t* host_pat = reinterpret_cast<uint32_t*>(d->pinned);  // (free: every call that fills it ends with a synchronisation)
-    const bool present = pattern_planes(text, P, m, host_pat, host_pat + sg::kPatWords);
-    if (!present || m > n) {  // a byte the text does not hold, or no window fits: no launch
-        *count = 0;
+    uint32_t X[2 * sg::kPatWords];
+    if (!batch_reserve(d, sizeof X, 1)) return SMARTGPU_ERR_NOMEM;
+    if (sg::encode_pattern(text->values, text->nvalues, P, m, X, X + sg::kPatWords, nullptr) || m > n) {
+        *count = 0;  // a byte the text does not hold, or no window fits: no launch
         return SMARTGPU_OK;
     }
-    const sg::PlaneArgs a = plane_args(d, text, host_pat, 0, m, off, n);
-    return pfind_run(d, "pfind64", "planes_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
-        return (m <= 32 || hipMemcpyAsync(d->arena, host_pat, kPatBytes, hipMemcpyHostToDevice, d->stream) == hipSuccess) &&
-               hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-               sg::launch_planes_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
-    });
+    sg::PlaneArgs a;
+    a.x0 = X[0];
+    a.x1 = X[sg::kPatWords];
+    return pfind_run(d, "pfind64", "planes_find", sg::launch_planes_find, a, text, X, sizeof X, m, off, n, positions, cap, count);
 }
 
 int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
@@ -2557,7 +2361,7 @@ int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, cons
         if (d->pinned_counts[k] != counts[k]) {  // the two passes disagree: refused, never reported
             set_error("planes_find: pattern %u: cursor %llu, planes_scan counted %llu", k, d->pinned_counts[k], (unsigned long long)counts[k]);
             r = SMARTGPU_ERR_HIP;
-        } else if (!order_spans(positions + starts[k], counts[k], off, off + n - m)) {
+        } else if (!sg::order_spans(positions + starts[k], counts[k], off, off + n - m)) {
             set_error("planes_find: pattern %u: the positions are not ascending spans of %llu start positions", k, (unsigned long long)sg::kFindSpan);
             r = SMARTGPU_ERR_HIP;
         }
@@ -2570,50 +2374,27 @@ int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, cons
 int smartgpu_psearch_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                             uint64_t* count, double* pre_ms, double* run_ms)
 {
-    uint32_t Y[kSetWords];
-    bool empty = false, full = false;
-    const int rc = check_psets_args("psearch_sets64", sets, m, text, off, n, count, Y, &empty, &full);
+    int rc = check_pext_args("psearch_sets64", "sets", sets, m, 0, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
-    uint64_t c = 0;
-    double pre = 0.0, run = 0.0;
-    if (empty || m > n) {
-        c = 0;  // a position that accepts nothing, or no window fits: no launch
-    } else if (full) {
-        c = n - m + 1;  // every start position of the range: no launch
-    } else {
-        DeviceCtx* d = sets_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
-        if (!d) return SMARTGPU_ERR_HIP;
-        const double t_pre = now_ms();
-        if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
-        if (!stage_sets(d, Y, m)) { set_error("psearch_sets64: %s", hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
-        pre = now_ms() - t_pre;
-        const double t0 = now_ms();
-        const sg::PlaneSetArgs a = plane_set_args(d, text, Y, m, off, n);
-        HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(sg::launch_planes_sets_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-        run = now_ms() - t0;
-        // more occurrences than start positions: refused like a poisoned count, never reported
-        if (d->pinned_counts[0] > n - m + 1) { set_error("planes_sets_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
-        c = d->pinned_counts[0];
-    }
-    g_last_pre_ms = pre;
-    g_last_run_ms = run;
-    *count = c;
-    if (pre_ms) *pre_ms = pre;
-    if (run_ms) *run_ms = run;
-    return SMARTGPU_OK;
+    uint32_t Y[sg::kSetWords], empty = 0;
+    bool full = false;
+    if ((rc = sets_planes(text, sets, m, false, Y, &empty, &full)) != SMARTGPU_OK) return rc;
+    if (empty || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // a position that accepts nothing, or no window fits: no launch
+    if (full) return pcount_done(n - m + 1, 0.0, 0.0, count, pre_ms, run_ms);    // every start position of the range: no launch
+    sg::PlaneSetArgs a;
+    set_words(a, Y);
+    return pcount_run("psearch_sets64", "planes_sets_scan", sg::launch_planes_sets_scan, a, text, Y, sizeof Y, m, off, n, count, pre_ms, run_ms);
 }
 
 int smartgpu_pfind_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                           uint64_t* positions, uint64_t cap, uint64_t* count)
 {
     if (cap && !positions) { set_error("pfind_sets64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
-    uint32_t Y[kSetWords];
-    bool empty = false, full = false;
-    const int rc = check_psets_args("pfind_sets64", sets, m, text, off, n, count, Y, &empty, &full);
+    int rc = check_pext_args("pfind_sets64", "sets", sets, m, 0, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
+    uint32_t Y[sg::kSetWords], empty = 0;
+    bool full = false;
+    if ((rc = sets_planes(text, sets, m, false, Y, &empty, &full)) != SMARTGPU_OK) return rc;
     if (empty || m > n) {
         *count = 0;
         return SMARTGPU_OK;
@@ -2625,146 +2406,92 @@ int smartgpu_pfind_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext*
         for (uint64_t i = 0; i < total; ++i) positions[i] = off + i;
         return SMARTGPU_OK;
     }
-    DeviceCtx* d = sets_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
-    const sg::PlaneSetArgs a = plane_set_args(d, text, Y, m, off, n);
-    return pfind_run(d, "pfind_sets64", "planes_sets_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
-        return stage_sets(d, Y, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-               sg::launch_planes_sets_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
-    });
+    if (!batch_reserve(d, sizeof Y, 1)) return SMARTGPU_ERR_NOMEM;
+    sg::PlaneSetArgs a;
+    set_words(a, Y);
+    return pfind_run(d, "pfind_sets64", "planes_sets_find", sg::launch_planes_sets_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count);
 }
 
 /* ---- mismatches: occurrences within Hamming distance k ---------------------------------------------------------------- */
 int smartgpu_psearch_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                            uint64_t* count, double* pre_ms, double* run_ms)
 {
-    const int rc = check_pmis_args("psearch_mis64", P, m, k, text, off, n, count);
+    const int rc = check_pext_args("psearch_mis64", "P", P, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     uint32_t X[kMisWords];
-    const uint32_t foreign = mis_pattern_planes(text, P, m, X);
-    uint64_t c = 0;
-    double pre = 0.0, run = 0.0;
-    if (foreign <= k && m <= n) {  // otherwise: more foreign bytes than mismatches allowed, or no window fits: no launch
-        DeviceCtx* d = mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
-        if (!d) return SMARTGPU_ERR_HIP;
-        const double t_pre = now_ms();
-        if (!batch_reserve(d, 4 * kMisWords, 1)) return SMARTGPU_ERR_NOMEM;
-        if (!stage_mis(d, X, m)) { set_error("psearch_mis64: %s", hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
-        pre = now_ms() - t_pre;
-        const double t0 = now_ms();
-        const sg::PlaneMisArgs a = plane_mis_args(d, text, X, m, k, foreign, off, n);
-        HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(sg::launch_planes_mis_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-        run = now_ms() - t0;
-        // more occurrences than start positions: refused like a poisoned count, never reported
-        if (d->pinned_counts[0] > n - m + 1) { set_error("planes_mis_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
-        c = d->pinned_counts[0];
-    }
-    g_last_pre_ms = pre;
-    g_last_run_ms = run;
-    *count = c;
-    if (pre_ms) *pre_ms = pre;
-    if (run_ms) *run_ms = run;
-    return SMARTGPU_OK;
+    sg::PlaneMisArgs a;
+    a.foreign = mis_planes(text, P, m, X, &a);
+    // more foreign bytes than mismatches allowed, or no window fits: no launch
+    if (a.foreign > k || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);
+    a.budget = k - a.foreign;
+    return pcount_run("psearch_mis64", "planes_mis_scan", sg::launch_planes_mis_scan, a, text, X, sizeof X, m, off, n, count, pre_ms, run_ms);
 }
 
 int smartgpu_pfind_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                          uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
 {
     if (cap && !positions) { set_error("pfind_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
-    const int rc = check_pmis_args("pfind_mis64", P, m, k, text, off, n, count);
+    const int rc = check_pext_args("pfind_mis64", "P", P, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     uint32_t X[kMisWords];
-    const uint32_t foreign = mis_pattern_planes(text, P, m, X);
-    if (foreign > k || m > n) {
+    sg::PlaneMisArgs a;
+    a.foreign = mis_planes(text, P, m, X, &a);
+    if (a.foreign > k || m > n) {
         *count = 0;
         return SMARTGPU_OK;
     }
-    DeviceCtx* d = mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+    a.budget = k - a.foreign;
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, 4 * kMisWords, 1)) return SMARTGPU_ERR_NOMEM;
-    const sg::PlaneMisArgs a = plane_mis_args(d, text, X, m, k, foreign, off, n);
-    const int r = pfind_run(d, "pfind_mis64", "planes_mis_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
-        return stage_mis(d, X, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-               sg::launch_planes_mis_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
-    }, sg::kMisShift);
-    if (r != SMARTGPU_OK) return r;
-    // the entries are position << kMisShift | distance, in ascending order: unpacked in place
-    for (uint64_t i = 0; i < *count; ++i) {
-        const uint64_t e = positions[i];
-        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << sg::kMisShift) - 1u));
-        positions[i] = e >> sg::kMisShift;
-    }
-    return SMARTGPU_OK;
+    if (!batch_reserve(d, sizeof X, 1)) return SMARTGPU_ERR_NOMEM;
+    const int r = pfind_run(d, "pfind_mis64", "planes_mis_find", sg::launch_planes_mis_find, a, text, X, sizeof X, m, off, n, positions, cap, count,
+                            sg::kMisShift);
+    if (r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
+    return r;
 }
 
 /* ---- set patterns with mismatches: at most k positions whose symbol is no member of the position's set ---------------- */
 int smartgpu_psearch_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                                 uint64_t* count, double* pre_ms, double* run_ms)
 {
-    uint32_t Y[kSetWords];
-    uint32_t foreign = 0;
-    const int rc = check_psets_mis_args("psearch_sets_mis64", sets, m, k, text, off, n, count, Y, &foreign);
+    int rc = check_pext_args("psearch_sets_mis64", "sets", sets, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
-    uint64_t c = 0;
-    double pre = 0.0, run = 0.0;
-    if (foreign <= k && m <= n) {  // otherwise: more empty sets than mismatches allowed, or no window fits: no launch
-        DeviceCtx* d = sets_mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
-        if (!d) return SMARTGPU_ERR_HIP;
-        const double t_pre = now_ms();
-        if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
-        if (!stage_sets(d, Y, m)) { set_error("psearch_sets_mis64: %s", hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
-        pre = now_ms() - t_pre;
-        const double t0 = now_ms();
-        const sg::PlaneSetMisArgs a = plane_set_mis_args(d, text, Y, m, k, foreign, off, n);
-        HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(sg::launch_planes_sets_mis_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-        HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-        run = now_ms() - t0;
-        // more occurrences than start positions: refused like a poisoned count, never reported
-        if (d->pinned_counts[0] > n - m + 1) { set_error("planes_sets_mis_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
-        c = d->pinned_counts[0];
-    }
-    g_last_pre_ms = pre;
-    g_last_run_ms = run;
-    *count = c;
-    if (pre_ms) *pre_ms = pre;
-    if (run_ms) *run_ms = run;
-    return SMARTGPU_OK;
+    uint32_t Y[sg::kSetWords];
+    bool full = false;
+    sg::PlaneSetMisArgs a;
+    if ((rc = sets_planes(text, sets, m, true, Y, &a.foreign, &full)) != SMARTGPU_OK) return rc;
+    // more empty sets than mismatches allowed, or no window fits: no launch
+    if (a.foreign > k || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);
+    a.budget = k - a.foreign;
+    set_words(a, Y);
+    return pcount_run("psearch_sets_mis64", "planes_sets_mis_scan", sg::launch_planes_sets_mis_scan, a, text, Y, sizeof Y, m, off, n, count, pre_ms, run_ms);
 }
 
 int smartgpu_pfind_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                               uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
 {
     if (cap && !positions) { set_error("pfind_sets_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
-    uint32_t Y[kSetWords];
-    uint32_t foreign = 0;
-    const int rc = check_psets_mis_args("pfind_sets_mis64", sets, m, k, text, off, n, count, Y, &foreign);
+    int rc = check_pext_args("pfind_sets_mis64", "sets", sets, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
-    if (foreign > k || m > n) {
+    uint32_t Y[sg::kSetWords];
+    bool full = false;
+    sg::PlaneSetMisArgs a;
+    if ((rc = sets_planes(text, sets, m, true, Y, &a.foreign, &full)) != SMARTGPU_OK) return rc;
+    if (a.foreign > k || m > n) {
         *count = 0;
         return SMARTGPU_OK;
     }
-    DeviceCtx* d = sets_mis_launchers_linked() ? device_ctx_flushed(text->device) : nullptr;
+    a.budget = k - a.foreign;
+    set_words(a, Y);
+    DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, 4 * kSetWords, 1)) return SMARTGPU_ERR_NOMEM;
-    const sg::PlaneSetMisArgs a = plane_set_mis_args(d, text, Y, m, k, foreign, off, n);
-    const int r = pfind_run(d, "pfind_sets_mis64", "planes_sets_mis_find", m, off, n, positions, cap, count, a.count, [&](unsigned long long* out, uint64_t room) {
-        return stage_sets(d, Y, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-               sg::launch_planes_sets_mis_find(a, out, room, text->planes, d->num_cus, d->stream) == hipSuccess;
-    }, sg::kMisShift);
-    if (r != SMARTGPU_OK) return r;
-    // the entries are position << kMisShift | distance, in ascending order: unpacked in place
-    for (uint64_t i = 0; i < *count; ++i) {
-        const uint64_t e = positions[i];
-        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << sg::kMisShift) - 1u));
-        positions[i] = e >> sg::kMisShift;
-    }
-    return SMARTGPU_OK;
+    if (!batch_reserve(d, sizeof Y, 1)) return SMARTGPU_ERR_NOMEM;
+    const int r = pfind_run(d, "pfind_sets_mis64", "planes_sets_mis_find", sg::launch_planes_sets_mis_find, a, text, Y, sizeof Y, m, off, n, positions,
+                            cap, count, sg::kMisShift);
+    if (r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
+    return r;
 }
 
 int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)

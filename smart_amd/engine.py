@@ -460,18 +460,41 @@ def search(algo, P, text, off=0, n=None):
     return int(c.value), float(pre.value), float(run.value)
 
 
-def psearch(P, ptext, off=0, n=None):
-    """(count, pre_ms, run_ms) of P in symbols [off, off+n) of a PackedText: the count by definition (bf.c:25-39)."""
-    P = _u8(P)
+def _pcount(name, pat, ptext, off, n, *k):
+    """(count, pre_ms, run_ms) of the packed count call smartgpu_<name>: `pat` the pattern or its sets, k the mismatches
+    where the call takes them."""
+    pat = _u8(pat)
     if n is None:
         n = len(ptext) - off
     c = C.c_uint64(0)
     pre = C.c_double(0.0)
     run = C.c_double(0.0)
-    rc = lib().smartgpu_psearch64(P.ctypes.data, len(P), ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, len(pat), *k, ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
     if rc != 0:
-        raise _err("psearch64 rc=%d" % rc)
+        raise _err("%s rc=%d" % (name, rc))
     return int(c.value), float(pre.value), float(run.value)
+
+
+def _pfind(name, pat, ptext, off, n, cap, *k):
+    """(positions[, mismatches], count) of the packed find call smartgpu_<name>; the distances where the call takes k.
+    More than `cap` occurrences (SMARTGPU_ERR_NOMEM with the count filled): None in place of the arrays."""
+    pat = _u8(pat)
+    if n is None:
+        n = len(ptext) - off
+    outs = [np.empty(max(cap, 1), dtype=dt) for dt in ((np.uint64, np.uint8) if k else (np.uint64,))]
+    c = C.c_uint64(0)
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, len(pat), *k, ptext._h, off, n,
+                                            *[o.ctypes.data if cap else None for o in outs], cap, C.byref(c))
+    if rc == -5 and c.value > cap:
+        return (None,) * len(outs) + (int(c.value),)
+    if rc != 0:
+        raise _err("%s rc=%d" % (name, rc))
+    return tuple(o[:c.value].copy() for o in outs) + (int(c.value),)
+
+
+def psearch(P, ptext, off=0, n=None):
+    """(count, pre_ms, run_ms) of P in symbols [off, off+n) of a PackedText: the count by definition (bf.c:25-39)."""
+    return _pcount("psearch64", P, ptext, off, n)
 
 
 def psearch_batch(patterns, ptext, off=0, n=None):
@@ -492,17 +515,7 @@ def pfind(P, ptext, off=0, n=None, cap=1 << 20):
     """(positions, count): the ascending start positions (relative to symbol 0) of P in symbols [off, off+n) of a
     PackedText, and their number — find() on a packed text.  When there are more than `cap`, positions is None and only
     the count is returned (smartgpu_pfind64 reports SMARTGPU_ERR_NOMEM; retry with cap >= count)."""
-    P = _u8(P)
-    if n is None:
-        n = len(ptext) - off
-    out = np.empty(max(cap, 1), dtype=np.uint64)
-    c = C.c_uint64(0)
-    rc = lib().smartgpu_pfind64(P.ctypes.data, len(P), ptext._h, off, n, out.ctypes.data if cap else None, cap, C.byref(c))
-    if rc == -5 and c.value > cap:
-        return None, int(c.value)
-    if rc != 0:
-        raise _err("pfind64 rc=%d" % rc)
-    return out[:c.value].copy(), int(c.value)
+    return _pfind("pfind64", P, ptext, off, n, cap)
 
 
 def pfind_batch(patterns, ptext, off=0, n=None, cap=1 << 20):
@@ -527,101 +540,40 @@ def pfind_batch(patterns, ptext, off=0, n=None, cap=1 << 20):
 def psearch_sets(sets, ptext, off=0, n=None):
     """(count, pre_ms, run_ms) of a SET pattern in symbols [off, off+n) of a PackedText: sets[j] is a byte whose bit c says
     that position j accepts the symbol ptext.symbols()[c] (smartgpu_psearch_sets64; PackedText.iupac builds such sets)."""
-    sets = _u8(sets)
-    if n is None:
-        n = len(ptext) - off
-    c = C.c_uint64(0)
-    pre = C.c_double(0.0)
-    run = C.c_double(0.0)
-    rc = lib().smartgpu_psearch_sets64(sets.ctypes.data, len(sets), ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
-    if rc != 0:
-        raise _err("psearch_sets64 rc=%d" % rc)
-    return int(c.value), float(pre.value), float(run.value)
+    return _pcount("psearch_sets64", sets, ptext, off, n)
 
 
 def pfind_sets(sets, ptext, off=0, n=None, cap=1 << 20):
     """(positions, count) of a SET pattern (psearch_sets) in symbols [off, off+n) of a PackedText, as pfind returns them:
     ascending, relative to symbol 0; positions is None when there are more than `cap`."""
-    sets = _u8(sets)
-    if n is None:
-        n = len(ptext) - off
-    out = np.empty(max(cap, 1), dtype=np.uint64)
-    c = C.c_uint64(0)
-    rc = lib().smartgpu_pfind_sets64(sets.ctypes.data, len(sets), ptext._h, off, n, out.ctypes.data if cap else None, cap, C.byref(c))
-    if rc == -5 and c.value > cap:
-        return None, int(c.value)
-    if rc != 0:
-        raise _err("pfind_sets64 rc=%d" % rc)
-    return out[:c.value].copy(), int(c.value)
+    return _pfind("pfind_sets64", sets, ptext, off, n, cap)
 
 
 def psearch_mis(P, ptext, k, off=0, n=None):
     """(count, pre_ms, run_ms) of the start positions in symbols [off, off+n) of a PackedText where P occurs with at most k
     mismatches (Hamming distance over bytes; 0 <= k <= 7; smartgpu_psearch_mis64).  A byte of P the text does not
     hold is a mismatch in every window."""
-    P = _u8(P)
-    if n is None:
-        n = len(ptext) - off
-    c = C.c_uint64(0)
-    pre = C.c_double(0.0)
-    run = C.c_double(0.0)
-    rc = lib().smartgpu_psearch_mis64(P.ctypes.data, len(P), k, ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
-    if rc != 0:
-        raise _err("psearch_mis64 rc=%d" % rc)
-    return int(c.value), float(pre.value), float(run.value)
+    return _pcount("psearch_mis64", P, ptext, off, n, k)
 
 
 def pfind_mis(P, ptext, k, off=0, n=None, cap=1 << 20):
     """(positions, mismatches, count) of P with at most k mismatches (psearch_mis) in symbols [off, off+n) of a PackedText:
     the ascending start positions (uint64, relative to symbol 0), the distance of each (uint8) and their number;
     (None, None, count) when there are more than `cap`."""
-    P = _u8(P)
-    if n is None:
-        n = len(ptext) - off
-    out = np.empty(max(cap, 1), dtype=np.uint64)
-    mis = np.empty(max(cap, 1), dtype=np.uint8)
-    c = C.c_uint64(0)
-    rc = lib().smartgpu_pfind_mis64(P.ctypes.data, len(P), k, ptext._h, off, n, out.ctypes.data if cap else None,
-                                    mis.ctypes.data if cap else None, cap, C.byref(c))
-    if rc == -5 and c.value > cap:
-        return None, None, int(c.value)
-    if rc != 0:
-        raise _err("pfind_mis64 rc=%d" % rc)
-    return out[:c.value].copy(), mis[:c.value].copy(), int(c.value)
+    return _pfind("pfind_mis64", P, ptext, off, n, cap, k)
 
 
 def psearch_sets_mis(sets, ptext, k, off=0, n=None):
     """(count, pre_ms, run_ms) of the start positions in symbols [off, off+n) of a PackedText where a SET pattern
     (psearch_sets) occurs with at most k mismatches — positions whose symbol is no member of the position's set; 0 <= k <= 7
     (smartgpu_psearch_sets_mis64).  A position with the empty set is a mismatch in every window."""
-    sets = _u8(sets)
-    if n is None:
-        n = len(ptext) - off
-    c = C.c_uint64(0)
-    pre = C.c_double(0.0)
-    run = C.c_double(0.0)
-    rc = lib().smartgpu_psearch_sets_mis64(sets.ctypes.data, len(sets), k, ptext._h, off, n, C.byref(c), C.byref(pre), C.byref(run))
-    if rc != 0:
-        raise _err("psearch_sets_mis64 rc=%d" % rc)
-    return int(c.value), float(pre.value), float(run.value)
+    return _pcount("psearch_sets_mis64", sets, ptext, off, n, k)
 
 
 def pfind_sets_mis(sets, ptext, k, off=0, n=None, cap=1 << 20):
     """(positions, mismatches, count) of a SET pattern with at most k mismatches (psearch_sets_mis) in symbols [off, off+n)
     of a PackedText, as pfind_mis returns them; (None, None, count) when there are more than `cap`."""
-    sets = _u8(sets)
-    if n is None:
-        n = len(ptext) - off
-    out = np.empty(max(cap, 1), dtype=np.uint64)
-    mis = np.empty(max(cap, 1), dtype=np.uint8)
-    c = C.c_uint64(0)
-    rc = lib().smartgpu_pfind_sets_mis64(sets.ctypes.data, len(sets), k, ptext._h, off, n, out.ctypes.data if cap else None,
-                                         mis.ctypes.data if cap else None, cap, C.byref(c))
-    if rc == -5 and c.value > cap:
-        return None, None, int(c.value)
-    if rc != 0:
-        raise _err("pfind_sets_mis64 rc=%d" % rc)
-    return out[:c.value].copy(), mis[:c.value].copy(), int(c.value)
+    return _pfind("pfind_sets_mis64", sets, ptext, off, n, cap, k)
 
 
 def iupac_revcomp(pattern):

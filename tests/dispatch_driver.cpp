@@ -65,6 +65,12 @@ hipError_t launch_probe_read(const uint8_t*, uint64_t, unsigned long long*, int,
 hipError_t launch_planes_pack(const uint8_t*, uint64_t, uint32_t*, uint32_t*, int, const uint8_t[3], hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_planes_scan(const PlaneArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_planes_find(const PlaneArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_planes_sets_scan(const PlaneSetArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_planes_sets_find(const PlaneSetArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_planes_mis_scan(const PlaneMisArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_planes_mis_find(const PlaneMisArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_planes_sets_mis_scan(const PlaneSetMisArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_planes_sets_mis_find(const PlaneSetMisArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
 
 }  // namespace sg
 
