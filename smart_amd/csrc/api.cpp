@@ -169,6 +169,7 @@ struct smartgpu_plan {
     uint32_t m = 0;
     sg::PlanWords words;  // see build_blob
     uint8_t* blob = nullptr;               // device: pattern + tables
+    uint8_t tail[sg::kTailRow] = {};       // host: the pattern's end as a shared pass takes it by value (multi.hpp)
     unsigned long long* results = nullptr; // device: kResultSlots counters (library-owned)
     unsigned long long* ext_results = nullptr; // caller-owned device buffer, if set
     int ext_slots = 0;
@@ -662,7 +663,8 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // entry point that waits for, times, orders work on, or frees what is on the device's stream sends what is pending
 // first (flush_queue), in arrival order; a launch that is alone by then goes through launch_scan as it always did.
 // The queue holds device pointers of plans and texts: smartgpu_plan_free, _plan_set_result_buffer and _text_free flush.
-struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; };
+// The plan's tail row is copied, not pointed to.
+struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; uint8_t tail[sg::kTailRow]; };
 struct QueuedKey {
     sg::ScanArgs key;  // text, s_begin, s_end, m, halo
     uint32_t n = 0;
@@ -679,7 +681,7 @@ struct LaunchQueue {
     uint64_t launches = 0, passes = 0;  // eligible launches seen / kernels sent for them
 };
 LaunchQueue g_queue[kMaxDevices];
-// launches per pass: 0 = off.  8, the most a pass takes, is a choice: the sweep over 2 / 4 / 8 has not been run (profiles/coalesce/RESULTS.md)
+// launches per pass: 0 = off.  8, the most a pass takes: per pattern, 0.080 / 0.040 / 0.0207 ms in groups of 2 / 4 / 8 (profiles/coalesce/RESULTS.md)
 std::atomic<int> g_coalesce{8};
 
 // send one key's launches (q.mu held, the device current)
@@ -699,6 +701,7 @@ hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
         for (uint32_t j = 0; j < k.n; ++j) {
             ma.blob[j] = k.scans[j].a.blob;
             ma.count[j] = k.scans[j].a.count;
+            std::memcpy(ma.tail[j], k.scans[j].tail, sg::kTailRow);
         }
         e = sg::g_hor_multi(ma, d->num_cus, d->stream);
     }
@@ -749,7 +752,7 @@ DeviceCtx* device_ctx_flushed(int device)
 
 // Queue the launch if it is one that can share a pass.  *queued = false: the caller launches it (after flush_queue).
 hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words, const sg::ScanArgs& a, const sg::TextCodes& codes,
-                        bool timed, bool* queued)
+                        const uint8_t (&tail)[sg::kTailRow], bool timed, bool* queued)
 {
     *queued = false;
     if (a.s_end <= a.s_begin || !words.sparse) return hipSuccess;
@@ -776,7 +779,11 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
         q.keys[at].n = 0;
     }
     QueuedKey& k = q.keys[at];
-    k.scans[k.n++] = QueuedScan{algo, a, codes};
+    QueuedScan& qs = k.scans[k.n++];
+    qs.algo = algo;
+    qs.a = a;
+    qs.codes = codes;
+    std::memcpy(qs.tail, tail, sg::kTailRow);
     if (k.n >= static_cast<uint32_t>(G)) {  // (G <= kMultiMax, the room a key has)
         const hipError_t e = send_key(d, q, k);
         if (e != hipSuccess && err == hipSuccess) err = e;
@@ -946,6 +953,7 @@ smartgpu_plan* smartgpu_plan_create(int algo, const uint8_t* P, uint32_t m, int 
     p->m = m;
     std::vector<uint8_t> blob;
     p->words = build_blob(blob, algo, P, m);
+    sg::tail_fill(p->tail, P, m);
     bool ok = hipMalloc(reinterpret_cast<void**>(&p->blob), blob.size()) == hipSuccess &&
               hipMalloc(reinterpret_cast<void**>(&p->results), sizeof(unsigned long long) * sg::kResultSlots) == hipSuccess;
     if (ok) {
@@ -991,7 +999,7 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
     if (!d) return SMARTGPU_ERR_HIP;
     const sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(slot), text, off, n);
     bool queued = false;
-    HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), timed != 0, &queued), return SMARTGPU_ERR_HIP);
+    HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), p->tail, timed != 0, &queued), return SMARTGPU_ERR_HIP);
     if (queued) { p->timed[slot] = false; return SMARTGPU_OK; }
     HIP_TRY(flush_queue(d), return SMARTGPU_ERR_HIP);  // everything else keeps its place behind what was queued before it
     p->timed[slot] = timed != 0;

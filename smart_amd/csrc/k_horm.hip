@@ -13,15 +13,21 @@ namespace sg {
 // LDS: u64 blob[8] | u64 count[8] | u64 hits[8] | u32 gram[kGramSlots] | np x pattern tail P[m-1-H..m-1] | text [tile0-H16, tile0+TB)
 // The walk: a Horspool walk per pattern asks np times, one pattern at a time, whether a pattern ends near a window end,
 // and np such walks of a staged tile cost more than its fetch.  ONE walk per lane asks it for all patterns at once:
-// the workgroup builds, in its prologue, the skip table of multi.hpp from the pattern bytes in the blobs — indexed by
-// the window's last two bytes, the least shift any pattern of the pass allows and the patterns whose last gram falls
-// into the slot (LDS atomics: min for the shifts, a barrier, or for the pattern bits).  np x (m - 2) grams hardly fill
+// the workgroup builds, in its prologue, the skip table of multi.hpp — indexed by the window's last two bytes, the
+// least shift any pattern of the pass allows and the patterns whose last gram falls into the slot (LDS atomics: min for
+// the shifts, a barrier, or for the pattern bits and the tag of the last gram).  np x (m - 2) grams hardly fill
 // kGramSlots slots, so nearly every step moves the window end by m - 1 and a lane leaves its 64-byte segment after
 // about 64 / (m - 1) steps whatever np is.  A step: two byte reads (tile_at permutes dwords, the two bytes of a gram
-// may lie in different ones), the slot, the entry; compare for every pattern bit; add the shift.
-// The arrays of MultiArgs are indexed with compile-time constants only, once, in the prologue that copies the pointers
-// to LDS (a run-time index into the arguments makes the compiler select between addresses and load through flat_load);
-// a pattern's pointer is read from LDS as a number and cast to GLOBAL memory.  The kernel is as long as hor_scan
+// may lie in different ones), the slot, the entry; compare for every pattern bit, but only where the entry's tag
+// says that the window ends in a pattern's last gram and not merely in its slot; add the shift.
+// The prologue reads no pattern from memory: the bytes the table and the tails are made of, at most 65 per pattern,
+// come BY VALUE in the rows of MultiArgs (multi.hpp), each thread reads its few of them from the arguments first, and
+// the first tile is asked for before the table is built — measured, a pass of eight fell from 167-170 us to 164-165 us
+// against a solo hor_scan's 156 us (1 GiB rand128, m = 32; profiles/coalesce/RESULTS.md); the tag took it to 162-163.
+// The pointer arrays of MultiArgs are indexed with compile-time constants only, once, in the prologue that copies them
+// to LDS (a run-time index into them makes the compiler select between addresses and load through flat_load);
+// a pattern's pointer — needed only to complete a window in memory — is read from LDS as a number and cast to GLOBAL
+// memory.  The kernel is as long as hor_scan
 // whatever NP is, so NP, the most patterns a pass can take, is instantiated once, at kMultiMax, and completion in
 // memory (m - 1 > H) is a run-time branch of that one kernel, taken by rare candidates only: the product library has a
 // size to keep (tests/test_abi.py holds it below 0.7 of the A/B build).
@@ -78,7 +84,7 @@ template <int THREADS, int L, int NP>
 __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t tile_first, uint32_t ntiles)
 {
     constexpr int TB = THREADS * L;
-    static_assert(NP <= kMultiMax && NP <= 16, "a pattern bit per pattern in an entry's high half");
+    static_assert(NP <= kMultiMax && NP <= 8, "a pattern bit per pattern in an entry's byte 2");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t m = a.m, H = a.halo, H16 = round16(H), np = a.np;
     const bool in_memory = m - 1 > H;  // windows are completed in HBM
@@ -90,36 +96,31 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
     uint8_t* tails = smem + kHormHead + kHormGram;
     uint8_t* txt = tails + np * tslot;  // txt[H16 + x] == T[tile0 + x]
 
-    if (threadIdx.x == 0) {
+    // What this thread takes of the rows in the arguments (multi.hpp), read before anything else: every address is the
+    // arguments' plus an index of the thread's, so no read waits for another.  Loads come back in the order they
+    // were sent, so these go out in front of the tile's and the table is built while the tile is on the way.  A thread
+    // with nothing to take reads a byte that exists all the same (m >= 3): no branch, no wait between the reads.
+    constexpr uint32_t kTslotMax = (kHaloMax + 16u) & ~15u;                // the longest tail, rounded: 32
+    constexpr uint32_t kShiftRounds = kMultiMax * kGramCap / THREADS;      // 2
+    static_assert(kMultiMax * kTslotMax <= THREADS && kShiftRounds * THREADS == kMultiMax * kGramCap, "a tail byte and kShiftRounds grams per thread");
+    // tails: thread x takes byte x % 32 of pattern x / 32: ptail[j] = P[m-1-H+j], j <= H
+    const uint32_t tail_g = threadIdx.x / kTslotMax, tail_j = threadIdx.x % kTslotMax;
+    const bool tail_mine = tail_g < np && tail_j <= H;
+    const uint32_t tail_byte = tail_at(a.tail[tail_mine ? tail_g : 0u], m, m - 1 - (tail_mine ? H - tail_j : 0u));
+    // shifts: in round r thread x takes position gram_first(m) + x % kGramCap of pattern (x + r * THREADS) / kGramCap
+    // (at most kGramCap - 1 positions of a pattern shift by less than the default)
+    const uint32_t shift_i = gram_first(m) + threadIdx.x % kGramCap;
+    const bool shift_mine = shift_i + 3 <= m;
+    uint32_t shift_prev[kShiftRounds], shift_last[kShiftRounds];
 #pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            blobs[i] = (uint32_t)i < np ? (unsigned long long)a.blob[i] : 0ull;
-            counts[i] = (uint32_t)i < np ? (unsigned long long)a.count[i] : 0ull;
-            sums[i] = 0;
-        }
+    for (uint32_t r = 0; r < kShiftRounds; ++r) {
+        const uint32_t g = (threadIdx.x + r * THREADS) / kGramCap, i = shift_mine ? shift_i : gram_first(m);
+        shift_prev[r] = tail_at(a.tail[g < np ? g : 0u], m, i);
+        shift_last[r] = tail_at(a.tail[g < np ? g : 0u], m, i + 1);
     }
-    const uint32_t dflt = gram_default(m);
-    for (uint32_t j = threadIdx.x; j < kGramSlots; j += THREADS) gram[j] = dflt;
-    __syncthreads();
-    for (uint32_t i = 0; i < np; ++i) {
-        const uint8_t* blob = horm_global(horm_first(blobs[i]));
-        uint8_t* ptail = tails + i * tslot;
-        for (uint32_t j = threadIdx.x; j <= H; j += THREADS) ptail[j] = blob[m - 1 - H + j];
-    }
-    // shifts: thread x takes position gram_first(m) + x % kGramCap of pattern x / kGramCap (at most kGramCap - 1
-    // positions of a pattern shift by less than the default)
-    for (uint32_t x = threadIdx.x; x < np * kGramCap; x += THREADS) {
-        const uint32_t i = gram_first(m) + x % kGramCap;
-        if (i + 3 <= m) {
-            const uint8_t* blob = horm_global(blobs[x / kGramCap]);
-            atomicMin(gram + gram_slot(blob[i], blob[i + 1]), gram_shift(m, i));
-        }
-    }
-    __syncthreads();  // every shift is in before a pattern bit makes an entry larger
-    if (threadIdx.x < np) {
-        const uint8_t* blob = horm_global(blobs[threadIdx.x]);
-        atomicOr(gram + gram_slot(blob[m - 2], blob[m - 1]), gram_entry_pattern_bit(threadIdx.x));
-    }
+    // pattern bits: thread g < np takes pattern g's last gram
+    const uint32_t bit_g = threadIdx.x < np ? threadIdx.x : 0u;
+    const uint32_t bit_prev = tail_at(a.tail[bit_g], m, m - 2), bit_last = tail_at(a.tail[bit_g], m, m - 1);
 
     const uint64_t e_begin = a.s_begin + m - 1, e_end = a.s_end + m - 1;
     const uint64_t t_end = tile_first + ntiles;
@@ -135,7 +136,28 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
         if (halo_lane) ph = ld_stream16(src - H16);
     };
     uint64_t t = tile_first + blockIdx.x;
-    issue(t * TB);
+    issue(t * TB);  // (the launcher starts no more workgroups than there are tiles)
+
+    // the table and the tails, in LDS: the default, a barrier, the least shift per slot, a barrier, the pattern bits
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            blobs[i] = (uint32_t)i < np ? (unsigned long long)a.blob[i] : 0ull;
+            counts[i] = (uint32_t)i < np ? (unsigned long long)a.count[i] : 0ull;
+            sums[i] = 0;
+        }
+    }
+    const uint32_t dflt = gram_default(m);
+    for (uint32_t j = threadIdx.x; j < kGramSlots; j += THREADS) gram[j] = dflt;
+    if (tail_mine) tails[tail_g * tslot + tail_j] = (uint8_t)tail_byte;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < kShiftRounds; ++r)
+        if ((threadIdx.x + r * THREADS) / kGramCap < np && shift_mine) atomicMin(gram + gram_slot(shift_prev[r], shift_last[r]), gram_shift(m, shift_i));
+    __syncthreads();  // every shift is in before a pattern bit makes an entry larger
+    if (threadIdx.x < np) atomicOr(gram + gram_slot(bit_prev, bit_last), gram_entry_pattern_bit(threadIdx.x) | gram_entry_tag(bit_prev));
+    // (the loop's first barrier stands between these bits and the first walk)
+
     for (; t < t_end; t += gridDim.x) {
         const uint64_t tile0 = t * TB;
         __syncthreads();  // previous tile fully consumed (and tables visible)
@@ -161,8 +183,9 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
         const uint8_t* parked_at = a.text;
         // the staged tile, walked once for all patterns (a lane without a window end has e0 == ehi)
         for (uint32_t e = e0; e < ehi;) {
-            const uint32_t ent = gram[gram_slot(txt[tile_at(e - 1)], txt[tile_at(e)])];  // e >= H16 >= 16: e - 1 is in the halo at least
-            for (uint32_t cand = gram_entry_patterns(ent); cand != 0; cand &= cand - 1) {
+            const uint32_t prev = txt[tile_at(e - 1)], last = txt[tile_at(e)];  // e >= H16 >= 16: e - 1 is in the halo at least
+            const uint32_t ent = gram[gram_slot(prev, last)];
+            for (uint32_t cand = gram_entry_hit(ent, prev); cand != 0; cand &= cand - 1) {  // (a slot hit that is no gram hit: no compare)
                 const uint32_t g = __builtin_ctz(cand);
                 const uint8_t* ptail = tails + g * tslot;
                 uint32_t k = 0;  // bytes matched so far, right to left (the slot promises none of them)
@@ -197,6 +220,17 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
 // ---------------------------------------------------------------------------
 // launcher: the grid and the tile's LDS as launch_hor's streaming branch, plus the skip table and the tails of np patterns
 // ---------------------------------------------------------------------------
+// Workgroups per CU.  A workgroup takes 24.5 KB of LDS and 60 VGPRs, so six could be resident, but the longer walk does
+// not want them: swept on 1 GiB of rand128 at m = 16, 32, 256 in groups of 2, 4, 8, FOUR wins at m = 32 (8 patterns:
+// 0.0207 ms per pattern with 4, 0.0215 with 5, 0.0214 with 6, 0.0222 with 7) and loses nowhere — the solo kernels' value.
+static int horm_wgs(uint32_t m)
+{
+    ScanArgs one = {};
+    one.m = m;
+    one.sparse = 1;
+    return tile_wgs(one);
+}
+
 hipError_t launch_hor_multi(const MultiArgs& a, int num_cus, hipStream_t stream)
 {
     if (a.np < 1 || a.np > (uint32_t)kMultiMax || a.m < 3 || a.halo < 1 || a.halo > kHaloMax || a.halo > a.m - 1) return hipErrorInvalidValue;  // (a gram and the byte before a lane's first window end exist)
@@ -204,11 +238,7 @@ hipError_t launch_hor_multi(const MultiArgs& a, int num_cus, hipStream_t stream)
     const TileRange tr = tiles_for(a.s_begin + m - 1, a.s_end + m - 1, (uint64_t)kHorT * kHorL);
     if (tr.count == 0) return hipSuccess;
     const size_t lds = kHormHead + kHormGram + (size_t)a.np * r16(H + 1) + ((r16(H) + (size_t)kHorT * kHorL + 16 + 63) & ~(size_t)63);  // whole 64-byte blocks: tile_at() permutes inside them
-    // workgroups per CU as a solo launch of one of these patterns (tile_wgs: they are all sparse); smartgpu_tune(4, .) applies
-    ScanArgs one = {};
-    one.m = m;
-    one.sparse = 1;
-    const int wgs_per_cu = g_tune[4] ? g_tune[4] : tile_wgs(one);
+    const int wgs_per_cu = g_tune[4] ? g_tune[4] : horm_wgs(m);  // smartgpu_tune(4, .) applies
     uint32_t grid = (uint32_t)num_cus * (uint32_t)wgs_per_cu;
     if (grid > tr.count) grid = tr.count;
     hipLaunchKernelGGL((hor_multi_scan<kHorT, kHorL, kMultiMax>), dim3(grid), dim3(kHorT), lds, stream, a, tr.first, tr.count);

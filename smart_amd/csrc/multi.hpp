@@ -9,9 +9,17 @@ namespace sg {
 
 constexpr int kMultiMax = 8;  // patterns per pass
 
-// What the patterns of a pass have in common — text, range, length, back halo — and, per pattern, its blob (pattern +
-// u16 tab[256], as launch_hor reads it) and its result slot.  The two arrays are only ever indexed with compile-time
-// constants: entries np .. kMultiMax-1 are not read.
+// The end of a pattern as a launch carries it BY VALUE: the bytes from position gram_first(m) (below) to m - 1 — every
+// gram the skip table enters and the at most 17 bytes a lane compares in LDS — at the front of a row, zeros behind
+// them.  At most kGramCap + 1 = 65 bytes; the row is padded to a multiple of 16.  The plan keeps its row on the host
+// from smartgpu_plan_create on, the launch queue copies it, and the kernel builds the tails and the table from the
+// rows in its arguments: no workgroup reads a pattern from memory before its first tile is on the way.
+constexpr uint32_t kTailRow = 80;
+
+// What the patterns of a pass have in common — text, range, length, back halo — and, per pattern, its row (above), its
+// blob (pattern + u16 tab[256], as launch_hor reads it: read only where a window is completed in memory, m - 1 > halo)
+// and its result slot.  The two pointer arrays are only ever indexed with compile-time constants.  Entries
+// np .. kMultiMax-1 are not read.
 struct MultiArgs {
     const uint8_t* text;        // device pointer to text byte 0
     uint64_t s_begin, s_end;    // start positions to count, as ScanArgs
@@ -20,6 +28,7 @@ struct MultiArgs {
     uint32_t np;                // patterns in this pass, 1 <= np <= kMultiMax
     const uint8_t* blob[kMultiMax];
     unsigned long long* count[kMultiMax];
+    uint8_t tail[kMultiMax][kTailRow];
 };
 
 // The skip table that the patterns of a pass share (Wu-Manber, blocks of two bytes): one entry per slot, indexed by the
@@ -40,10 +49,29 @@ __host__ __device__ inline uint32_t gram_default(uint32_t m) { return m - 1u < k
 __host__ __device__ inline uint32_t gram_shift(uint32_t m, uint32_t i) { return m - 2u - i; }
 // the first position whose gram is entered: those before it allow gram_default(m) or more
 __host__ __device__ inline uint32_t gram_first(uint32_t m) { return m - 1u > kGramCap ? m - 1u - kGramCap : 0u; }
-// an entry's halves
-__host__ __device__ inline uint32_t gram_entry_shift(uint32_t ent) { return ent & 0xFFFFu; }
-__host__ __device__ inline uint32_t gram_entry_patterns(uint32_t ent) { return ent >> 16; }
+// an entry's parts: the shift in byte 0 (at most kGramCap), the pattern bits in byte 2
+__host__ __device__ inline uint32_t gram_entry_shift(uint32_t ent) { return ent & 0xFFu; }
+__host__ __device__ inline uint32_t gram_entry_patterns(uint32_t ent) { return (ent >> 16) & 0xFFu; }
 __host__ __device__ inline uint32_t gram_entry_pattern_bit(uint32_t g) { return 0x10000u << g; }
+// Bytes 1 and 3 tell a slot hit from a gram hit without a compare: a pattern ORs gram_entry_tag(P[m-2]) into its slot
+// with its bit — `prev` in byte 1, its complement in byte 3 — and a window whose last two bytes fall into the slot is
+// compared only if every bit of ITS tag is there.  Slot and prev determine last (the slot is 37 prev + last mod
+// kGramSlots, and last < 256 <= kGramSlots), so with one last gram in a slot this asks for the gram itself; with
+// several, bits of both kinds add up and more windows pass, never fewer.  An entry without a pattern has no tag bit:
+// nothing passes.
+__host__ __device__ inline uint32_t gram_entry_tag(uint32_t prev) { return (prev << 8) | ((prev ^ 0xFFu) << 24); }
+__host__ __device__ inline uint32_t gram_entry_hit(uint32_t ent, uint32_t prev) { return (gram_entry_tag(prev) & ~ent) == 0 ? gram_entry_patterns(ent) : 0u; }
+
+
+// a row: how many bytes it holds, the fill rule, and the byte at pattern position i, gram_first(m) <= i <= m - 1
+__host__ __device__ inline uint32_t tail_stored(uint32_t m) { return m - gram_first(m); }
+static_assert(kGramCap + 1 <= kTailRow && kTailRow % 16 == 0, "a row holds kGramCap grams and is padded to 16 bytes");
+__host__ __device__ inline void tail_fill(uint8_t* row, const uint8_t* P, uint32_t m)
+{
+    const uint32_t first = gram_first(m), n = tail_stored(m);
+    for (uint32_t j = 0; j < kTailRow; ++j) row[j] = j < n ? P[first + j] : (uint8_t)0;
+}
+__host__ __device__ inline uint32_t tail_at(const uint8_t* row, uint32_t m, uint32_t i) { return row[(int32_t)i - (int32_t)gram_first(m)]; }
 
 // The launcher of k_horm.hip, reached through a pointer that the unit's own static initialiser sets: api.cpp holds
 // the pointer (null: no launch is ever queued), so a program that includes api.cpp without k_horm.hip still links.
