@@ -180,7 +180,8 @@ void smartgpu_plan_free(smartgpu_plan *p);
  * Untimed streaming Horspool / Tuned BM launches over one range of one text with
  * one pattern length may be held back until smartgpu_coalesce() of them have
  * gathered and then run as ONE pass over the text (hor_multi_scan); the counts
- * are the same.  A launch is complete no later than the next
+ * are the same; launches that are held back may run after later launches that are
+ * not (counts are added, so the order decides nothing).  A launch is complete no later than the next
  * smartgpu_device_sync(), smartgpu_plan_result() or smartgpu_stream_mark() on its
  * device; every other call that waits for, times, resets or frees what the launch
  * touches sends it first as well.  A caller who synchronises by other means (the

@@ -662,6 +662,8 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // never waits for a flush while full groups exist, and at most g_coalesce - 1 launches per key are ever pending.  Every
 // entry point that waits for, times, orders work on, or frees what is on the device's stream sends what is pending
 // first (flush_queue), in arrival order; a launch that is alone by then goes through launch_scan as it always did.
+// An untimed launch that cannot share a pass (another algorithm, a pattern whose symbols repeat) is no such entry point:
+// it is sent at once, ahead of what is pending, and a key goes on gathering its launches across it.
 // The queue holds device pointers of plans and texts: smartgpu_plan_free, _plan_set_result_buffer and _text_free flush.
 // The plan's tail row is copied, not pointed to.
 struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; uint8_t tail[sg::kTailRow]; };
@@ -1001,7 +1003,11 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
     bool queued = false;
     HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), p->tail, timed != 0, &queued), return SMARTGPU_ERR_HIP);
     if (queued) { p->timed[slot] = false; return SMARTGPU_OK; }
-    HIP_TRY(flush_queue(d), return SMARTGPU_ERR_HIP);  // everything else keeps its place behind what was queued before it
+    // A timed launch keeps its place behind what was queued before it: its events bracket this kernel alone.  Any other
+    // launch that cannot share a pass goes ahead of what is pending: counts are ADDED to their slots, in any order, and
+    // sending a half-filled key here costs its launches a pass of their own over the text.  (One m = 32 pattern in the
+    // 250 of bench.py repeats its symbols: it used to turn the 25 passes of the 200 timed launches into 26 and a solo scan.)
+    if (timed) HIP_TRY(flush_queue(d), return SMARTGPU_ERR_HIP);
     p->timed[slot] = timed != 0;
     if (timed) {
         if (!p->ev0[slot]) {
