@@ -410,8 +410,8 @@ int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char *P, uin
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P == NULL, m = 0 or m > SMARTGPU_XSIZE,
  * k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0.
  * No launch: m > n (count 0), more foreign bytes than k (count 0).
- * NOT offered: a batch call, insertions and deletions (edit distance), k > 7, byte texts.  (Set patterns with mismatches:
- * smartgpu_psearch_sets_mis64 below.)
+ * NOT offered: a batch call, k > 7, byte texts.  (Set patterns with mismatches: smartgpu_psearch_sets_mis64 below; insertions
+ * and deletions: smartgpu_psearch_edit64 below.)
  * MEASURED on an MI355X, 1 Gi symbols (profiles/packed/RESULTS.md, "Mismatches"): on rand4, m = 8 .. 256, planes_mis_scan takes
  * 1.22-1.26 / 1.25-1.94 / 1.34-2.11 / 1.55-3.56 x planes_scan's kernel time for k = 0 / 1 / 3 / 7 (per call 1.07-1.17 /
  * 1.07-1.62 / 1.13-1.76 / 1.24-2.76 x), outside the run-to-run spread in every cell.  m = 16: ONE k = 1 call is 14.8 x
@@ -446,7 +446,7 @@ int smartgpu_pfind_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgp
  * m > SMARTGPU_XSIZE, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0, and a set with a
  * bit at or above the text's number of values (bits 4..7 always are; the message names the position).
  * No launch: m > n (count 0), more empty sets than k (count 0).
- * NOT offered: a batch call, insertions and deletions (edit distance), k > 7, byte texts.
+ * NOT offered: a batch call, k > 7, byte texts.  (Insertions and deletions: smartgpu_psearch_sets_edit64 below.)
  * NOT measured: everything — no timing of these calls has been taken (tools/sets_mis_probe.py takes the three comparisons:
  * singleton sets against smartgpu_psearch_mis64, k = 0 against smartgpu_psearch_sets64, one find against the finds over
  * the pattern's exact expansions); the occupancy choices are smartgpu_psearch_mis64's, taken over unmeasured. */
@@ -454,6 +454,52 @@ int smartgpu_psearch_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, con
                                 uint64_t *count, double *pre_ms, double *run_ms);
 int smartgpu_pfind_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
                               uint64_t *positions, uint8_t *mismatches, uint64_t cap, uint64_t *count);
+/* EDIT DISTANCE on a packed text: the occurrences of P within k unit-cost substitutions, INSERTIONS and DELETIONS ("where does
+ * this primer bind with one base skipped?" — invisible to smartgpu_psearch_mis64 at any k).  Nothing in the reference does this.
+ * For the range [off, off+n) and every off <= e < off+n, D(e) is the minimum over off <= s <= e+1 of the Levenshtein distance
+ * between P and the symbols [s, e]; s = e+1 is the empty substring, at distance m.  That is the last row of Sellers' dynamic
+ * programme on the range alone — D[0][*] = 0, D[i][before off] = i —: a match never reaches outside the range.  An
+ * OCCURRENCE is an END position e with D(e) <= k.  It is reported as e, the index of the match's last symbol relative to
+ * symbol 0 of the text, together with D(e); start positions and alignments are not.  With k = 0 the occurrences are exactly
+ * smartgpu_pfind64's positions plus m - 1.
+ * 1 <= m <= SMARTGPU_PEDIT_MAXM; 0 <= k <= SMARTGPU_PMIS_MAX.  k >= m is legal: every end position of the range is an
+ * occurrence, its distance is still reported.  m > n is legal here, unlike the Hamming calls: a short range can match with
+ * deletions; only n + k < m is "count 0, no launch".  A pattern byte the text does not hold accepts nothing (a substitution,
+ * or a deletion, wherever it is aligned): these calls need no bookkeeping for it.
+ * The sets calls take sets[j] as smartgpu_psearch_sets64 does, with "T[e'] == P[j]" replaced by "the code of T[e'] is a
+ * member of sets[j]"; an empty set accepts nothing, as a foreign byte; a full set accepts everything.  With singleton sets
+ * the answers are those of the byte-pattern calls.
+ * One pass over the planes (planes_edit_scan, planes_edit_find; smart_amd/csrc/k_pedit.hip): Myers' bit-vector recurrence
+ * in Hyyrö's search form, one text symbol per step and lane — a column depends on the one before it, so these kernels walk
+ * the text per lane where every other plane kernel decides 32 positions per instruction.  A lane owns 128 consecutive end
+ * positions and walks up to m + k symbols before them without counting: (128 + m + k) / 128 = 1.07 .. 1.55 symbols walked
+ * per symbol of the range.  The recurrence consumes only the masks "which pattern positions accept code c", so a set pattern
+ * costs the kernels what a byte pattern costs.
+ * The count width, times, cap / count / SMARTGPU_ERR_NOMEM behaviour (cap == 0 with NULL buffers is a count), distances == NULL
+ * and the order (ascending, relative to symbol 0) are those of smartgpu_psearch_mis64 / smartgpu_pfind_mis64, with ends[i] /
+ * distances[i] in place of positions[i] / mismatches[i].
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / sets == NULL, m = 0 or m > SMARTGPU_PEDIT_MAXM (the
+ * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
+ * cap > 0, and — the sets calls — a set with a bit at or above the text's number of values (the message names the position).
+ * NOT offered: m > 64 (block-based Myers), k > 7, affine or weighted costs, start positions or alignments, a batch call, byte
+ * texts.
+ * MEASURED on an MI355X, 1 Gi symbols, m = 8 .. 64, k = 0 .. 7 (profiles/packed/RESULTS.md, "Edit distance"; tools/edit_probe.py):
+ * on rand4 planes_edit_scan takes 0.90-1.06 ms for m <= 32 (one dword per column: 1.0-1.2 T symbols/s) and 1.49-1.81 ms for
+ * m = 33, 64 (two dwords: 0.59-0.72 T symbols/s), per call 0.94-1.11 / 1.46-1.77 ms; the time grows with the warm-up factor and
+ * hardly with the number of occurrences.  That is 5.5-24.7 x planes_mis_scan's kernel time at the same m and k (per call 5.5-
+ * 19.8 x), outside the run-to-run spread in every cell: the nearest question the library already answers, not the same one.
+ * On rand2 0.61-0.73 / 1.15-1.41 ms (planes of Infinity-Cache size: possibly flattered).
+ * NOT measured: the run of 128 positions per lane against a longer one, the occupancy and the grid (planes_scan's, taken over),
+ * the find form's speed, texts beyond 1 Gi symbols. */
+#define SMARTGPU_PEDIT_MAXM 64
+int smartgpu_psearch_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                            uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_pfind_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                          uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+int smartgpu_psearch_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                                 uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_pfind_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                               uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
 /* No device: the reverse complement of an IUPAC nucleotide pattern — a primer is searched on both strands.  P[0..m): the
  * letters smartgpu_iupac_sets accepts; out[j] = the complement of P[m-1-j]: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and
  * N stay; U reads as T (its complement is A; no U is ever written).  Case is preserved.  out has m bytes (no terminator is

@@ -25,6 +25,7 @@
 
 #include "kernels.hpp"
 #include "multi.hpp"
+#include "pedit.hpp"
 #include "planes.hpp"
 #include "planes_host.hpp"
 #include "route.hpp"
@@ -799,6 +800,9 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
 
 namespace sg {
 hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // multi.hpp: set by k_horm.hip where that unit is linked
+// pedit.hpp: set by k_pedit.hip where that unit is linked
+hipError_t (*g_planes_edit_scan)(const PlaneEditArgs&, int, int, hipStream_t) = nullptr;
+hipError_t (*g_planes_edit_find)(const PlaneEditArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
 }
 
 extern "C" {
@@ -2170,6 +2174,130 @@ uint32_t mis_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint3
     return foreign;
 }
 
+// ---- edit distance (pedit.hpp): END positions, n of them whatever m is, and m > n is legal — its own run path, so that
+// no bound of pcount_run / pfind_run (n - m + 1 start positions) changes ----
+
+// The checks of the four edit calls that need no device; `what` names the pattern argument.
+int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off,
+                     uint64_t n, const uint64_t* count)
+{
+    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
+    if (m < 1 || m > SMARTGPU_PEDIT_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_PEDIT_MAXM); return SMARTGPU_ERR_ARG; }
+    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
+    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
+    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
+    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
+    return SMARTGPU_OK;
+}
+
+// The pattern's masks for a checked call: from bytes (sets == false) or from sets.  SMARTGPU_ERR_ARG: a set names a code the
+// text does not hold.
+int edit_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, sg::PlaneEditArgs* a)
+{
+    if (!sets) {
+        sg::edit_peq_pattern(t->values, t->nvalues, pat, m, a->peq);
+        return SMARTGPU_OK;
+    }
+    const int bad = sg::edit_peq_sets(t->nvalues, pat, m, a->peq);
+    if (bad < 0) return SMARTGPU_OK;
+    set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, pat[bad], t->nvalues);
+    return SMARTGPU_ERR_ARG;
+}
+
+void edit_head(sg::PlaneEditArgs& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
+{
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.e_begin = off;
+    a.e_end = off + n;
+    a.m = m;
+    a.k = k;
+    a.count = d->batch_counts;
+}
+
+// One count of end positions, n + k >= m: the times are pcount_run's (no pattern is staged: the masks are kernel arguments).
+int pedit_count(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                uint64_t* count, double* pre_ms, double* run_ms)
+{
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    sg::PlaneEditArgs a;
+    if ((rc = edit_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
+    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
+    if (!sg::g_planes_edit_scan) { set_error("%s: this program holds no planes_edit_scan kernel (k_pedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const double t_pre = now_ms();
+    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
+    const double pre = now_ms() - t_pre;
+    const double t0 = now_ms();
+    edit_head(a, d, text, m, k, off, n);
+    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(sg::g_planes_edit_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+    const double run = now_ms() - t0;
+    // more occurrences than end positions: refused like a poisoned count, never reported
+    if (d->pinned_counts[0] > n) { set_error("planes_edit_scan: count %llu exceeds the %llu end positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)n); return SMARTGPU_ERR_HIP; }
+    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
+}
+
+// One find of end positions: pfind_run's steps and return codes with n end positions in place of n - m + 1 start positions.
+int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+               uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    sg::PlaneEditArgs a;
+    if ((rc = edit_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
+    if (n + k < m) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    if (!sg::g_planes_edit_find) { set_error("%s: this program holds no planes_edit_find kernel (k_pedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
+    edit_head(a, d, text, m, k, off, n);
+    const uint64_t room = cap < n ? cap : n;  // no more entries than end positions
+    bool own = false;
+    unsigned long long* out = nullptr;
+    uint64_t room_got = room;
+    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
+    const bool ok = hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+                    sg::g_planes_edit_find(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
+                    hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+                    hipStreamSynchronize(d->stream) == hipSuccess;
+    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
+    int r = SMARTGPU_OK;
+    if (!ok) {
+        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        r = SMARTGPU_ERR_HIP;
+    } else if (total > n) {  // refused like a poisoned count, never reported
+        set_error("planes_edit_find: cursor %llu exceeds the %llu end positions", total, (unsigned long long)n);
+        r = SMARTGPU_ERR_HIP;
+    } else if (total && total <= room_got) {
+        if (!copy_positions(d, ends, out, total)) {
+            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+            r = SMARTGPU_ERR_HIP;
+        } else if (!sg::order_spans(ends, total, off, off + n - 1, sg::kMisShift)) {
+            set_error("planes_edit_find: the entries are not ascending spans of %llu end positions", (unsigned long long)sg::kFindSpan);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (own) (void)hipFree(out);
+    if (r != SMARTGPU_OK) return r;
+    *count = total;
+    if (total <= cap && total > room_got) {
+        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu entries", call, total, (unsigned long long)cap, (unsigned long long)room);
+        return SMARTGPU_ERR_NOMEM;
+    }
+    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    unpack_mis(ends, distances, total);
+    return SMARTGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2506,6 +2634,31 @@ int smartgpu_pfind_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const
                             cap, count, sg::kMisShift);
     if (r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
     return r;
+}
+
+/* ---- edit distance: end positions within k substitutions, insertions and deletions (pedit.hpp, k_pedit.hip) ------------ */
+int smartgpu_psearch_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                            uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return pedit_count("psearch_edit64", P, false, m, k, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_pfind_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                          uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return pedit_find("pfind_edit64", P, false, m, k, text, off, n, ends, distances, cap, count);
+}
+
+int smartgpu_psearch_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                                 uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return pedit_count("psearch_sets_edit64", sets, true, m, k, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_pfind_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                               uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return pedit_find("pfind_sets_edit64", sets, true, m, k, text, off, n, ends, distances, cap, count);
 }
 
 int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)

@@ -130,6 +130,10 @@ def _load(path):
         "smartgpu_pfind_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_sets_mis64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_sets_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_psearch_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_pfind_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_psearch_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_pfind_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
     }
     for a in ALGOS:
@@ -574,6 +578,31 @@ def pfind_sets_mis(sets, ptext, k, off=0, n=None, cap=1 << 20):
     """(positions, mismatches, count) of a SET pattern with at most k mismatches (psearch_sets_mis) in symbols [off, off+n)
     of a PackedText, as pfind_mis returns them; (None, None, count) when there are more than `cap`."""
     return _pfind("pfind_sets_mis64", sets, ptext, off, n, cap, k)
+
+
+def psearch_edit(P, ptext, k, off=0, n=None):
+    """(count, pre_ms, run_ms) of the END positions e in symbols [off, off+n) of a PackedText where P occurs within edit
+    distance k — substitutions, insertions and deletions, 0 <= k <= 7, 1 <= len(P) <= 64 (smartgpu_psearch_edit64): some
+    substring [s, e] of the range, off <= s, is at most k edits from P."""
+    return _pcount("psearch_edit64", P, ptext, off, n, k)
+
+
+def pfind_edit(P, ptext, k, off=0, n=None, cap=1 << 20):
+    """(ends, distances, count) of P within edit distance k (psearch_edit) in symbols [off, off+n) of a PackedText: the
+    ascending end positions (uint64, the match's last symbol, relative to symbol 0), the edit distance of each (uint8) and
+    their number; (None, None, count) when there are more than `cap`."""
+    return _pfind("pfind_edit64", P, ptext, off, n, cap, k)
+
+
+def psearch_sets_edit(sets, ptext, k, off=0, n=None):
+    """psearch_edit for a SET pattern (psearch_sets): a text symbol matches position j when its code is a member of sets[j]
+    (smartgpu_psearch_sets_edit64).  An empty set matches nothing."""
+    return _pcount("psearch_sets_edit64", sets, ptext, off, n, k)
+
+
+def pfind_sets_edit(sets, ptext, k, off=0, n=None, cap=1 << 20):
+    """(ends, distances, count) of a SET pattern within edit distance k (psearch_sets_edit), as pfind_edit returns them."""
+    return _pfind("pfind_sets_edit64", sets, ptext, off, n, cap, k)
 
 
 def iupac_revcomp(pattern):
