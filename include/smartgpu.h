@@ -460,7 +460,7 @@ int smartgpu_pfind_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, const
  * between P and the symbols [s, e]; s = e+1 is the empty substring, at distance m.  That is the last row of Sellers' dynamic
  * programme on the range alone — D[0][*] = 0, D[i][before off] = i —: a match never reaches outside the range.  An
  * OCCURRENCE is an END position e with D(e) <= k.  It is reported as e, the index of the match's last symbol relative to
- * symbol 0 of the text, together with D(e); start positions and alignments are not.  With k = 0 the occurrences are exactly
+ * symbol 0 of the text, together with D(e); start positions and alignments come from smartgpu_palign_edit64.  With k = 0 the occurrences are exactly
  * smartgpu_pfind64's positions plus m - 1.
  * 1 <= m <= SMARTGPU_PEDIT_MAXM; 0 <= k <= SMARTGPU_PMIS_MAX.  k >= m is legal: every end position of the range is an
  * occurrence, its distance is still reported.  m > n is legal here, unlike the Hamming calls: a short range can match with
@@ -481,8 +481,8 @@ int smartgpu_pfind_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, const
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / sets == NULL, m = 0 or m > SMARTGPU_PEDIT_MAXM (the
  * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
  * cap > 0, and — the sets calls — a set with a bit at or above the text's number of values (the message names the position).
- * NOT offered: m > 64 (block-based Myers), k > 7, affine or weighted costs, start positions or alignments, a batch call, byte
- * texts.
+ * NOT offered: m > 64 (block-based Myers), k > 7, affine or weighted costs, a batch call, byte texts.  (Start positions and
+ * alignments: smartgpu_palign_edit64 below.)
  * MEASURED on an MI355X, 1 Gi symbols, m = 8 .. 64, k = 0 .. 7 (profiles/packed/RESULTS.md, "Edit distance"; tools/edit_probe.py):
  * on rand4 planes_edit_scan takes 0.90-1.06 ms for m <= 32 (one dword per column: 1.0-1.2 T symbols/s) and 1.49-1.81 ms for
  * m = 33, 64 (two dwords: 0.59-0.72 T symbols/s), per call 0.94-1.11 / 1.46-1.77 ms; the time grows with the warm-up factor and
@@ -500,6 +500,54 @@ int smartgpu_psearch_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, co
                                  uint64_t *count, double *pre_ms, double *run_ms);
 int smartgpu_pfind_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
                                uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+/* START POSITIONS and ALIGNMENTS of edit-distance occurrences: which interval of the text an end position e reported by
+ * smartgpu_pfind_edit64 stands for, and which symbols were substituted, added or skipped.  For the range [off, off+n), the
+ * pattern (bytes or sets) and an end position off <= e < off+n, with D(e) as smartgpu_psearch_edit64 defines it:
+ * START.  s(e) is the LARGEST s in [off, e+1] with ed(P, T[s..e]) = D(e): the shortest nearest substring (s = e+1 is the
+ * empty substring, at distance m).  It is unique, and it is what a backward walk from e meets first.
+ * ALIGNMENT.  A sequence of L <= m + k operations in text order from s to e, two bits each:
+ *   0 '=': the text symbol is accepted by the pattern position; consumes one of each;
+ *   1 'X': a substitution; consumes one of each, the symbol is not accepted;
+ *   2 'I': a text symbol with no pattern partner (an insertion: a text symbol added); consumes text only;
+ *   3 'D': a pattern symbol with no text partner; consumes pattern only.
+ * I and D are the PATTERN's edits: they are the opposite letters from SAM's CIGAR with the text as the reference.
+ * Which optimal alignment is returned is fixed, on the suffix distances R[i][j] = ed(P[i..m), T[s+j..e]), J = e - s + 1:
+ * start at (i, j) = (0, 0); until i == m and j == J take the first of these that applies:
+ *   1. if i < m, j < J and R[i+1][j+1] + (accepted ? 0 : 1) == R[i][j]: '=' or 'X';
+ *   2. else if i < m and R[i+1][j] + 1 == R[i][j]: 'D';
+ *   3. else 'I'.
+ * PACKING.  Three uint64_t per occurrence: operation t is in bits 2 * (t mod 32) of word t / 32, the top byte of the third
+ * word (bits 56..63) holds L, every other unused bit is 0 (m + k <= 71 operations take 142 bits).
+ * INPUT.  ends[0..count): end positions relative to symbol 0 of the text, as smartgpu_pfind_edit64 returns them for the same
+ * P, m, k, off, n — but any e in [off, off+n) is legal, in any order, duplicates included; a subset of the find's list is fine.
+ * OUTPUT.  starts[i] = s(ends[i]); distances[i] = D(ends[i]), computed, not taken on trust (no distances are passed in);
+ * ops[3i .. 3i+3) the alignment.  distances and ops may be NULL; ops == NULL skips the traceback.
+ * AN END THAT IS NO OCCURRENCE is decided exactly: the kernel walks min(m + k, e - off + 1) columns backward, whose minimum
+ * is D(e) whenever D(e) <= k (a match within k has at most m + k symbols); a minimum above k means D(e) > k, and then
+ * starts[i] = UINT64_MAX, distances[i] = 255, the three ops words are 0, and the call still returns SMARTGPU_OK.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: the refusals of smartgpu_pfind_edit64 (P / sets == NULL, m
+ * outside [1, SMARTGPU_PEDIT_MAXM], k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, a set with a bit at or above
+ * the text's number of values), ends == NULL or starts == NULL with count > 0, and an ends[i] outside [off, off+n) (the
+ * message names i and the value).  count == 0 is SMARTGPU_OK with no launch.  Lists longer than the device's find buffer
+ * (8 Mi entries: 8 Mi occurrences without ops, 2 Mi with them) are worked through in pieces of that size.
+ * One lane per occurrence (planes_edit_align; smart_amd/csrc/k_palign.hip): the recurrence of the edit calls in its DISTANCE
+ * form over the reversed pattern, walking e, e-1, ...; with ops every column goes to LDS and the traceback reads cell values
+ * back from the columns' bit vectors.
+ * NOT offered: the longest start, all starts, all optimal alignments; m > 64, k > 7, affine costs, byte texts, a kernel that
+ * finds and aligns in one pass.
+ * MEASURED on an MI355X, 1 Gi symbols of rand4 with planted copies of the pattern, about 1 Mi occurrences (7 Mi for m = 20,
+ * k = 7, which rand4 holds by itself), every end of the find aligned, ms per call by the host clock, the list's copy to the
+ * device and the results' copy back included (profiles/packed/RESULTS.md, "Edit distance: starts and alignments";
+ * tools/align_probe.py): m = 20 / 64, k = 2 / 7: without ops 1.85-1.91 ms per Mi occurrences (1.8-2.0 ns per occurrence),
+ * which ADDS 19-31 % TO THE FIND that produced the ends (6.7-9.8 ms; 45 ms for the 7 Mi); with ops 4.3-4.7 ms (4.0-4.5 ns
+ * per occurrence), 44-71 % of the find, 2.3-2.6 x the call without ops, outside the run-to-run spread in every cell.
+ * NOT measured: the kernel's own time (no kernel trace: how a call divides between kernel and copies is not known), 64 / 32
+ * occurrences per workgroup against other sizes, the uncoalesced text loads, texts beyond 1 Gi symbols, positions beyond
+ * 2^32 (the tests' texts have at most 2^20 + 3 symbols). */
+int smartgpu_palign_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                           const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+int smartgpu_palign_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                                const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 /* No device: the reverse complement of an IUPAC nucleotide pattern — a primer is searched on both strands.  P[0..m): the
  * letters smartgpu_iupac_sets accepts; out[j] = the complement of P[m-1-j]: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and
  * N stay; U reads as T (its complement is A; no U is ever written).  Case is preserved.  out has m bytes (no terminator is

@@ -26,6 +26,7 @@
 #include "kernels.hpp"
 #include "multi.hpp"
 #include "pedit.hpp"
+#include "palign.hpp"
 #include "planes.hpp"
 #include "planes_host.hpp"
 #include "route.hpp"
@@ -803,6 +804,8 @@ hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // mul
 // pedit.hpp: set by k_pedit.hip where that unit is linked
 hipError_t (*g_planes_edit_scan)(const PlaneEditArgs&, int, int, hipStream_t) = nullptr;
 hipError_t (*g_planes_edit_find)(const PlaneEditArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
+// palign.hpp: set by k_palign.hip where that unit is linked
+hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
 }
 
 extern "C" {
@@ -2298,6 +2301,82 @@ int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
     return SMARTGPU_OK;
 }
 
+// ---- starts and alignments of edit-distance occurrences (palign.hpp): a list of END positions in, one lane each ----
+
+// copy_positions the other way: the caller's (pageable) end positions to the device through the pinned staging buffer
+bool upload_positions(DeviceCtx* d, unsigned long long* dst, const uint64_t* src, uint64_t count)
+{
+    for (uint64_t done = 0; done < count;) {
+        const uint64_t part = std::min<uint64_t>(count - done, d->pinned_bytes / 8);
+        std::memcpy(d->pinned, src + done, part * 8);
+        if (hipMemcpyAsync(dst + done, d->pinned, part * 8, hipMemcpyHostToDevice, d->stream) != hipSuccess ||
+            hipStreamSynchronize(d->stream) != hipSuccess)
+            return false;
+        done += part;
+    }
+    return true;
+}
+
+// Both align calls.  The device works in the find's own buffer (find_reserve, at most kFindKeep entries, so never an
+// allocation per call beyond the first): a piece of `part` occurrences is [io: part entries | ops: 3 * part words], so a piece
+// is kFindKeep occurrences without ops and kFindKeep / 4 with them; longer lists go through piece after piece.
+int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
+    if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, k, text, off, n, &count);
+    if (rc != SMARTGPU_OK) return rc;
+    sg::PlaneEditArgs masks;
+    if ((rc = edit_masks(text, pat, m, sets, &masks)) != SMARTGPU_OK) return rc;  // (the pattern as given: the message names ITS position)
+    for (uint64_t i = 0; i < count; ++i)
+        if (ends[i] < off || ends[i] - off >= n) {
+            set_error("%s: ends[%llu] = %llu outside the range [%llu,+%llu)", call, (unsigned long long)i, (unsigned long long)ends[i], (unsigned long long)off, (unsigned long long)n);
+            return SMARTGPU_ERR_ARG;
+        }
+    if (count == 0) return SMARTGPU_OK;
+    if (!sg::g_planes_edit_align) { set_error("%s: this program holds no planes_edit_align kernel (k_palign.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    uint8_t rev[SMARTGPU_PEDIT_MAXM];
+    for (uint32_t j = 0; j < m; ++j) rev[j] = pat[m - 1 - j];
+    (void)edit_masks(text, rev, m, sets, &masks);  // the kernel walks backward: the masks of the REVERSED pattern
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    sg::PlaneAlignArgs a;
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.e_begin = off;
+    a.e_end = off + n;
+    a.m = m;
+    a.k = k;
+    std::memcpy(a.peq, masks.peq, sizeof a.peq);
+    const uint64_t piece = ops ? kFindKeep / 4 : kFindKeep;
+    for (uint64_t done = 0; done < count;) {
+        const uint64_t part = std::min<uint64_t>(count - done, piece);
+        bool own = false;
+        unsigned long long* buf = find_reserve(d, part * (ops ? 4 : 1), &own);
+        if (!buf) return SMARTGPU_ERR_NOMEM;
+        a.io = buf;
+        a.ops = ops ? buf + part : nullptr;
+        a.count = part;
+        const bool ok = upload_positions(d, a.io, ends + done, part) &&
+                        sg::g_planes_edit_align(a, text->planes, d->stream) == hipSuccess &&
+                        hipStreamSynchronize(d->stream) == hipSuccess &&
+                        copy_positions(d, starts + done, a.io, part) &&
+                        (!ops || copy_positions(d, ops + 3 * done, a.ops, 3 * part));
+        if (!ok) set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        if (own) (void)hipFree(buf);
+        if (!ok) return SMARTGPU_ERR_HIP;
+        for (uint64_t i = done; i < done + part; ++i) {
+            const uint64_t v = starts[i];
+            const bool none = v == sg::kAlignNone;
+            starts[i] = none ? UINT64_MAX : v >> sg::kMisShift;
+            if (distances) distances[i] = none ? 255 : static_cast<uint8_t>(v & ((1u << sg::kMisShift) - 1u));
+        }
+        done += part;
+    }
+    return SMARTGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2659,6 +2738,19 @@ int smartgpu_pfind_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, cons
                                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     return pedit_find("pfind_sets_edit64", sets, true, m, k, text, off, n, ends, distances, cap, count);
+}
+
+/* ---- edit distance: start positions and alignments of listed end positions (palign.hpp, k_palign.hip) ------------------ */
+int smartgpu_palign_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                           const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    return palign_run("palign_edit64", P, false, m, k, text, off, n, ends, count, starts, distances, ops);
+}
+
+int smartgpu_palign_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                                const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    return palign_run("palign_sets_edit64", sets, true, m, k, text, off, n, ends, count, starts, distances, ops);
 }
 
 int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)

@@ -134,6 +134,8 @@ def _load(path):
         "smartgpu_pfind_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_palign_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "smartgpu_palign_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
     }
     for a in ALGOS:
@@ -603,6 +605,71 @@ def psearch_sets_edit(sets, ptext, k, off=0, n=None):
 def pfind_sets_edit(sets, ptext, k, off=0, n=None, cap=1 << 20):
     """(ends, distances, count) of a SET pattern within edit distance k (psearch_sets_edit), as pfind_edit returns them."""
     return _pfind("pfind_sets_edit64", sets, ptext, off, n, cap, k)
+
+
+def _palign(name, pat, ptext, k, ends, off, n, ops):
+    pat = _u8(pat)
+    if n is None:
+        n = len(ptext) - off
+    ends = np.ascontiguousarray(ends, dtype=np.uint64)
+    count = len(ends)
+    starts = np.empty(count, dtype=np.uint64)
+    dist = np.empty(count, dtype=np.uint8)
+    words = np.empty((count, 3), dtype=np.uint64) if ops else None
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, len(pat), k, ptext._h, off, n, ends.ctypes.data if count else None, count,
+                                            starts.ctypes.data if count else None, dist.ctypes.data if count else None,
+                                            words.ctypes.data if ops and count else None)
+    if rc != 0:
+        raise _err("%s rc=%d" % (name, rc))
+    return starts, dist, words
+
+
+def palign_edit(P, ptext, k, ends, off=0, n=None, ops=True):
+    """(starts, distances, ops) of the END positions `ends` (as pfind_edit returns them for the same P, k, off, n; any order,
+    duplicates allowed, any e of the range) — smartgpu_palign_edit64: starts[i] is the LARGEST s with ed(P, T[s..ends[i]]) =
+    D(ends[i]) (uint64), distances[i] = D(ends[i]) (uint8, computed), ops the alignment as uint64 of shape (count, 3), two
+    bits per operation (edit_cigar reads a row), or None with ops=False (no traceback).  An end with D(e) > k:
+    start 2**64 - 1, distance 255, ops 0."""
+    return _palign("palign_edit64", P, ptext, k, ends, off, n, ops)
+
+
+def palign_sets_edit(sets, ptext, k, ends, off=0, n=None, ops=True):
+    """palign_edit for a SET pattern (psearch_sets_edit; smartgpu_palign_sets_edit64)."""
+    return _palign("palign_sets_edit64", sets, ptext, k, ends, off, n, ops)
+
+
+def pfind_edit_align(P, ptext, k, off=0, n=None, cap=1 << 20):
+    """(starts, ends, distances, ops, count): pfind_edit, then palign_edit on its ends — every occurrence of P within edit
+    distance k as the interval [start, end] of the text, its distance and its alignment.  More than `cap` occurrences:
+    (None, None, None, None, count)."""
+    ends, dist, count = pfind_edit(P, ptext, k, off=off, n=n, cap=cap)
+    if ends is None:
+        return None, None, None, None, count
+    starts, adist, ops = palign_edit(P, ptext, k, ends, off=off, n=n)
+    if not np.array_equal(adist, dist):
+        raise SmartGpuError("pfind_edit_align: the align call's distances differ from the find's")
+    return starts, ends, dist, ops, count
+
+
+def edit_cigar(ops_row, sam=False):
+    """The run-length string of one alignment (a row of palign_edit's ops: three uint64), e.g. "12=1X3=1D4=": '=' accepted,
+    'X' substituted, 'I' a text symbol with no pattern partner, 'D' a pattern symbol with no text partner — the PATTERN's
+    edits.  sam=True swaps the letters I and D: SAM's CIGAR with the text as the reference.  No operations: ""."""
+    w = [int(x) for x in ops_row]
+    if len(w) != 3:
+        raise ValueError("an alignment is three uint64 words, not %d" % len(w))
+    letters = "=XDI" if sam else "=XID"
+    out, run, last = [], 0, None
+    for t in range(w[2] >> 56):
+        op = letters[w[t // 32] >> (2 * (t % 32)) & 3]
+        if op != last and run:
+            out.append("%d%s" % (run, last))
+            run = 0
+        last = op
+        run += 1
+    if run:
+        out.append("%d%s" % (run, last))
+    return "".join(out)
 
 
 def iupac_revcomp(pattern):

@@ -22,6 +22,7 @@ UNITS = {
     "k_util": ("k_util.hip",),
     "k_planes": ("k_planes.hip", "planes.hpp"),
     "k_pedit": ("k_pedit.hip", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_palign": ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {
     "hor_scan": "k_hor", "hor_multi_scan": "k_horm", "hor_scan_bp": "k_hor", "hor_scan_gram": "k_horg", "bm_scan_gram": "k_bmg", "bm_scan": "k_bm", "bndm_scan": "k_bndm", "sbndm_scan": "k_bndmx",
@@ -32,6 +33,7 @@ KERNEL_UNIT = {
     "planes_mis_scan": "k_planes", "planes_mis_find": "k_planes",
     "planes_sets_mis_scan": "k_planes", "planes_sets_mis_find": "k_planes",
     "planes_edit_scan": "k_pedit", "planes_edit_find": "k_pedit",
+    "planes_edit_align": "k_palign",
 }
 
 
