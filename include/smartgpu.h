@@ -481,8 +481,8 @@ int smartgpu_pfind_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, const
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / sets == NULL, m = 0 or m > SMARTGPU_PEDIT_MAXM (the
  * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
  * cap > 0, and — the sets calls — a set with a bit at or above the text's number of values (the message names the position).
- * NOT offered: m > 64 (block-based Myers), k > 7, affine or weighted costs, a batch call, byte texts.  (Start positions and
- * alignments: smartgpu_palign_edit64 below.)
+ * NOT offered: affine or weighted costs, a batch call, byte texts.  (m > 64 and k > 7: smartgpu_psearch_editl64 below, up to
+ * 256 symbols and 31 edits.  Start positions and alignments: smartgpu_palign_edit64 below.)
  * MEASURED on an MI355X, 1 Gi symbols, m = 8 .. 64, k = 0 .. 7 (profiles/packed/RESULTS.md, "Edit distance"; tools/edit_probe.py):
  * on rand4 planes_edit_scan takes 0.90-1.06 ms for m <= 32 (one dword per column: 1.0-1.2 T symbols/s) and 1.49-1.81 ms for
  * m = 33, 64 (two dwords: 0.59-0.72 T symbols/s), per call 0.94-1.11 / 1.46-1.77 ms; the time grows with the warm-up factor and
@@ -533,8 +533,8 @@ int smartgpu_pfind_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, cons
  * One lane per occurrence (planes_edit_align; smart_amd/csrc/k_palign.hip): the recurrence of the edit calls in its DISTANCE
  * form over the reversed pattern, walking e, e-1, ...; with ops every column goes to LDS and the traceback reads cell values
  * back from the columns' bit vectors.
- * NOT offered: the longest start, all starts, all optimal alignments; m > 64, k > 7, affine costs, byte texts, a kernel that
- * finds and aligns in one pass.
+ * NOT offered: the longest start, all starts, all optimal alignments; m > 64, k > 7 (smartgpu_pfind_editl64 finds the ends of
+ * longer patterns; their alignments are not offered), affine costs, byte texts, a kernel that finds and aligns in one pass.
  * MEASURED on an MI355X, 1 Gi symbols of rand4 with planted copies of the pattern, about 1 Mi occurrences (7 Mi for m = 20,
  * k = 7, which rand4 holds by itself), every end of the find aligned, ms per call by the host clock, the list's copy to the
  * device and the results' copy back included (profiles/packed/RESULTS.md, "Edit distance: starts and alignments";
@@ -548,6 +548,52 @@ int smartgpu_palign_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smart
                            const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 int smartgpu_palign_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
                                 const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+/* EDIT DISTANCE, LONG PATTERNS: smartgpu_psearch_edit64 / smartgpu_pfind_edit64 and their sets forms for 1 <= m <=
+ * SMARTGPU_PEDITL_MAXM = 256 symbols and 0 <= k <= SMARTGPU_PEDITL_MAXK = 31 edits — a short read, an adapter followed by a
+ * barcode, a capture probe.  The contract is that of those calls, word for word, with only the bounds widened: D(e) is the
+ * last row of Sellers' programme on the range alone; an occurrence is an END position e with D(e) <= k; ends are ascending
+ * and relative to symbol 0, distances[i] = D(ends[i]); m > n is legal, only n + k < m is "count 0, no launch"; k >= m is
+ * legal; a foreign byte or an empty set accepts nothing, a full set everything; cap / count / SMARTGPU_ERR_NOMEM and
+ * distances == NULL behave the same, cap == 0 with NULL buffers is a count.  Lengths up to 64 are legal here too: the answers
+ * are those of the calls above, from a second, independent kernel.
+ * flags: 0, or SMARTGPU_PEDITL_ALL_BLOCKS (bit 0): compute every block of every column, without the cut-off described below.
+ * The answers are the same; the bit exists for the cross-check and the measurement.  Any other bit is SMARTGPU_ERR_ARG.
+ * One pass over the planes (planes_editl_scan, planes_editl_find; smart_amd/csrc/k_peditl.hip): the recurrence of the calls
+ * above in BLOCKS of 32 pattern rows with Ukkonen's cut-off — a block is stepped only while a value <= k can lie in it, so
+ * on DNA-like text a long pattern at a small k costs little more than its first block.  The number of active blocks is
+ * shared by the 64 lanes of a wave.  A lane owns 512 consecutive end positions and walks up to m + k <= 287 symbols before
+ * them without counting.  The find's entries are sorted on the host.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / sets == NULL, m = 0 or m > SMARTGPU_PEDITL_MAXM, k >
+ * SMARTGPU_PEDITL_MAXK (the messages name the limits), a flags bit other than SMARTGPU_PEDITL_ALL_BLOCKS, a NULL text, a
+ * range outside the text, count == NULL, ends == NULL with cap > 0, and — the sets calls — a set with a bit at or above the
+ * text's number of values (the message names the position).
+ * NOT offered: start positions and ALIGNMENTS of long patterns (smartgpu_palign_edit64 stays at m <= 64, k <= 7), m > 256,
+ * k > 31, affine or weighted costs, a batch call, byte texts.
+ * MEASURED on an MI355X, 1 Gi symbols, m = 64, 65, 100, 150, 256, k = 0, 3, 7, 15, 31, the pattern cut from the text
+ * (profiles/packed/RESULTS.md, "Edit distance: long patterns"; tools/editl_probe.py).  rand4, planes_editl_scan: 1.48-1.77 ms
+ * for m <= 100 at k <= 7 (0.60-0.72 T symbols/s), 2.13-2.22 ms at m = 150, 2.51-2.59 ms at m = 256 (one active block: the
+ * growth with m is the warm-up), 2.28-3.76 ms at k = 15 and 2.35-4.86 ms at k = 31 (two and three active blocks); per call
+ * 1.50-4.85 ms.  THE CUT-OFF'S WORTH: with SMARTGPU_PEDITL_ALL_BLOCKS the same cells take 2.07-9.66 ms; all blocks / cut-off is
+ * 3.6-3.7 at m = 256, k <= 7 (the CPU counts 1.00 of 8 blocks active), 2.0 at m = 256, k = 31, 1.36-1.40 at m = 64, k <= 7, outside
+ * the run-to-run spread in every cell; where every block is active anyway the cut-off form is the SLOWER one, by 3-7 % (m = 64
+ * at k = 15 and 31, m = 65 at k = 31: its votes and branches buy nothing there).  AGAINST smartgpu_psearch_edit64 at m = 64,
+ * k = 0, 3, 7, same pattern: 0.86-0.88 x its kernel time on rand4 (the longer run walks 1.13-1.14 symbols per owned one where
+ * that kernel walks 1.50-1.55).  rand2 (planes of Infinity-Cache size: possibly flattered): 1.24-5.27 ms with the cut-off,
+ * 1.61-7.18 ms with all blocks; 0.93 / 1.06 / 1.33 x smartgpu_psearch_edit64's kernel at m = 64, k = 0 / 3 / 7 — two values
+ * keep the second block active from k = 7 on.
+ * NOT measured: other run lengths, the occupancy, the number of active blocks on the device (the figures are the CPU's), the
+ * find form's speed and the host ordering's share in it, texts beyond 1 Gi symbols. */
+#define SMARTGPU_PEDITL_MAXM 256
+#define SMARTGPU_PEDITL_MAXK 31
+#define SMARTGPU_PEDITL_ALL_BLOCKS 1u   /* flags bit 0 */
+int smartgpu_psearch_editl64(const uint8_t *P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext *text,
+                             uint64_t off, uint64_t n, uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_pfind_editl64(const uint8_t *P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext *text,
+                           uint64_t off, uint64_t n, uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+int smartgpu_psearch_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext *text,
+                                  uint64_t off, uint64_t n, uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_pfind_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext *text,
+                                uint64_t off, uint64_t n, uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
 /* No device: the reverse complement of an IUPAC nucleotide pattern — a primer is searched on both strands.  P[0..m): the
  * letters smartgpu_iupac_sets accepts; out[j] = the complement of P[m-1-j]: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and
  * N stay; U reads as T (its complement is A; no U is ever written).  Case is preserved.  out has m bytes (no terminator is

@@ -26,6 +26,7 @@
 #include "kernels.hpp"
 #include "multi.hpp"
 #include "pedit.hpp"
+#include "peditl.hpp"
 #include "palign.hpp"
 #include "planes.hpp"
 #include "planes_host.hpp"
@@ -804,6 +805,9 @@ hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // mul
 // pedit.hpp: set by k_pedit.hip where that unit is linked
 hipError_t (*g_planes_edit_scan)(const PlaneEditArgs&, int, int, hipStream_t) = nullptr;
 hipError_t (*g_planes_edit_find)(const PlaneEditArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
+// peditl.hpp: set by k_peditl.hip where that unit is linked
+hipError_t (*g_planes_editl_scan)(const PlaneEditlArgs&, int, int, hipStream_t) = nullptr;
+hipError_t (*g_planes_editl_find)(const PlaneEditlArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
 // palign.hpp: set by k_palign.hip where that unit is linked
 hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
 }
@@ -2301,6 +2305,147 @@ int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
     return SMARTGPU_OK;
 }
 
+// ---- edit distance, long patterns (peditl.hpp): the contract of the calls above with m <= 256 and k <= 31, their own
+// kernels, and a switch that travels with the call ----
+
+// The checks of the four editl calls that need no device; `what` names the pattern argument.
+int check_peditl_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text,
+                      uint64_t off, uint64_t n, const uint64_t* count)
+{
+    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
+    if (m < 1 || m > SMARTGPU_PEDITL_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_PEDITL_MAXM); return SMARTGPU_ERR_ARG; }
+    if (k > SMARTGPU_PEDITL_MAXK) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PEDITL_MAXK); return SMARTGPU_ERR_ARG; }
+    if (flags & ~SMARTGPU_PEDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_PEDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_PEDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
+    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
+    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
+    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
+    return SMARTGPU_OK;
+}
+
+// edit_masks, eight dwords wide
+int editl_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, sg::PlaneEditlArgs* a)
+{
+    if (!sets) {
+        sg::editl_peq_pattern(t->values, t->nvalues, pat, m, a->peq);
+        return SMARTGPU_OK;
+    }
+    const int bad = sg::editl_peq_sets(t->nvalues, pat, m, a->peq);
+    if (bad < 0) return SMARTGPU_OK;
+    set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, pat[bad], t->nvalues);
+    return SMARTGPU_ERR_ARG;
+}
+
+void editl_head(sg::PlaneEditlArgs& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint32_t k, uint32_t flags, uint64_t off, uint64_t n)
+{
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.e_begin = off;
+    a.e_end = off + n;
+    a.m = m;
+    a.k = k;
+    a.all_blocks = flags & SMARTGPU_PEDITL_ALL_BLOCKS;
+    a.count = d->batch_counts;
+}
+
+// pedit_count with the long kernels
+int peditl_count(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off,
+                 uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
+{
+    int rc = check_peditl_args(call, sets ? "sets" : "P", pat, m, k, flags, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    sg::PlaneEditlArgs a;
+    if ((rc = editl_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
+    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
+    if (!sg::g_planes_editl_scan) { set_error("%s: this program holds no planes_editl_scan kernel (k_peditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const double t_pre = now_ms();
+    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
+    const double pre = now_ms() - t_pre;
+    const double t0 = now_ms();
+    editl_head(a, d, text, m, k, flags, off, n);
+    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(sg::g_planes_editl_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+    const double run = now_ms() - t0;
+    if (d->pinned_counts[0] > n) { set_error("planes_editl_scan: count %llu exceeds the %llu end positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)n); return SMARTGPU_ERR_HIP; }
+    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
+}
+
+// The entries of planes_editl_find, (e << kEditlShift) | D(e) in the order the waves' pieces reached the cursor: sorted,
+// then refused unless they are distinct end positions of [lo, hi] with distances <= k.
+bool order_editl(uint64_t* entries, uint64_t count, uint64_t lo, uint64_t hi, uint32_t k)
+{
+    std::sort(entries, entries + count);
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint64_t e = entries[i] >> sg::kEditlShift;
+        if (e < lo || e > hi || (entries[i] & ((1u << sg::kEditlShift) - 1u)) > k) return false;
+        if (i && e == entries[i - 1] >> sg::kEditlShift) return false;
+    }
+    return true;
+}
+
+// pedit_find with the long kernels; the entries are ordered by a sort (order_editl)
+int peditl_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off,
+                uint64_t n, uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
+    int rc = check_peditl_args(call, sets ? "sets" : "P", pat, m, k, flags, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    sg::PlaneEditlArgs a;
+    if ((rc = editl_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
+    if (n + k < m) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    if (!sg::g_planes_editl_find) { set_error("%s: this program holds no planes_editl_find kernel (k_peditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
+    editl_head(a, d, text, m, k, flags, off, n);
+    const uint64_t room = cap < n ? cap : n;  // no more entries than end positions
+    bool own = false;
+    unsigned long long* out = nullptr;
+    uint64_t room_got = room;
+    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
+    const bool ok = hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+                    sg::g_planes_editl_find(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
+                    hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+                    hipStreamSynchronize(d->stream) == hipSuccess;
+    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
+    int r = SMARTGPU_OK;
+    if (!ok) {
+        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        r = SMARTGPU_ERR_HIP;
+    } else if (total > n) {  // refused like a poisoned count, never reported
+        set_error("planes_editl_find: cursor %llu exceeds the %llu end positions", total, (unsigned long long)n);
+        r = SMARTGPU_ERR_HIP;
+    } else if (total && total <= room_got) {
+        if (!copy_positions(d, ends, out, total)) {
+            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+            r = SMARTGPU_ERR_HIP;
+        } else if (!order_editl(ends, total, off, off + n - 1, k)) {
+            set_error("planes_editl_find: the entries are not distinct end positions of the range with distances <= %u", k);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (own) (void)hipFree(out);
+    if (r != SMARTGPU_OK) return r;
+    *count = total;
+    if (total <= cap && total > room_got) {
+        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu entries", call, total, (unsigned long long)cap, (unsigned long long)room);
+        return SMARTGPU_ERR_NOMEM;
+    }
+    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    for (uint64_t i = 0; i < total; ++i) {
+        const uint64_t e = ends[i];
+        if (distances) distances[i] = static_cast<uint8_t>(e & ((1u << sg::kEditlShift) - 1u));
+        ends[i] = e >> sg::kEditlShift;
+    }
+    return SMARTGPU_OK;
+}
+
 // ---- starts and alignments of edit-distance occurrences (palign.hpp): a list of END positions in, one lane each ----
 
 // copy_positions the other way: the caller's (pageable) end positions to the device through the pinned staging buffer
@@ -2738,6 +2883,31 @@ int smartgpu_pfind_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, cons
                                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     return pedit_find("pfind_sets_edit64", sets, true, m, k, text, off, n, ends, distances, cap, count);
+}
+
+/* ---- edit distance, long patterns: m <= 256, k <= 31 (peditl.hpp, k_peditl.hip) ---------------------------------------- */
+int smartgpu_psearch_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                             uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return peditl_count("psearch_editl64", P, false, m, k, flags, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_pfind_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                           uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return peditl_find("pfind_editl64", P, false, m, k, flags, text, off, n, ends, distances, cap, count);
+}
+
+int smartgpu_psearch_sets_editl64(const uint8_t* sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                                  uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return peditl_count("psearch_sets_editl64", sets, true, m, k, flags, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_pfind_sets_editl64(const uint8_t* sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return peditl_find("pfind_sets_editl64", sets, true, m, k, flags, text, off, n, ends, distances, cap, count);
 }
 
 /* ---- edit distance: start positions and alignments of listed end positions (palign.hpp, k_palign.hip) ------------------ */

@@ -1,0 +1,39 @@
+// peditl_host.hpp — what the long-pattern edit-distance calls of api.cpp decide on the host before a launch: the pattern
+// as the masks Peq the recurrence of edit_block.hpp consumes — pedit_host.hpp's, eight dwords wide.  Host only: no HIP
+// call, no error text — tests/packed_editl_check.cpp runs it without a device.
+#pragma once
+#include "edit_block.hpp"
+
+#include <cstring>
+
+namespace sg {
+
+constexpr uint32_t kEditlMaxM = 256;                    // SMARTGPU_PEDITL_MAXM
+constexpr uint32_t kEditlMaxK = 31;                     // SMARTGPU_PEDITL_MAXK
+constexpr uint32_t kEditlWords = kEditlMaxM / 32;       // dwords of one mask
+
+// peq[c][j / 32] bit j % 32 = pattern position j accepts code c (edit_peq_pattern's rules: zero beyond m and for the
+// codes the text does not hold; a byte the text does not hold has its bit in NO mask).
+inline void editl_peq_pattern(const uint8_t values[4], int nvalues, const uint8_t* P, uint32_t m, uint32_t (&peq)[4][kEditlWords])
+{
+    std::memset(peq, 0, sizeof peq);
+    for (uint32_t j = 0; j < m; ++j)
+        for (int c = 0; c < nvalues; ++c)
+            if (values[c] == P[j]) peq[c][j >> 5] |= 1u << (j & 31);
+}
+
+// The same from sets (edit_peq_sets' rules).  Returns -1, or the first position whose set names a code >= nvalues (peq
+// is then unfinished).
+inline int editl_peq_sets(int nvalues, const uint8_t* sets, uint32_t m, uint32_t (&peq)[4][kEditlWords])
+{
+    const uint32_t all = (1u << nvalues) - 1u;
+    std::memset(peq, 0, sizeof peq);
+    for (uint32_t j = 0; j < m; ++j) {
+        if (sets[j] & ~all) return static_cast<int>(j);
+        for (uint32_t c = 0; c < 4; ++c)
+            if (sets[j] >> c & 1u) peq[c][j >> 5] |= 1u << (j & 31);
+    }
+    return -1;
+}
+
+}  // namespace sg

@@ -134,6 +134,10 @@ def _load(path):
         "smartgpu_pfind_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_psearch_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_pfind_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_psearch_sets_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_pfind_sets_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_palign_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_palign_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
@@ -605,6 +609,28 @@ def psearch_sets_edit(sets, ptext, k, off=0, n=None):
 def pfind_sets_edit(sets, ptext, k, off=0, n=None, cap=1 << 20):
     """(ends, distances, count) of a SET pattern within edit distance k (psearch_sets_edit), as pfind_edit returns them."""
     return _pfind("pfind_sets_edit64", sets, ptext, off, n, cap, k)
+
+
+def psearch_editl(P, ptext, k, off=0, n=None, all_blocks=False):
+    """psearch_edit for LONG patterns: 1 <= len(P) <= 256, 0 <= k <= 31 (smartgpu_psearch_editl64; Myers' recurrence in blocks
+    of 32 rows with Ukkonen's cut-off).  all_blocks=True computes every block of every column (SMARTGPU_PEDITL_ALL_BLOCKS): the
+    same answer, for cross-checks and measurements."""
+    return _pcount("psearch_editl64", P, ptext, off, n, k, int(bool(all_blocks)))
+
+
+def pfind_editl(P, ptext, k, off=0, n=None, cap=1 << 20, all_blocks=False):
+    """(ends, distances, count) as pfind_edit returns them, for LONG patterns (psearch_editl; smartgpu_pfind_editl64)."""
+    return _pfind("pfind_editl64", P, ptext, off, n, cap, k, int(bool(all_blocks)))
+
+
+def psearch_sets_editl(sets, ptext, k, off=0, n=None, all_blocks=False):
+    """psearch_editl for a SET pattern (psearch_sets_edit; smartgpu_psearch_sets_editl64)."""
+    return _pcount("psearch_sets_editl64", sets, ptext, off, n, k, int(bool(all_blocks)))
+
+
+def pfind_sets_editl(sets, ptext, k, off=0, n=None, cap=1 << 20, all_blocks=False):
+    """(ends, distances, count) of a SET pattern within edit distance k, for LONG patterns (smartgpu_pfind_sets_editl64)."""
+    return _pfind("pfind_sets_editl64", sets, ptext, off, n, cap, k, int(bool(all_blocks)))
 
 
 def _palign(name, pat, ptext, k, ends, off, n, ops):

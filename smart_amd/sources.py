@@ -22,6 +22,7 @@ UNITS = {
     "k_util": ("k_util.hip",),
     "k_planes": ("k_planes.hip", "planes.hpp"),
     "k_pedit": ("k_pedit.hip", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_peditl": ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_palign": ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {
@@ -33,6 +34,7 @@ KERNEL_UNIT = {
     "planes_mis_scan": "k_planes", "planes_mis_find": "k_planes",
     "planes_sets_mis_scan": "k_planes", "planes_sets_mis_find": "k_planes",
     "planes_edit_scan": "k_pedit", "planes_edit_find": "k_pedit",
+    "planes_editl_scan": "k_peditl", "planes_editl_find": "k_peditl",
     "planes_edit_align": "k_palign",
 }
 
