@@ -1,6 +1,7 @@
 """Starts and alignments of edit-distance occurrences on the GPU (planes_edit_align): starts, distances and operations
 against the DEFINITION — the plain DP of tests/test_packed_align.py (align_many, held there to the cell-by-cell align_one).
-Every comparison is exact equality; no text is longer than 2^20 + 3 symbols, so positions beyond 2^32 are not exercised."""
+Every comparison is exact equality; no text here is longer than 2^20 + 3 symbols — ends beyond 2^32 are in
+tests/test_packed_at_size_gpu.py."""
 import numpy as np
 import pytest
 

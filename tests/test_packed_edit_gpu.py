@@ -1,6 +1,7 @@
 """Occurrences within edit distance k on packed texts on the GPU (planes_edit_scan, planes_edit_find): counts, end positions
 and distances against the DEFINITION — Sellers' DP on the range, computed row by row with numpy (tests/test_packed_edit.py,
-where it is checked against the plain DP).  Every comparison is exact equality; no text is longer than 2^20 + 3 symbols."""
+where it is checked against the plain DP).  Every comparison is exact equality; no text here is longer than 2^20 + 3 symbols — later trips of the grid-stride
+loop and positions beyond 2^32 are in tests/test_packed_at_size_gpu.py."""
 import ctypes
 
 import numpy as np
