@@ -282,8 +282,15 @@ int smartgpu_tune(int key, int value);
 
 /* How many queued smartgpu_plan_launch() calls share one pass over the text: 0 = none (every launch is sent at
  * once), 2..8.  Returns the previous value, SMARTGPU_ERR_ARG for anything else.  Needs no device; what is pending
- * is sent first. */
+ * is sent first.  This is the narrow view of the setting of smartgpu_coalesce_wide(): a previous value above 8 is
+ * returned as 8. */
 int smartgpu_coalesce(int max_group);
+/* The same setting over its whole range: 0 or 2..32, the most patterns one hor_multi_scan takes.  Returns the previous
+ * value as it was, SMARTGPU_ERR_ARG for anything else.  The library starts with 32: on 1 GiB of rand128 at m = 32 a
+ * pass of 32 takes 0.19 ms against 0.16 ms for a pass of eight or a solo scan, 0.0060 ms per pattern against 0.0203 and
+ * 0.156, and it is the fastest width at m = 16, 64 and 256 too (profiles/coalesce/RESULTS.md).  A key's first pass is
+ * sent once that many launches have gathered or at the next call that sends what is pending, whichever comes first. */
+int smartgpu_coalesce_wide(int max_group);
 /* Of the launches on `device` that could share a pass: how many were seen, and how many kernels were sent for them
  * (equal when nothing was coalesced).  Either pointer may be NULL. */
 int smartgpu_coalesce_stats(int device, uint64_t *launches, uint64_t *passes);

@@ -661,8 +661,8 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // A streaming Horspool scan runs at the rate the text can be read, so what is left to save lies BETWEEN searches: K plans
 // launched over the same text read it K times.  smartgpu_plan_launch therefore does not send a launch that would reach
 // launch_hor's streaming branch (route {hor, 0}, a sparse pattern); it queues the finished arguments per device under
-// (text, range, m, halo).  A key that has collected g_coalesce launches is sent at once as ONE hor_multi_scan — the GPU
-// never waits for a flush while full groups exist, and at most g_coalesce - 1 launches per key are ever pending.  Every
+// (text, range, m, halo).  A key that has collected g_coalesce launches (at most kMultiMax = 32) is sent at once as ONE
+// hor_multi_scan — the GPU never waits for a flush while full groups exist, and at most g_coalesce - 1 launches per key are ever pending.  Every
 // entry point that waits for, times, orders work on, or frees what is on the device's stream sends what is pending
 // first (flush_queue), in arrival order; a launch that is alone by then goes through launch_scan as it always did.
 // An untimed launch that cannot share a pass (another algorithm, a pattern whose symbols repeat) is no such entry point:
@@ -686,8 +686,13 @@ struct LaunchQueue {
     uint64_t launches = 0, passes = 0;  // eligible launches seen / kernels sent for them
 };
 LaunchQueue g_queue[kMaxDevices];
-// launches per pass: 0 = off.  8, the most a pass takes: per pattern, 0.080 / 0.040 / 0.0207 ms in groups of 2 / 4 / 8 (profiles/coalesce/RESULTS.md)
-std::atomic<int> g_coalesce{8};
+// launches per pass: 0 = off, 2..kMultiMax.  ONE number with two calls: smartgpu_coalesce, the first, sets 0 or
+// 2..kCoalesceNarrow and reports a wider value as kCoalesceNarrow; smartgpu_coalesce_wide sets and reports all of it.
+// The default is the widest pass: per pattern on 1 GiB of rand128 at m = 32, 0.0203 / 0.0105 / 0.0072 / 0.0060 ms in
+// passes of 8 / 16 / 24 / 32, and 32 is the fastest at m = 16, 64 and 256 as well (profiles/coalesce/RESULTS.md), so no
+// length gets a cap of its own.
+constexpr int kCoalesceNarrow = 8;
+std::atomic<int> g_coalesce{32};
 
 // send one key's launches (q.mu held, the device current)
 hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
@@ -1134,11 +1139,23 @@ int smartgpu_tune(int key, int value)
     return SMARTGPU_OK;
 }
 
-int smartgpu_coalesce(int max_group)
+// the one setting behind smartgpu_coalesce (most = kCoalesceNarrow) and smartgpu_coalesce_wide (most = kMultiMax)
+static int set_coalesce(int max_group, int most)
 {
-    if (max_group != 0 && (max_group < 2 || max_group > sg::kMultiMax)) { set_error("coalesce: a pass takes 2..%d launches (0: off), not %d", sg::kMultiMax, max_group); return SMARTGPU_ERR_ARG; }
+    if (max_group != 0 && (max_group < 2 || max_group > most)) { set_error("coalesce: a pass takes 2..%d launches (0: off), not %d", most, max_group); return SMARTGPU_ERR_ARG; }
     flush_all_queues();
     return g_coalesce.exchange(max_group);
+}
+
+int smartgpu_coalesce(int max_group)
+{
+    const int prev = set_coalesce(max_group, kCoalesceNarrow);
+    return prev > kCoalesceNarrow ? kCoalesceNarrow : prev;
+}
+
+int smartgpu_coalesce_wide(int max_group)
+{
+    return set_coalesce(max_group, sg::kMultiMax);
 }
 
 int smartgpu_coalesce_stats(int device, uint64_t* launches, uint64_t* passes)

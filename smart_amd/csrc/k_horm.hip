@@ -1,4 +1,4 @@
-// k_horm.hip — hor_multi_scan: Horspool (and Tuned BM) on hor_scan's LDS tiles for up to eight patterns of one length
+// k_horm.hip — hor_multi_scan: Horspool (and Tuned BM) on hor_scan's LDS tiles for up to 32 patterns of one length
 // in ONE pass over the text (a translation unit of its own: dev_common.hpp says why)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
@@ -10,22 +10,29 @@ namespace sg {
 // hor_scan<.., VAR 0> (k_hor.hip) with the tile staged ONCE for np <= NP patterns: searches of one text that are queued
 // together (api.cpp) share the fetch and HBM bytes per pattern fall by np.  Same tiles on absolute offsets indexed by
 // window end, same back halo, same prefetch one tile ahead, same swizzle, same range clamps.
-// LDS: u64 blob[8] | u64 count[8] | u64 hits[8] | u32 gram[kGramSlots] | np x pattern tail P[m-1-H..m-1] | text [tile0-H16, tile0+TB)
+// LDS: u64 blob[32] | u64 count[32] | u64 hits[32] | u32 gram[kGramSlots] | np x pattern tail P[m-1-H..m-1] | text [tile0-H16, tile0+TB)
 // The walk: a Horspool walk per pattern asks np times, one pattern at a time, whether a pattern ends near a window end,
 // and np such walks of a staged tile cost more than its fetch.  ONE walk per lane asks it for all patterns at once:
 // the workgroup builds, in its prologue, the skip table of multi.hpp — indexed by the window's last two bytes, the
-// least shift any pattern of the pass allows and the patterns whose last gram falls into the slot (LDS atomics: min for
-// the shifts, a barrier, or for the pattern bits and the tag of the last gram).  np x (m - 2) grams hardly fill
+// least shift any pattern of the pass allows and the CLASSES of the patterns whose last gram falls into the slot (LDS
+// atomics: min for the shifts, a barrier, or for the class bits and the tag of the last gram).  An entry has eight
+// class bits and a pass up to kMultiMax = 32 patterns: pattern g is of class g & 7, and a window whose entry passes the
+// tag test is compared with the patterns c, c + 8, c + 16, c + 24 below np of every class c that is set.  A gram hit is
+// rare (about np / 16384 per step on rand128) and a class mate that is not the pattern dies on its first byte; counts
+// stay exact because every compare is a whole one.  A pass of at most eight has one pattern per class: nothing changes.
+// np x (m - 2) grams hardly fill
 // kGramSlots slots, so nearly every step moves the window end by m - 1 and a lane leaves its 64-byte segment after
 // about 64 / (m - 1) steps whatever np is.  A step: two byte reads (tile_at permutes dwords, the two bytes of a gram
-// may lie in different ones), the slot, the entry; compare for every pattern bit, but only where the entry's tag
+// may lie in different ones), the slot, the entry; compare for every pattern of every class bit, but only where the entry's tag
 // says that the window ends in a pattern's last gram and not merely in its slot; add the shift.
 // The prologue reads no pattern from memory: the bytes the table and the tails are made of, at most 65 per pattern,
 // come BY VALUE in the rows of MultiArgs (multi.hpp), each thread reads its few of them from the arguments first, and
 // the first tile is asked for before the table is built — measured, a pass of eight fell from 167-170 us to 164-165 us
 // against a solo hor_scan's 156 us (1 GiB rand128, m = 32; profiles/coalesce/RESULTS.md); the tag took it to 162-163.
-// The pointer arrays of MultiArgs are indexed with compile-time constants only, once, in the prologue that copies them
-// to LDS (a run-time index into them makes the compiler select between addresses and load through flat_load);
+// The arguments are 3112 bytes at 32 patterns, with tile_first and ntiles 3124 of the 4096 a kernel may take
+// (multi.hpp asserts it).  The pointer arrays of MultiArgs are read once, in the prologue: thread g < np takes blob[g]
+// and count[g] from the argument segment AS NUMBERS and writes them to LDS — one thread filling all 32 would unroll
+// into 64 selects, and a pointer picked by a run-time index and then dereferenced is loaded through flat_load;
 // a pattern's pointer — needed only to complete a window in memory — is read from LDS as a number and cast to GLOBAL
 // memory.  The kernel is as long as hor_scan
 // whatever NP is, so NP, the most patterns a pass can take, is instantiated once, at kMultiMax, and completion in
@@ -84,7 +91,7 @@ template <int THREADS, int L, int NP>
 __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t tile_first, uint32_t ntiles)
 {
     constexpr int TB = THREADS * L;
-    static_assert(NP <= kMultiMax && NP <= 8, "a pattern bit per pattern in an entry's byte 2");
+    static_assert(NP == kMultiMax && NP <= 4 * (int)kGramClasses && NP <= THREADS, "a class bit in an entry's byte 2 stands for at most four patterns");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t m = a.m, H = a.halo, H16 = round16(H), np = a.np;
     const bool in_memory = m - 1 > H;  // windows are completed in HBM
@@ -100,27 +107,44 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
     // arguments' plus an index of the thread's, so no read waits for another.  Loads come back in the order they
     // were sent, so these go out in front of the tile's and the table is built while the tile is on the way.  A thread
     // with nothing to take reads a byte that exists all the same (m >= 3): no branch, no wait between the reads.
+    // The rounds beyond a pass of eight stand behind a test of np, the same for the whole workgroup: a pass of at most
+    // eight sends the reads of its own patterns only.
     constexpr uint32_t kTslotMax = (kHaloMax + 16u) & ~15u;                // the longest tail, rounded: 32
-    constexpr uint32_t kShiftRounds = kMultiMax * kGramCap / THREADS;      // 2
-    static_assert(kMultiMax * kTslotMax <= THREADS && kShiftRounds * THREADS == kMultiMax * kGramCap, "a tail byte and kShiftRounds grams per thread");
-    // tails: thread x takes byte x % 32 of pattern x / 32: ptail[j] = P[m-1-H+j], j <= H
-    const uint32_t tail_g = threadIdx.x / kTslotMax, tail_j = threadIdx.x % kTslotMax;
-    const bool tail_mine = tail_g < np && tail_j <= H;
-    const uint32_t tail_byte = tail_at(a.tail[tail_mine ? tail_g : 0u], m, m - 1 - (tail_mine ? H - tail_j : 0u));
-    // shifts: in round r thread x takes position gram_first(m) + x % kGramCap of pattern (x + r * THREADS) / kGramCap
-    // (at most kGramCap - 1 positions of a pattern shift by less than the default)
+    constexpr uint32_t kTailPer = THREADS / kTslotMax;                     // 8 patterns' tails in a round
+    constexpr uint32_t kTailRounds = kMultiMax / kTailPer;                 // 4
+    constexpr uint32_t kShiftPer = THREADS / kGramCap;                     // 4 patterns' grams in a round
+    constexpr uint32_t kShiftRounds = kMultiMax / kShiftPer;               // 8
+    static_assert(kTailRounds * kTailPer == kMultiMax && kShiftRounds * kShiftPer == kMultiMax && kTailPer * kTslotMax == THREADS && kShiftPer * kGramCap == THREADS,
+                  "kTailRounds tail bytes and kShiftRounds grams per thread");
+    // tails: in round r thread x takes byte x % 32 of pattern x / 32 + 8 r: ptail[j] = P[m-1-H+j], j <= H
+    const uint32_t tail_j = threadIdx.x % kTslotMax;
+    uint32_t tail_byte[kTailRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kTailRounds; ++r) {
+        tail_byte[r] = 0;
+        if (r == 0 || np > r * kTailPer) {
+            const uint32_t g = threadIdx.x / kTslotMax + r * kTailPer;
+            const bool mine = g < np && tail_j <= H;
+            tail_byte[r] = tail_at(a.tail[mine ? g : 0u], m, m - 1 - (mine ? H - tail_j : 0u));
+        }
+    }
+    // shifts: in round r thread x takes the gram at position gram_first(m) + x % kGramCap of pattern x / kGramCap + 4 r,
+    // both bytes in one read (at most kGramCap - 1 positions of a pattern shift by less than the default)
     const uint32_t shift_i = gram_first(m) + threadIdx.x % kGramCap;
     const bool shift_mine = shift_i + 3 <= m;
-    uint32_t shift_prev[kShiftRounds], shift_last[kShiftRounds];
+    uint32_t shift_gram[kShiftRounds];
 #pragma unroll
     for (uint32_t r = 0; r < kShiftRounds; ++r) {
-        const uint32_t g = (threadIdx.x + r * THREADS) / kGramCap, i = shift_mine ? shift_i : gram_first(m);
-        shift_prev[r] = tail_at(a.tail[g < np ? g : 0u], m, i);
-        shift_last[r] = tail_at(a.tail[g < np ? g : 0u], m, i + 1);
+        shift_gram[r] = 0;
+        if (r * kShiftPer < 8 || np > r * kShiftPer) {
+            const uint32_t g = threadIdx.x / kGramCap + r * kShiftPer;
+            shift_gram[r] = tail_gram_at(a.tail[g < np ? g : 0u], m, shift_mine ? shift_i : gram_first(m));
+        }
     }
-    // pattern bits: thread g < np takes pattern g's last gram
+    // class bits: thread g < np takes pattern g's last gram — and its blob and its result slot, as numbers
     const uint32_t bit_g = threadIdx.x < np ? threadIdx.x : 0u;
-    const uint32_t bit_prev = tail_at(a.tail[bit_g], m, m - 2), bit_last = tail_at(a.tail[bit_g], m, m - 1);
+    const uint32_t bit_gram = tail_gram_at(a.tail[bit_g], m, m - 2);
+    const unsigned long long head_blob = (unsigned long long)a.blob[bit_g], head_count = (unsigned long long)a.count[bit_g];
 
     const uint64_t e_begin = a.s_begin + m - 1, e_end = a.s_end + m - 1;
     const uint64_t t_end = tile_first + ntiles;
@@ -139,23 +163,24 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
     issue(t * TB);  // (the launcher starts no more workgroups than there are tiles)
 
     // the table and the tails, in LDS: the default, a barrier, the least shift per slot, a barrier, the pattern bits
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            blobs[i] = (uint32_t)i < np ? (unsigned long long)a.blob[i] : 0ull;
-            counts[i] = (uint32_t)i < np ? (unsigned long long)a.count[i] : 0ull;
-            sums[i] = 0;
-        }
+    if (threadIdx.x < (uint32_t)NP) {
+        blobs[threadIdx.x] = threadIdx.x < np ? head_blob : 0ull;
+        counts[threadIdx.x] = threadIdx.x < np ? head_count : 0ull;
+        sums[threadIdx.x] = 0;
     }
     const uint32_t dflt = gram_default(m);
     for (uint32_t j = threadIdx.x; j < kGramSlots; j += THREADS) gram[j] = dflt;
-    if (tail_mine) tails[tail_g * tslot + tail_j] = (uint8_t)tail_byte;
+#pragma unroll
+    for (uint32_t r = 0; r < kTailRounds; ++r) {
+        const uint32_t g = threadIdx.x / kTslotMax + r * kTailPer;
+        if (g < np && tail_j <= H) tails[g * tslot + tail_j] = (uint8_t)tail_byte[r];
+    }
     __syncthreads();
 #pragma unroll
     for (uint32_t r = 0; r < kShiftRounds; ++r)
-        if ((threadIdx.x + r * THREADS) / kGramCap < np && shift_mine) atomicMin(gram + gram_slot(shift_prev[r], shift_last[r]), gram_shift(m, shift_i));
-    __syncthreads();  // every shift is in before a pattern bit makes an entry larger
-    if (threadIdx.x < np) atomicOr(gram + gram_slot(bit_prev, bit_last), gram_entry_pattern_bit(threadIdx.x) | gram_entry_tag(bit_prev));
+        if (threadIdx.x / kGramCap + r * kShiftPer < np && shift_mine) atomicMin(gram + gram_slot(shift_gram[r] & 0xFFu, shift_gram[r] >> 8), gram_shift(m, shift_i));
+    __syncthreads();  // every shift is in before a class bit makes an entry larger
+    if (threadIdx.x < np) atomicOr(gram + gram_slot(bit_gram & 0xFFu, bit_gram >> 8), gram_entry_class_bit(threadIdx.x) | gram_entry_tag(bit_gram & 0xFFu));
     // (the loop's first barrier stands between these bits and the first walk)
 
     for (; t < t_end; t += gridDim.x) {
@@ -185,24 +210,26 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
         for (uint32_t e = e0; e < ehi;) {
             const uint32_t prev = txt[tile_at(e - 1)], last = txt[tile_at(e)];  // e >= H16 >= 16: e - 1 is in the halo at least
             const uint32_t ent = gram[gram_slot(prev, last)];
-            for (uint32_t cand = gram_entry_hit(ent, prev); cand != 0; cand &= cand - 1) {  // (a slot hit that is no gram hit: no compare)
-                const uint32_t g = __builtin_ctz(cand);
-                const uint8_t* ptail = tails + g * tslot;
-                uint32_t k = 0;  // bytes matched so far, right to left (the slot promises none of them)
-                while (k <= H && ptail[H - k] == txt[tile_at(e - k)]) ++k;
-                bool ok = k == H + 1;
-                if (in_memory && ok) {  // the rest of the window is not in LDS
-                    const uint8_t* rest = a.text + tile0 + (e - H16) - (m - 1);
-                    if (!parked) {
-                        parked = true;
-                        parked_at = rest;
-                        parked_g = g;
-                        ok = false;  // counted after the loop
-                    } else {
-                        ok = global_equal(rest, horm_global(blobs[g]), m - 1 - H);
+            for (uint32_t cls = gram_entry_hit(ent, prev); cls != 0; cls &= cls - 1) {  // (a slot hit that is no gram hit: no compare)
+                // the class's patterns below np: a mate that is not the pattern dies on its first byte, almost always
+                for (uint32_t g = __builtin_ctz(cls); g < np; g += kGramClasses) {
+                    const uint8_t* ptail = tails + g * tslot;
+                    uint32_t k = 0;  // bytes matched so far, right to left (the slot promises none of them)
+                    while (k <= H && ptail[H - k] == txt[tile_at(e - k)]) ++k;
+                    bool ok = k == H + 1;
+                    if (in_memory && ok) {  // the rest of the window is not in LDS
+                        const uint8_t* rest = a.text + tile0 + (e - H16) - (m - 1);
+                        if (!parked) {
+                            parked = true;
+                            parked_at = rest;
+                            parked_g = g;
+                            ok = false;  // counted after the loop
+                        } else {
+                            ok = global_equal(rest, horm_global(blobs[g]), m - 1 - H);
+                        }
                     }
+                    if (ok) atomicAdd(sums + g, 1ull);
                 }
-                if (ok) atomicAdd(sums + g, 1ull);
             }
             e += gram_entry_shift(ent);
         }
@@ -220,9 +247,11 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
 // ---------------------------------------------------------------------------
 // launcher: the grid and the tile's LDS as launch_hor's streaming branch, plus the skip table and the tails of np patterns
 // ---------------------------------------------------------------------------
-// Workgroups per CU.  A workgroup takes 24.5 KB of LDS and 60 VGPRs, so six could be resident, but the longer walk does
-// not want them: swept on 1 GiB of rand128 at m = 16, 32, 256 in groups of 2, 4, 8, FOUR wins at m = 32 (8 patterns:
-// 0.0207 ms per pattern with 4, 0.0215 with 5, 0.0214 with 6, 0.0222 with 7) and loses nowhere — the solo kernels' value.
+// Workgroups per CU.  A workgroup takes up to 33.8 KB of LDS (the table 16 KB of it) and 62 VGPRs, so four are resident
+// at most — and with the table of 2048 slots, where six were, FOUR won: swept on 1 GiB of rand128 at m = 16, 32, 256 in
+// groups of 2, 4, 8 (8 patterns, m = 32: 0.0207 ms per pattern with 4, 0.0215 with 5, 0.0214 with 6, 0.0222 with 7), and
+// at m = 16, 32, 64, 256 in groups of 8 to 32, where 5 won a pass of 32 at m = 32 alone (0.0059 against 0.0063) and lost
+// at the other lengths by 2 - 5 % (profiles/coalesce/RESULTS.md) — the solo kernels' value.
 static int horm_wgs(uint32_t m)
 {
     ScanArgs one = {};

@@ -7,7 +7,7 @@
 
 namespace sg {
 
-constexpr int kMultiMax = 8;  // patterns per pass
+constexpr int kMultiMax = 32;  // patterns per pass: four to each of the eight class bits of a skip-table entry (below)
 
 // The end of a pattern as a launch carries it BY VALUE: the bytes from position gram_first(m) (below) to m - 1 — every
 // gram the skip table enters and the at most 17 bytes a lane compares in LDS — at the front of a row, zeros behind
@@ -30,15 +30,23 @@ struct MultiArgs {
     unsigned long long* count[kMultiMax];
     uint8_t tail[kMultiMax][kTailRow];
 };
+// the kernel takes MultiArgs and two more arguments, a u64 and a u32, by value: HIP passes at most 4096 bytes
+static_assert(sizeof(MultiArgs) + 8 + 4 <= 4096, "MultiArgs, tile_first and ntiles fit the kernel argument segment");
 
 // The skip table that the patterns of a pass share (Wu-Manber, blocks of two bytes): one entry per slot, indexed by the
 // LAST TWO bytes of a window.  Low half: how far the window end may move — the least m-2-i over every pattern P of the
 // pass and every position i <= m-3 whose gram (P[i], P[i+1]) falls into the slot; m-1 where no gram does (the next
-// window may still overlap this one by its last byte).  High half: bit g for every pattern g whose LAST gram
-// (P[m-2], P[m-1]) falls into the slot — the windows that are compared.  Grams that collide in a slot only lower a
-// shift or add a comparison, so any slot function counts right.  The rule is written once, for the kernel and for
+// window may still overlap this one by its last byte).  High half: bit g & 7 — the CLASS of pattern g — for every
+// pattern g whose LAST gram (P[m-2], P[m-1]) falls into the slot: a window that ends in such a slot is compared with
+// the patterns c, c + 8, c + 16, c + 24 below np of every class c whose bit is set.  A pass of at most eight has one
+// pattern per class, and the bit names the pattern.  Grams that collide in a slot, and class mates that are not the
+// pattern, only lower a shift or add a comparison (every comparison is a whole one), so any slot function counts right.  The rule is written once, for the kernel and for
 // the host program that checks it (tests/coalesce_gram_check.cpp).
-constexpr uint32_t kGramSlots = 2048;  // 8 KB of LDS: with the tile and the tails, five workgroups per CU stay below 160 KB
+// 16 KB of LDS: with the tile and the tails of 32 patterns a workgroup takes 33.8 KB, and the four per CU that the pass
+// runs with (k_horm.hip: horm_wgs) stay below 160 KB.  32 patterns of m = 32 enter 37 % of 2048 slots and 20 % of 4096:
+// measured per pattern in a pass of 32, 0.0060 ms against 0.0063 at m = 32 and no slower at m = 16, 64, 256 or in a
+// pass of eight (profiles/coalesce/RESULTS.md, "Up to 32 patterns in a pass")
+constexpr uint32_t kGramSlots = 4096;
 constexpr uint32_t kGramCap = 64;      // a lane owns 64 window ends: a longer shift leaves its segment just the same
 
 // the slot of the gram (prev, last).  Injective for alphabets up to 37 symbols; byte pairs spread over all slots
@@ -49,10 +57,12 @@ __host__ __device__ inline uint32_t gram_default(uint32_t m) { return m - 1u < k
 __host__ __device__ inline uint32_t gram_shift(uint32_t m, uint32_t i) { return m - 2u - i; }
 // the first position whose gram is entered: those before it allow gram_default(m) or more
 __host__ __device__ inline uint32_t gram_first(uint32_t m) { return m - 1u > kGramCap ? m - 1u - kGramCap : 0u; }
-// an entry's parts: the shift in byte 0 (at most kGramCap), the pattern bits in byte 2
+// an entry's parts: the shift in byte 0 (at most kGramCap), the class bits in byte 2
 __host__ __device__ inline uint32_t gram_entry_shift(uint32_t ent) { return ent & 0xFFu; }
 __host__ __device__ inline uint32_t gram_entry_patterns(uint32_t ent) { return (ent >> 16) & 0xFFu; }
-__host__ __device__ inline uint32_t gram_entry_pattern_bit(uint32_t g) { return 0x10000u << g; }
+__host__ __device__ inline uint32_t gram_entry_pattern_bit(uint32_t g) { return 0x10000u << g; }  // g < 8
+__host__ __device__ inline uint32_t gram_entry_class_bit(uint32_t g) { return gram_entry_pattern_bit(g & 7u); }  // g < kMultiMax
+constexpr uint32_t kGramClasses = 8;  // the patterns of class c: c, c + kGramClasses, ... below np
 // Bytes 1 and 3 tell a slot hit from a gram hit without a compare: a pattern ORs gram_entry_tag(P[m-2]) into its slot
 // with its bit — `prev` in byte 1, its complement in byte 3 — and a window whose last two bytes fall into the slot is
 // compared only if every bit of ITS tag is there.  Slot and prev determine last (the slot is 37 prev + last mod
@@ -72,6 +82,14 @@ __host__ __device__ inline void tail_fill(uint8_t* row, const uint8_t* P, uint32
     for (uint32_t j = 0; j < kTailRow; ++j) row[j] = j < n ? P[first + j] : (uint8_t)0;
 }
 __host__ __device__ inline uint32_t tail_at(const uint8_t* row, uint32_t m, uint32_t i) { return row[(int32_t)i - (int32_t)gram_first(m)]; }
+// the gram at pattern positions i and i + 1 in ONE read of two bytes (they are neighbours in the row, at any
+// alignment): position i in the low byte.  gram_first(m) <= i <= m - 2
+__host__ __device__ inline uint32_t tail_gram_at(const uint8_t* row, uint32_t m, uint32_t i)
+{
+    uint16_t two;
+    __builtin_memcpy(&two, row + ((int32_t)i - (int32_t)gram_first(m)), 2);
+    return two;
+}
 
 // The launcher of k_horm.hip, reached through a pointer that the unit's own static initialiser sets: api.cpp holds
 // the pointer (null: no launch is ever queued), so a program that includes api.cpp without k_horm.hip still links.

@@ -97,6 +97,7 @@ def _load(path):
         "smartgpu_stream_handle": (vp, [i32]),
         "smartgpu_tune": (i32, [i32, i32]),
         "smartgpu_coalesce": (i32, [i32]),
+        "smartgpu_coalesce_wide": (i32, [i32]),
         "smartgpu_coalesce_stats": (i32, [i32, C.POINTER(u64), C.POINTER(u64)]),
         "smartgpu_mtext_upload": (vp, [vp, u64, i32, vp]),
         "smartgpu_mtext_generate": (vp, [u64, i32, u64, i32, vp]),
@@ -809,8 +810,17 @@ def tune(key, value):
 
 
 def coalesce(max_group):
-    """How many queued Plan.launch calls share one pass over the text (0: none, 2..8); returns the previous value."""
+    """How many queued Plan.launch calls share one pass over the text (0: none, 2..8); returns the previous value,
+    a wider one (coalesce_wide) as 8."""
     prev = lib().smartgpu_coalesce(max_group)
+    if prev < 0:
+        raise _err("coalesce")
+    return prev
+
+
+def coalesce_wide(max_group):
+    """coalesce() over the setting's whole range (0: none, 2..32); returns the previous value as it was."""
+    prev = lib().smartgpu_coalesce_wide(max_group)
     if prev < 0:
         raise _err("coalesce")
     return prev

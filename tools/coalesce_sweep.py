@@ -7,6 +7,8 @@
 Per cell: --plans Horspool plans (patterns cut from the text at bench.py's seeded offsets) are launched between two HIP
 events on the launch stream, --rounds times; the cell is the median round in ms per pattern, with the best and the worst.
 group 0 = smartgpu_coalesce(0): every launch a hor_scan of its own; wgs 0 = the library's default (smartgpu_tune(4, 0)).
+Groups above 8 go through smartgpu_coalesce_wide (a library without it skips them); give --plans a multiple of every
+group, 96 for 8, 16, 24 and 32, or the last pass of a round is a partial one.
 One line per cell, and all cells as JSON in --out.  Every count is compared with the group-0 count of the same pattern."""
 import argparse
 import json
@@ -46,7 +48,9 @@ def main():
     n = int(args.gib * (1 << 30))
     text = Text.generate(SEED, args.sigma, n)
     engine.probe_read_gbs(text, reps=64)  # clocks
-    default_group = engine.coalesce(8)
+    wide = hasattr(engine.lib(), "smartgpu_coalesce_wide")
+    set_group = engine.coalesce_wide if wide else engine.coalesce
+    default_group = set_group(8)
     cells = []
     print("library %s, default group %d" % (engine.LIB_PATH, default_group))
     for m in ints(args.ms):
@@ -63,7 +67,9 @@ def main():
             for wgs in ints(args.wgs):
                 if group == 0 and wgs != 0:
                     continue  # tune key 4 is the shared pass's
-                engine.coalesce(group)
+                if group > 8 and not wide:
+                    continue
+                set_group(group)
                 engine.tune(4, wgs)
                 for pl in plans:
                     pl.reset()
@@ -83,12 +89,12 @@ def main():
                 cell = {"m": m, "group": group, "wgs": wgs, "ms": round(rounds[len(rounds) // 2], 5), "best": round(rounds[0], 5),
                         "worst": round(rounds[-1], 5), "count_ok": ok}
                 cells.append(cell)
-                print("m %-4d group %d wgs %d  %.5f ms per pattern (best %.5f worst %.5f)  %s"
+                print("m %-4d group %-2d wgs %d  %.5f ms per pattern (best %.5f worst %.5f)  %s"
                       % (m, group, wgs, cell["ms"], cell["best"], cell["worst"], "ok" if ok else "COUNT MISMATCH"), flush=True)
         for pl in plans:
             pl.free()
     engine.tune(4, 0)
-    engine.coalesce(default_group)
+    set_group(default_group)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
