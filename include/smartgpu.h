@@ -285,12 +285,16 @@ int smartgpu_tune(int key, int value);
  * is sent first.  This is the narrow view of the setting of smartgpu_coalesce_wide(): a previous value above 8 is
  * returned as 8. */
 int smartgpu_coalesce(int max_group);
-/* The same setting over its whole range: 0 or 2..32, the most patterns one hor_multi_scan takes.  Returns the previous
- * value as it was, SMARTGPU_ERR_ARG for anything else.  The library starts with 32: on 1 GiB of rand128 at m = 32 a
- * pass of 32 takes 0.19 ms against 0.16 ms for a pass of eight or a solo scan, 0.0060 ms per pattern against 0.0203 and
- * 0.156, and it is the fastest width at m = 16, 64 and 256 too (profiles/coalesce/RESULTS.md).  A key's first pass is
- * sent once that many launches have gathered or at the next call that sends what is pending, whichever comes first. */
+/* The same setting up to 32: 0 or 2..32.  Returns the previous value, a value above 32 (smartgpu_coalesce_pass) as 32;
+ * SMARTGPU_ERR_ARG for anything else.  A pass set through this call or smartgpu_coalesce() is sent when exactly that
+ * many launches have gathered, or at the next call that sends what is pending, whichever comes first. */
 int smartgpu_coalesce_wide(int max_group);
+/* The same setting over its whole range: 0 or 2..96, the most patterns one hor_multi_scan takes.  Returns the previous
+ * value as it was, SMARTGPU_ERR_ARG for anything else.  How many patterns a pass really takes also depends on their
+ * length, because a pass carries the end of every pattern in its kernel arguments: 96 up to m = 16, 84 up to m = 32,
+ * 63 up to m = 48, 50 up to m = 64, 42 beyond; a wider setting is clipped to that per length, not refused.  The
+ * library starts with 96 (profiles/coalesce/RESULTS.md has the measurements). */
+int smartgpu_coalesce_pass(int max_group);
 /* Of the launches on `device` that could share a pass: how many were seen, and how many kernels were sent for them
  * (equal when nothing was coalesced).  Either pointer may be NULL. */
 int smartgpu_coalesce_stats(int device, uint64_t *launches, uint64_t *passes);

@@ -68,6 +68,7 @@ struct DeviceCtx {
     size_t pinned_bytes = 0;
     unsigned long long* pinned_count = nullptr;  // 8-byte readback slot
     hipEvent_t mark[2] = {nullptr, nullptr};     // smartgpu_stream_mark()
+    bool hor_preloaded = false;                  // sg::g_hor_preload has run on this device (smartgpu_plan_create)
     // smartgpu_search_batch64(): one arena for the K pattern blobs and the K counts, grown when a
     // batch needs more, never per pattern; K+1 events for the per-pattern device times
     uint8_t* arena = nullptr;
@@ -109,6 +110,16 @@ DeviceCtx* device_ctx(int device)
         d.ready = true;
     }
     return &d;
+}
+
+// device_ctx without a HIP call where the device has been set up — and WITHOUT making it current: for
+// smartgpu_plan_launch, whose launches are mostly queued (below) and touch the device only when a key is sent.  Two HIP
+// calls per launch were a visible part of the host's launch loop once a pass took 84 launches: that loop, not the GPU,
+// bounds the flagship workload (profiles/coalesce/RESULTS.md).  Whoever sends makes the device current (send_key).
+DeviceCtx* device_ctx_ready(int device)
+{
+    if (device >= 0 && device < kMaxDevices && g_dev[device].ready) return &g_dev[device];
+    return device_ctx(device);
 }
 
 // hor_flat, bm_scan, bndm_scan and kmp_runs address LDS by absolute offset; a kernel that finds its dynamic segment
@@ -661,8 +672,12 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // A streaming Horspool scan runs at the rate the text can be read, so what is left to save lies BETWEEN searches: K plans
 // launched over the same text read it K times.  smartgpu_plan_launch therefore does not send a launch that would reach
 // launch_hor's streaming branch (route {hor, 0}, a sparse pattern); it queues the finished arguments per device under
-// (text, range, m, halo).  A key that has collected g_coalesce launches (at most kMultiMax = 32) is sent at once as ONE
-// hor_multi_scan — the GPU never waits for a flush while full groups exist, and at most g_coalesce - 1 launches per key are ever pending.  Every
+// (text, range, m, halo).  A key that has collected its width — g_coalesce launches, or what the arguments of a pass of
+// its length have room for (sg::pass_width(m), at most kPassMax = 96) if that is less — is sent at once as ONE
+// hor_multi_scan — the GPU never waits for a flush while full groups exist, and fewer than a width per key are ever pending.
+// (Sending a key that is still gathering whenever it held a multiple of 32 launches and hipStreamQuery found the stream
+// idle was tried and left out: on the flagship workload it changed ms_per_step by less than the run-to-run spread —
+// profiles/coalesce/RESULTS.md.)  Every
 // entry point that waits for, times, orders work on, or frees what is on the device's stream sends what is pending
 // first (flush_queue), in arrival order; a launch that is alone by then goes through launch_scan as it always did.
 // An untimed launch that cannot share a pass (another algorithm, a pattern whose symbols repeat) is no such entry point:
@@ -673,7 +688,7 @@ struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; uint8_t tail[
 struct QueuedKey {
     sg::ScanArgs key;  // text, s_begin, s_end, m, halo
     uint32_t n = 0;
-    QueuedScan scans[sg::kMultiMax];
+    QueuedScan scans[sg::kPassMax];
     bool holds(const sg::ScanArgs& a) const { return key.text == a.text && key.s_begin == a.s_begin && key.s_end == a.s_end && key.m == a.m && key.halo == a.halo; }
 };
 struct LaunchQueue {
@@ -686,33 +701,37 @@ struct LaunchQueue {
     uint64_t launches = 0, passes = 0;  // eligible launches seen / kernels sent for them
 };
 LaunchQueue g_queue[kMaxDevices];
-// launches per pass: 0 = off, 2..kMultiMax.  ONE number with two calls: smartgpu_coalesce, the first, sets 0 or
-// 2..kCoalesceNarrow and reports a wider value as kCoalesceNarrow; smartgpu_coalesce_wide sets and reports all of it.
-// The default is the widest pass: per pattern on 1 GiB of rand128 at m = 32, 0.0203 / 0.0105 / 0.0072 / 0.0060 ms in
-// passes of 8 / 16 / 24 / 32, and 32 is the fastest at m = 16, 64 and 256 as well (profiles/coalesce/RESULTS.md), so no
-// length gets a cap of its own.
+// launches per pass: 0 = off, 2..kPassMax.  ONE number with three calls: smartgpu_coalesce, the first, sets 0 or
+// 2..kCoalesceNarrow and reports a wider value as kCoalesceNarrow; smartgpu_coalesce_wide sets 0 or 2..kMultiMax and
+// reports a wider value as kMultiMax; smartgpu_coalesce_pass sets and reports all of it.
+// The default is the widest pass, clipped per key to sg::pass_width(m): per pattern on 1 GiB of rand128 at m = 32,
+// 0.0202 / 0.0055 / 0.0034 / 0.0028 ms in passes of 8 / 32 / 64 / 84, and the widest pass is the fastest at m = 16, 64 and
+// 256 as well (profiles/coalesce/RESULTS.md), so no length gets a cap beyond what its rows leave room for.
 constexpr int kCoalesceNarrow = 8;
-std::atomic<int> g_coalesce{32};
+std::atomic<int> g_coalesce{sg::kPassMax};
 
-// send one key's launches (q.mu held, the device current)
+// send one key's launches (q.mu held); makes the device current
 hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
 {
-    hipError_t e = hipSuccess;
+    hipError_t e = k.n ? hipSetDevice(d->device) : hipSuccess;
+    if (e != hipSuccess) {
+        k.n = 0;
+        return e;
+    }
     if (k.n == 1) {
         e = sg::launch_scan(k.scans[0].algo, k.scans[0].a, d->num_cus, d->stream, k.scans[0].codes);
     } else if (k.n > 1) {
-        sg::MultiArgs ma = {};
+        sg::MultiArgs ma;  // (not zeroed: 4 KB, and the kernel reads the entries of np patterns only)
         ma.text = k.key.text;
         ma.s_begin = k.key.s_begin;
         ma.s_end = k.key.s_end;
         ma.m = k.key.m;
         ma.halo = k.key.halo & 0xFFu;  // as prepare_scan_args: H without the plan's marks
         ma.np = k.n;
-        for (uint32_t j = 0; j < k.n; ++j) {
-            ma.blob[j] = k.scans[j].a.blob;
-            ma.count[j] = k.scans[j].a.count;
-            std::memcpy(ma.tail[j], k.scans[j].tail, sg::kTailRow);
-        }
+        ma.width = sg::pass_width(k.key.m);
+        ma.stride = sg::tail_stride(k.key.m);
+        ma.reserved = 0;
+        for (uint32_t j = 0; j < k.n; ++j) sg::multi_set(ma, j, k.scans[j].a.blob, k.scans[j].a.count, k.scans[j].tail);
         e = sg::g_hor_multi(ma, d->num_cus, d->stream);
     }
     if (k.n && e == hipSuccess) ++q.passes;
@@ -794,7 +813,9 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
     qs.a = a;
     qs.codes = codes;
     std::memcpy(qs.tail, tail, sg::kTailRow);
-    if (k.n >= static_cast<uint32_t>(G)) {  // (G <= kMultiMax, the room a key has)
+    uint32_t width = sg::pass_width(a.m);  // (at most kPassMax, the room a key has)
+    if (static_cast<uint32_t>(G) < width) width = static_cast<uint32_t>(G);
+    if (k.n >= width) {
         const hipError_t e = send_key(d, q, k);
         if (e != hipSuccess && err == hipSuccess) err = e;
         q.drop(at);
@@ -807,6 +828,7 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
 
 namespace sg {
 hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // multi.hpp: set by k_horm.hip where that unit is linked
+hipError_t (*g_hor_preload)() = nullptr;  // launch_common.hpp: set by k_hor.hip where that unit is linked
 // pedit.hpp: set by k_pedit.hip where that unit is linked
 hipError_t (*g_planes_edit_scan)(const PlaneEditArgs&, int, int, hipStream_t) = nullptr;
 hipError_t (*g_planes_edit_find)(const PlaneEditArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
@@ -972,6 +994,11 @@ smartgpu_plan* smartgpu_plan_create(int algo, const uint8_t* P, uint32_t m, int 
     std::vector<uint8_t> blob;
     p->words = build_blob(blob, algo, P, m);
     sg::tail_fill(p->tail, P, m);
+    if ((algo == SMARTGPU_HOR || algo == SMARTGPU_TUNEDBM) && sg::g_hor_preload && !d->hor_preloaded) {
+        // hor_scan's code object and kernels now, not at the first launch that cannot share a pass (k_hor.hip)
+        d->hor_preloaded = true;
+        if (sg::g_hor_preload() != hipSuccess) (void)hipGetLastError();  // (a launch will report what is wrong)
+    }
     bool ok = hipMalloc(reinterpret_cast<void**>(&p->blob), blob.size()) == hipSuccess &&
               hipMalloc(reinterpret_cast<void**>(&p->results), sizeof(unsigned long long) * sg::kResultSlots) == hipSuccess;
     if (ok) {
@@ -1013,12 +1040,13 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
     if (slot < 0 || slot >= p->num_slots()) { set_error("slot %d out of range", slot); return SMARTGPU_ERR_ARG; }
     if (text->device != p->device) { set_error("plan is on device %d, text on %d", p->device, text->device); return SMARTGPU_ERR_ARG; }
     if (off > text->n || n > text->n - off) { set_error("range outside the text"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx(p->device);
+    DeviceCtx* d = device_ctx_ready(p->device);  // (not current yet: a queued launch makes no HIP call)
     if (!d) return SMARTGPU_ERR_HIP;
     const sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(slot), text, off, n);
     bool queued = false;
     HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), p->tail, timed != 0, &queued), return SMARTGPU_ERR_HIP);
     if (queued) { p->timed[slot] = false; return SMARTGPU_OK; }
+    HIP_TRY(hipSetDevice(p->device), return SMARTGPU_ERR_HIP);
     // A timed launch keeps its place behind what was queued before it: its events bracket this kernel alone.  Any other
     // launch that cannot share a pass goes ahead of what is pending: counts are ADDED to their slots, in any order, and
     // sending a half-filled key here costs its launches a pass of their own over the text.  (One m = 32 pattern in the
@@ -1139,7 +1167,8 @@ int smartgpu_tune(int key, int value)
     return SMARTGPU_OK;
 }
 
-// the one setting behind smartgpu_coalesce (most = kCoalesceNarrow) and smartgpu_coalesce_wide (most = kMultiMax)
+// the one setting behind smartgpu_coalesce (most = kCoalesceNarrow), smartgpu_coalesce_wide (most = kMultiMax) and
+// smartgpu_coalesce_pass (most = kPassMax)
 static int set_coalesce(int max_group, int most)
 {
     if (max_group != 0 && (max_group < 2 || max_group > most)) { set_error("coalesce: a pass takes 2..%d launches (0: off), not %d", most, max_group); return SMARTGPU_ERR_ARG; }
@@ -1155,7 +1184,13 @@ int smartgpu_coalesce(int max_group)
 
 int smartgpu_coalesce_wide(int max_group)
 {
-    return set_coalesce(max_group, sg::kMultiMax);
+    const int prev = set_coalesce(max_group, sg::kMultiMax);
+    return prev > sg::kMultiMax ? sg::kMultiMax : prev;
+}
+
+int smartgpu_coalesce_pass(int max_group)
+{
+    return set_coalesce(max_group, sg::kPassMax);
 }
 
 int smartgpu_coalesce_stats(int device, uint64_t* launches, uint64_t* passes)

@@ -511,5 +511,27 @@ hipError_t launch_hor_bp(const ScanArgs& a, int num_cus, hipStream_t stream)
 }
 #endif
 
+// The runtime loads a unit's code object, and makes a kernel's function object, when the process first launches a
+// kernel of it.  For hor_scan that moment used to lie in the middle of a launch loop: Horspool launches that share a
+// pass go to hor_multi_scan (k_horm.hip), and the first one that cannot — a pattern whose symbols repeat, a launch that
+// is alone when something waits — made the host stop for some hundred microseconds while the GPU ran dry
+// (profiles/coalesce/RESULTS.md: the one long boundary of the traces).  smartgpu_plan_create calls this once per
+// device for a Horspool or Tuned BM plan instead.
+static hipError_t preload_hor()
+{
+    const void* const kernels[4] = {(const void*)&hor_scan<kHorT, kHorL, false, 0>, (const void*)&hor_scan<kHorT, kHorL, true, 0>,
+                                    (const void*)&hor_scan<kBmBusyT, kHorL, false, 9>, (const void*)&hor_scan<kBmBusyT, kHorL, true, 9>};
+    for (const void* k : kernels) {
+        hipFuncAttributes at;
+        const hipError_t e = hipFuncGetAttributes(&at, k);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+namespace {
+struct RegisterHorPreload {
+    RegisterHorPreload() { g_hor_preload = &preload_hor; }
+} g_register_hor_preload;
+}  // namespace
 
 }  // namespace sg

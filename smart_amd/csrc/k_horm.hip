@@ -1,5 +1,5 @@
-// k_horm.hip — hor_multi_scan: Horspool (and Tuned BM) on hor_scan's LDS tiles for up to 32 patterns of one length
-// in ONE pass over the text (a translation unit of its own: dev_common.hpp says why)
+// k_horm.hip — hor_multi_scan: Horspool (and Tuned BM) on hor_scan's LDS tiles for up to kPassMax = 96 patterns of one
+// length in ONE pass over the text (a translation unit of its own: dev_common.hpp says why)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
 #include "multi.hpp"
@@ -7,44 +7,44 @@
 namespace sg {
 
 // ---------------------------------------------------------------------------
-// hor_scan<.., VAR 0> (k_hor.hip) with the tile staged ONCE for np <= NP patterns: searches of one text that are queued
-// together (api.cpp) share the fetch and HBM bytes per pattern fall by np.  Same tiles on absolute offsets indexed by
-// window end, same back halo, same prefetch one tile ahead, same swizzle, same range clamps.
-// LDS: u64 blob[32] | u64 count[32] | u64 hits[32] | u32 gram[kGramSlots] | np x pattern tail P[m-1-H..m-1] | text [tile0-H16, tile0+TB)
+// hor_scan<.., VAR 0> (k_hor.hip) with the tile staged ONCE for the np patterns of a pass: searches of one text that are
+// queued together (api.cpp) share the fetch and HBM bytes per pattern fall by np.  Same tiles on absolute offsets indexed
+// by window end, same back halo, same prefetch one tile ahead, same swizzle, same range clamps.
+// LDS: u8 gram[kGramSlots] | u32 heads[kGramBuckets] | u32 next[kPassMax] | u32 sums[kPassMax] | np rows | text [tile0-H16, tile0+TB)
 // The walk: a Horspool walk per pattern asks np times, one pattern at a time, whether a pattern ends near a window end,
 // and np such walks of a staged tile cost more than its fetch.  ONE walk per lane asks it for all patterns at once:
-// the workgroup builds, in its prologue, the skip table of multi.hpp — indexed by the window's last two bytes, the
-// least shift any pattern of the pass allows and the CLASSES of the patterns whose last gram falls into the slot (LDS
-// atomics: min for the shifts, a barrier, or for the class bits and the tag of the last gram).  An entry has eight
-// class bits and a pass up to kMultiMax = 32 patterns: pattern g is of class g & 7, and a window whose entry passes the
-// tag test is compared with the patterns c, c + 8, c + 16, c + 24 below np of every class c that is set.  A gram hit is
-// rare (about np / 16384 per step on rand128) and a class mate that is not the pattern dies on its first byte; counts
-// stay exact because every compare is a whole one.  A pass of at most eight has one pattern per class: nothing changes.
-// np x (m - 2) grams hardly fill
-// kGramSlots slots, so nearly every step moves the window end by m - 1 and a lane leaves its 64-byte segment after
-// about 64 / (m - 1) steps whatever np is.  A step: two byte reads (tile_at permutes dwords, the two bytes of a gram
-// may lie in different ones), the slot, the entry; compare for every pattern of every class bit, but only where the entry's tag
-// says that the window ends in a pattern's last gram and not merely in its slot; add the shift.
-// The prologue reads no pattern from memory: the bytes the table and the tails are made of, at most 65 per pattern,
-// come BY VALUE in the rows of MultiArgs (multi.hpp), each thread reads its few of them from the arguments first, and
-// the first tile is asked for before the table is built — measured, a pass of eight fell from 167-170 us to 164-165 us
-// against a solo hor_scan's 156 us (1 GiB rand128, m = 32; profiles/coalesce/RESULTS.md); the tag took it to 162-163.
-// The arguments are 3112 bytes at 32 patterns, with tile_first and ntiles 3124 of the 4096 a kernel may take
-// (multi.hpp asserts it).  The pointer arrays of MultiArgs are read once, in the prologue: thread g < np takes blob[g]
-// and count[g] from the argument segment AS NUMBERS and writes them to LDS — one thread filling all 32 would unroll
-// into 64 selects, and a pointer picked by a run-time index and then dereferenced is loaded through flat_load;
-// a pattern's pointer — needed only to complete a window in memory — is read from LDS as a number and cast to GLOBAL
-// memory.  The kernel is as long as hor_scan
-// whatever NP is, so NP, the most patterns a pass can take, is instantiated once, at kMultiMax, and completion in
-// memory (m - 1 > H) is a run-time branch of that one kernel, taken by rare candidates only: the product library has a
-// size to keep (tests/test_abi.py holds it below 0.7 of the A/B build).
+// the workgroup builds, in its prologue, the skip table of multi.hpp — one BYTE per slot, indexed by the window's last
+// two bytes: the least shift any pattern of the pass allows, and a bit that says that some pattern's last gram falls
+// into the slot.  LDS has no byte atomics: a shift is entered with a compare-and-swap on the dword that holds the byte
+// (horm_byte_min), the bit after a barrier with an OR.  A step: two byte reads (tile_at permutes dwords, the two bytes
+// of a gram may lie in different ones), the slot, the entry, add the shift.  np x (m - 2) grams hardly fill 16384
+// slots, and the slot function is exact on 7-bit symbols, so nearly every step moves the window end by m - 1 and a lane
+// leaves its 64-byte segment after about 64 / (m - 1) steps whatever np is.
+// The candidates: a window whose entry has the bit follows the chain of its gram's bucket — heads[gram_bucket], then
+// next[g]; pattern g + 1 stands for g, 0 ends the chain; thread g < np links pattern g in with one atomicExch — and is
+// compared, whole, right to left, with each pattern on it.  A hit is rare (about np / 16384 per step on rand128), a
+// chain holds one pattern and seldom two, and a pattern of the bucket that is not the window's dies on its first bytes;
+// counts stay exact because every compare is a whole one.  The same pattern twice in a pass is twice on its chain.
+// The prologue reads no pattern from memory: the rows of the pass come BY VALUE in the arguments' area (multi.hpp), at
+// the stride of their own length; thread x copies 16 bytes of them to LDS with ONE read, sent before the first tile is
+// asked for, and the table is built from LDS while the tile is on the way.  A row in LDS is also what a lane compares a
+// window with (its last H + 1 stored bytes).  A narrow pass sends few reads: np x stride / 16.
+// The arguments are 4080 bytes, with tile_first and ntiles 4092 of the 4096 a kernel may take (multi.hpp asserts it).
+// The pointers in the area are read as numbers and cast to GLOBAL memory: thread g < np keeps count[g] in registers
+// from the prologue to the end; blob[g] is read by the rare lane that completes a window in memory.
+// One instantiation; completion in memory (m - 1 > H) is a run-time branch of it, taken by rare candidates only: the
+// product library has a size to keep (tests/test_abi.py holds it below 0.7 of the A/B build).
 // Counts: an occurrence is rare for a streaming pattern (the only kind that gets here), so a lane adds each one straight
 // to its pattern's LDS counter, and at the end the workgroup adds every non-zero counter to that pattern's result slot.
+// A counter is a u32: a workgroup counts at most one occurrence per window end, and the launcher gives no workgroup
+// more than 2^17 tiles of 2^14 window ends (launch_hor_multi).
 // Not through the staging slots of flush_hits: those assume ONE flush per grid, and here a grid flushes np sums.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kHormHead = 3 * 8 * kMultiMax;  // the three u64 arrays in front of the skip table
-constexpr uint32_t kHormGram = 4 * kGramSlots;    // the skip table
-static_assert(kHormHead % 64 == 0 && kHormGram % 64 == 0, "the tails and the tile stay 16-byte aligned");
+constexpr uint32_t kHormHead = kGramSlots + 4 * (kGramBuckets + 2 * kPassMax);  // the table, the heads, the links and the sums
+static_assert(kHormHead % 64 == 0, "the rows stay 16-byte aligned and the tile 64-byte aligned");
+// four workgroups per CU: 160 KB of LDS, allocated in blocks of at most 2 KB
+static_assert(kHormHead + ((kPassMax * 16u + 63u) & ~63u) + 16448u <= 40960u && kHormHead + ((50u * 64u + 63u) & ~63u) + 16448u <= 40960u &&
+              kHormHead + ((42u * kTailRow + 63u) & ~63u) + 16448u <= 40960u, "the widest pass of every row stride leaves four workgroups per CU resident");
 
 // a pointer into global memory from the number an LDS slot holds (per lane: lanes may ask for different patterns)
 __device__ __forceinline__ const uint8_t* horm_global(unsigned long long v)
@@ -87,64 +87,51 @@ __device__ __forceinline__ uint32_t horm_wave_verify(bool has, const uint8_t* tp
     return mine;
 }
 
-template <int THREADS, int L, int NP>
+// the least of the byte at `slot` and s, in a table of bytes that has no byte atomics: compare-and-swap on its dword.
+// (Bit 7 of every byte is still clear: the hit bits are set after a barrier.)
+__device__ __forceinline__ void horm_byte_min(uint8_t* table, uint32_t slot, uint32_t s)
+{
+    uint32_t* const word = reinterpret_cast<uint32_t*>(table + (slot & ~3u));
+    const uint32_t sh = 8u * (slot & 3u);
+    uint32_t old = *word;
+    while (((old >> sh) & 0xFFu) > s) {
+        const uint32_t seen = atomicCAS(word, old, (old & ~(0xFFu << sh)) | (s << sh));
+        if (seen == old) break;
+        old = seen;
+    }
+}
+
+// a u64 of the arguments' area as a number, at an offset of the lane's own
+__device__ __forceinline__ unsigned long long horm_area64(const MultiArgs& a, uint32_t at)
+{
+    return *reinterpret_cast<const unsigned long long*>(a.area + at);
+}
+
+template <int THREADS, int L>
 __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t tile_first, uint32_t ntiles)
 {
     constexpr int TB = THREADS * L;
-    static_assert(NP == kMultiMax && NP <= 4 * (int)kGramClasses && NP <= THREADS, "a class bit in an entry's byte 2 stands for at most four patterns");
+    static_assert(kPassMax <= THREADS && THREADS % (int)kGramCap == 0, "a thread per pattern; the grams of THREADS / kGramCap patterns in a round");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t m = a.m, H = a.halo, H16 = round16(H), np = a.np;
+    const uint32_t m = a.m, H = a.halo, H16 = round16(H), np = a.np, W = a.width, stride = a.stride;
     const bool in_memory = m - 1 > H;  // windows are completed in HBM
-    const uint32_t tslot = round16(H + 1);  // one pattern's tail; ptail[H-k] == P[m-1-k]
-    unsigned long long* blobs = reinterpret_cast<unsigned long long*>(smem);
-    unsigned long long* counts = blobs + kMultiMax;
-    unsigned long long* sums = counts + kMultiMax;
-    uint32_t* gram = reinterpret_cast<uint32_t*>(smem + kHormHead);
-    uint8_t* tails = smem + kHormHead + kHormGram;
-    uint8_t* txt = tails + np * tslot;  // txt[H16 + x] == T[tile0 + x]
+    const uint32_t rlast = m - 1 - gram_first(m);  // P[m-1-k] is byte rlast - k of a row
+    uint8_t* gram = smem;
+    uint32_t* heads = reinterpret_cast<uint32_t*>(smem + kGramSlots);
+    uint32_t* next = heads + kGramBuckets;
+    uint32_t* sums = next + kPassMax;
+    uint8_t* rows = smem + kHormHead;
+    const uint32_t row_bytes = np * stride;              // a multiple of 16
+    uint8_t* txt = rows + ((row_bytes + 63u) & ~63u);  // txt[H16 + x] == T[tile0 + x]
 
-    // What this thread takes of the rows in the arguments (multi.hpp), read before anything else: every address is the
-    // arguments' plus an index of the thread's, so no read waits for another.  Loads come back in the order they
-    // were sent, so these go out in front of the tile's and the table is built while the tile is on the way.  A thread
-    // with nothing to take reads a byte that exists all the same (m >= 3): no branch, no wait between the reads.
-    // The rounds beyond a pass of eight stand behind a test of np, the same for the whole workgroup: a pass of at most
-    // eight sends the reads of its own patterns only.
-    constexpr uint32_t kTslotMax = (kHaloMax + 16u) & ~15u;                // the longest tail, rounded: 32
-    constexpr uint32_t kTailPer = THREADS / kTslotMax;                     // 8 patterns' tails in a round
-    constexpr uint32_t kTailRounds = kMultiMax / kTailPer;                 // 4
-    constexpr uint32_t kShiftPer = THREADS / kGramCap;                     // 4 patterns' grams in a round
-    constexpr uint32_t kShiftRounds = kMultiMax / kShiftPer;               // 8
-    static_assert(kTailRounds * kTailPer == kMultiMax && kShiftRounds * kShiftPer == kMultiMax && kTailPer * kTslotMax == THREADS && kShiftPer * kGramCap == THREADS,
-                  "kTailRounds tail bytes and kShiftRounds grams per thread");
-    // tails: in round r thread x takes byte x % 32 of pattern x / 32 + 8 r: ptail[j] = P[m-1-H+j], j <= H
-    const uint32_t tail_j = threadIdx.x % kTslotMax;
-    uint32_t tail_byte[kTailRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kTailRounds; ++r) {
-        tail_byte[r] = 0;
-        if (r == 0 || np > r * kTailPer) {
-            const uint32_t g = threadIdx.x / kTslotMax + r * kTailPer;
-            const bool mine = g < np && tail_j <= H;
-            tail_byte[r] = tail_at(a.tail[mine ? g : 0u], m, m - 1 - (mine ? H - tail_j : 0u));
-        }
-    }
-    // shifts: in round r thread x takes the gram at position gram_first(m) + x % kGramCap of pattern x / kGramCap + 4 r,
-    // both bytes in one read (at most kGramCap - 1 positions of a pattern shift by less than the default)
-    const uint32_t shift_i = gram_first(m) + threadIdx.x % kGramCap;
-    const bool shift_mine = shift_i + 3 <= m;
-    uint32_t shift_gram[kShiftRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kShiftRounds; ++r) {
-        shift_gram[r] = 0;
-        if (r * kShiftPer < 8 || np > r * kShiftPer) {
-            const uint32_t g = threadIdx.x / kGramCap + r * kShiftPer;
-            shift_gram[r] = tail_gram_at(a.tail[g < np ? g : 0u], m, shift_mine ? shift_i : gram_first(m));
-        }
-    }
-    // class bits: thread g < np takes pattern g's last gram — and its blob and its result slot, as numbers
-    const uint32_t bit_g = threadIdx.x < np ? threadIdx.x : 0u;
-    const uint32_t bit_gram = tail_gram_at(a.tail[bit_g], m, m - 2);
-    const unsigned long long head_blob = (unsigned long long)a.blob[bit_g], head_count = (unsigned long long)a.count[bit_g];
+    // What this thread takes of the arguments' area (multi.hpp), read before anything else: 16 bytes of the rows, and
+    // (thread g < np) the result slot of pattern g as a number.  Loads come back in the order they were sent, so these
+    // go out in front of the tile's and the table is built while the tile is on the way.
+    const bool row_mine = threadIdx.x * 16u < row_bytes;
+    uint4 row16 = {};
+    if (row_mine) row16 = *reinterpret_cast<const uint4*>(a.area + multi_rows_at(W) + threadIdx.x * 16u);
+    unsigned long long head_count = 0;
+    if (threadIdx.x < np) head_count = horm_area64(a, multi_count_at(W, threadIdx.x));
 
     const uint64_t e_begin = a.s_begin + m - 1, e_end = a.s_end + m - 1;
     const uint64_t t_end = tile_first + ntiles;
@@ -162,26 +149,36 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
     uint64_t t = tile_first + blockIdx.x;
     issue(t * TB);  // (the launcher starts no more workgroups than there are tiles)
 
-    // the table and the tails, in LDS: the default, a barrier, the least shift per slot, a barrier, the pattern bits
-    if (threadIdx.x < (uint32_t)NP) {
-        blobs[threadIdx.x] = threadIdx.x < np ? head_blob : 0ull;
-        counts[threadIdx.x] = threadIdx.x < np ? head_count : 0ull;
-        sums[threadIdx.x] = 0;
-    }
-    const uint32_t dflt = gram_default(m);
-    for (uint32_t j = threadIdx.x; j < kGramSlots; j += THREADS) gram[j] = dflt;
-#pragma unroll
-    for (uint32_t r = 0; r < kTailRounds; ++r) {
-        const uint32_t g = threadIdx.x / kTslotMax + r * kTailPer;
-        if (g < np && tail_j <= H) tails[g * tslot + tail_j] = (uint8_t)tail_byte[r];
+    // the table, the chains and the rows, in LDS: the default and the rows, a barrier, the least shift per slot, a
+    // barrier, the hit bits and the links
+    {
+        const uint32_t dflt = gram_default(m) * 0x01010101u;
+        const uint4 dflt16 = {dflt, dflt, dflt, dflt};
+        for (uint32_t j = threadIdx.x * 16u; j < kGramSlots; j += THREADS * 16u) *reinterpret_cast<uint4*>(gram + j) = dflt16;
+        for (uint32_t j = threadIdx.x; j < kGramBuckets; j += THREADS) heads[j] = 0;
+        if (threadIdx.x < (uint32_t)kPassMax) sums[threadIdx.x] = 0;
+        if (row_mine) *reinterpret_cast<uint4*>(rows + threadIdx.x * 16u) = row16;
     }
     __syncthreads();
-#pragma unroll
-    for (uint32_t r = 0; r < kShiftRounds; ++r)
-        if (threadIdx.x / kGramCap + r * kShiftPer < np && shift_mine) atomicMin(gram + gram_slot(shift_gram[r] & 0xFFu, shift_gram[r] >> 8), gram_shift(m, shift_i));
-    __syncthreads();  // every shift is in before a class bit makes an entry larger
-    if (threadIdx.x < np) atomicOr(gram + gram_slot(bit_gram & 0xFFu, bit_gram >> 8), gram_entry_class_bit(threadIdx.x) | gram_entry_tag(bit_gram & 0xFFu));
-    // (the loop's first barrier stands between these bits and the first walk)
+    {
+        // shifts: in a round, thread x takes the gram at position gram_first(m) + x % kGramCap of pattern x / kGramCap +
+        // (THREADS / kGramCap) r (at most kGramCap - 1 positions of a pattern shift by less than the default); the
+        // rounds a pass takes follow np, the same for the whole workgroup
+        const uint32_t shift_i = gram_first(m) + threadIdx.x % kGramCap;
+        if (shift_i + 3 <= m)
+            for (uint32_t g = threadIdx.x / kGramCap; g < np; g += THREADS / kGramCap) {
+                const uint32_t two = tail_gram_at(rows + g * stride, m, shift_i);
+                horm_byte_min(gram, gram_slot(two & 0xFFu, two >> 8), gram_shift(m, shift_i));
+            }
+    }
+    __syncthreads();  // every shift is in before a hit bit makes a byte larger
+    if (threadIdx.x < np) {
+        const uint32_t two = tail_gram_at(rows + threadIdx.x * stride, m, m - 2);
+        const uint32_t slot = gram_slot(two & 0xFFu, two >> 8);
+        atomicOr(reinterpret_cast<uint32_t*>(gram + (slot & ~3u)), kGramHit << (8u * (slot & 3u)));
+        next[threadIdx.x] = atomicExch(heads + gram_bucket(two & 0xFFu, two >> 8), threadIdx.x + 1u);
+    }
+    // (the loop's first barrier stands between these and the first walk)
 
     for (; t < t_end; t += gridDim.x) {
         const uint64_t tile0 = t * TB;
@@ -203,52 +200,56 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
         const bool any = lo < hi;
         const uint32_t e0 = any ? (uint32_t)(lo - tile0) + H16 : H16;
         const uint32_t ehi = any ? (uint32_t)(hi - tile0) + H16 : H16;
-        bool parked = false;  // first candidate of this tile awaiting the wave-wide compare, and its pattern
+        bool parked = false;  // first candidate of this tile awaiting the wave-wide compare, its pattern and that pattern's blob
         uint32_t parked_g = 0;
         const uint8_t* parked_at = a.text;
+        unsigned long long parked_blob = (unsigned long long)a.text;
         // the staged tile, walked once for all patterns (a lane without a window end has e0 == ehi)
         for (uint32_t e = e0; e < ehi;) {
             const uint32_t prev = txt[tile_at(e - 1)], last = txt[tile_at(e)];  // e >= H16 >= 16: e - 1 is in the halo at least
             const uint32_t ent = gram[gram_slot(prev, last)];
-            for (uint32_t cls = gram_entry_hit(ent, prev); cls != 0; cls &= cls - 1) {  // (a slot hit that is no gram hit: no compare)
-                // the class's patterns below np: a mate that is not the pattern dies on its first byte, almost always
-                for (uint32_t g = __builtin_ctz(cls); g < np; g += kGramClasses) {
-                    const uint8_t* ptail = tails + g * tslot;
+            if (gram_byte_hit(ent)) {
+                // the patterns of the gram's bucket: one that is not the window's dies on its first bytes
+                for (uint32_t c = heads[gram_bucket(prev, last)]; c != 0; c = next[c - 1u]) {
+                    const uint32_t g = c - 1u;
+                    const uint8_t* prow = rows + g * stride;
                     uint32_t k = 0;  // bytes matched so far, right to left (the slot promises none of them)
-                    while (k <= H && ptail[H - k] == txt[tile_at(e - k)]) ++k;
+                    while (k <= H && prow[rlast - k] == txt[tile_at(e - k)]) ++k;
                     bool ok = k == H + 1;
                     if (in_memory && ok) {  // the rest of the window is not in LDS
                         const uint8_t* rest = a.text + tile0 + (e - H16) - (m - 1);
+                        const unsigned long long blob = horm_area64(a, multi_blob_at(g));
                         if (!parked) {
                             parked = true;
                             parked_at = rest;
                             parked_g = g;
+                            parked_blob = blob;
                             ok = false;  // counted after the loop
                         } else {
-                            ok = global_equal(rest, horm_global(blobs[g]), m - 1 - H);
+                            ok = global_equal(rest, horm_global(blob), m - 1 - H);
                         }
                     }
-                    if (ok) atomicAdd(sums + g, 1ull);
+                    if (ok) atomicAdd(sums + g, 1u);
                 }
             }
-            e += gram_entry_shift(ent);
+            e += gram_byte_shift(ent);
         }
-        if (in_memory && horm_wave_verify(parked, parked_at, horm_global(blobs[parked_g]), m - 1 - H)) atomicAdd(sums + parked_g, 1ull);
+        if (in_memory && horm_wave_verify(parked, parked_at, horm_global(parked_blob), m - 1 - H)) atomicAdd(sums + parked_g, 1u);
     }
 
     // the workgroup's np sums, each straight to its pattern's result slot
     __syncthreads();
     if (threadIdx.x < np && sums[threadIdx.x] != 0) {
         typedef __attribute__((address_space(1))) unsigned long long* global_u64;
-        atomicAdd((unsigned long long*)reinterpret_cast<global_u64>(counts[threadIdx.x]), sums[threadIdx.x]);
+        atomicAdd((unsigned long long*)reinterpret_cast<global_u64>(head_count), (unsigned long long)sums[threadIdx.x]);
     }
 }
 
 // ---------------------------------------------------------------------------
-// launcher: the grid and the tile's LDS as launch_hor's streaming branch, plus the skip table and the tails of np patterns
+// launcher: the grid and the tile's LDS as launch_hor's streaming branch, plus the skip table, the chains and the rows
 // ---------------------------------------------------------------------------
-// Workgroups per CU.  A workgroup takes up to 33.8 KB of LDS (the table 16 KB of it) and 62 VGPRs, so four are resident
-// at most — and with the table of 2048 slots, where six were, FOUR won: swept on 1 GiB of rand128 at m = 16, 32, 256 in
+// Workgroups per CU.  A workgroup takes up to 39 KB of LDS (the table 16 KB of it), so four are resident at most — and
+// with the table of 2048 u32 slots, where six were, FOUR won: swept on 1 GiB of rand128 at m = 16, 32, 256 in
 // groups of 2, 4, 8 (8 patterns, m = 32: 0.0207 ms per pattern with 4, 0.0215 with 5, 0.0214 with 6, 0.0222 with 7), and
 // at m = 16, 32, 64, 256 in groups of 8 to 32, where 5 won a pass of 32 at m = 32 alone (0.0059 against 0.0063) and lost
 // at the other lengths by 2 - 5 % (profiles/coalesce/RESULTS.md) — the solo kernels' value.
@@ -262,15 +263,18 @@ static int horm_wgs(uint32_t m)
 
 hipError_t launch_hor_multi(const MultiArgs& a, int num_cus, hipStream_t stream)
 {
-    if (a.np < 1 || a.np > (uint32_t)kMultiMax || a.m < 3 || a.halo < 1 || a.halo > kHaloMax || a.halo > a.m - 1) return hipErrorInvalidValue;  // (a gram and the byte before a lane's first window end exist)
+    if (a.m < 3 || a.halo < 1 || a.halo > kHaloMax || a.halo > a.m - 1) return hipErrorInvalidValue;  // (a gram and the byte before a lane's first window end exist)
+    if (a.width != pass_width(a.m) || a.stride != tail_stride(a.m) || a.np < 1 || a.np > a.width) return hipErrorInvalidValue;
     const uint32_t m = a.m, H = a.halo;
     const TileRange tr = tiles_for(a.s_begin + m - 1, a.s_end + m - 1, (uint64_t)kHorT * kHorL);
     if (tr.count == 0) return hipSuccess;
-    const size_t lds = kHormHead + kHormGram + (size_t)a.np * r16(H + 1) + ((r16(H) + (size_t)kHorT * kHorL + 16 + 63) & ~(size_t)63);  // whole 64-byte blocks: tile_at() permutes inside them
+    const size_t lds = kHormHead + (((size_t)a.np * a.stride + 63) & ~(size_t)63) + ((r16(H) + (size_t)kHorT * kHorL + 16 + 63) & ~(size_t)63);  // whole 64-byte blocks: tile_at() permutes inside them
     const int wgs_per_cu = g_tune[4] ? g_tune[4] : horm_wgs(m);  // smartgpu_tune(4, .) applies
     uint32_t grid = (uint32_t)num_cus * (uint32_t)wgs_per_cu;
     if (grid > tr.count) grid = tr.count;
-    hipLaunchKernelGGL((hor_multi_scan<kHorT, kHorL, kMultiMax>), dim3(grid), dim3(kHorT), lds, stream, a, tr.first, tr.count);
+    const uint32_t least = (uint32_t)(((uint64_t)tr.count + (1u << 17) - 1) >> 17);  // a workgroup's u32 sums: at most 2^17 tiles each
+    if (grid < least) grid = least;
+    hipLaunchKernelGGL((hor_multi_scan<kHorT, kHorL>), dim3(grid), dim3(kHorT), lds, stream, a, tr.first, tr.count);
     return hipGetLastError();
 }
 

@@ -149,6 +149,10 @@ inline void allow_lds(const void* kernel, size_t lds)
 hipError_t launch_hor(const ScanArgs& a, uint32_t q, int num_cus, hipStream_t stream);     // HOR, TUNEDBM: hor_scan<.., 0> / the flat form <.., 9>; q: <.., q>, the q-gram table
 hipError_t launch_hor_var(int algo, const ScanArgs& a, int num_cus, hipStream_t stream);   // RAITA, QS, HASH3/5/8
 hipError_t launch_kr(const ScanArgs& a, int num_cus, hipStream_t stream);                  // Karp-Rabin on the bank-private tiles
+// Loads k_hor.hip's code object on the current device and resolves the kernels launch_hor sends, so that the first
+// launch of one of them does not do it in the middle of a launch loop.  Reached through a pointer that k_hor.hip's
+// static initialiser sets and api.cpp holds (null: nothing is preloaded), as g_hor_multi (multi.hpp).
+extern hipError_t (*g_hor_preload)();
 #ifdef SMARTGPU_AB
 hipError_t launch_hor_bp(const ScanArgs& a, int num_cus, hipStream_t stream);              // Horspool on the bank-private tiles (tune(0,2))
 #endif

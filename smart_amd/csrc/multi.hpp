@@ -3,84 +3,98 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace sg {
 
-constexpr int kMultiMax = 32;  // patterns per pass: four to each of the eight class bits of a skip-table entry (below)
+constexpr int kMultiMax = 32;  // the widest pass smartgpu_coalesce_wide sets (api.cpp); a pass takes up to kPassMax patterns
+constexpr int kPassMax = 96;   // patterns per pass at the most; what a length's rows leave room for is pass_width(m) below
 
 // The end of a pattern as a launch carries it BY VALUE: the bytes from position gram_first(m) (below) to m - 1 — every
 // gram the skip table enters and the at most 17 bytes a lane compares in LDS — at the front of a row, zeros behind
 // them.  At most kGramCap + 1 = 65 bytes; the row is padded to a multiple of 16.  The plan keeps its row on the host
-// from smartgpu_plan_create on, the launch queue copies it, and the kernel builds the tails and the table from the
-// rows in its arguments: no workgroup reads a pattern from memory before its first tile is on the way.
-constexpr uint32_t kTailRow = 80;
+// from smartgpu_plan_create on, the launch queue copies it, and the kernel builds the table from the rows in its
+// arguments: no workgroup reads a pattern from memory before its first tile is on the way.
+constexpr uint32_t kTailRow = 80;  // the longest row; a pass stores its rows at tail_stride(m), their own length
 
-// What the patterns of a pass have in common — text, range, length, back halo — and, per pattern, its row (above), its
-// blob (pattern + u16 tab[256], as launch_hor reads it: read only where a window is completed in memory, m - 1 > halo)
-// and its result slot.  The two pointer arrays are only ever indexed with compile-time constants.  Entries
-// np .. kMultiMax-1 are not read.
-struct MultiArgs {
+// What the patterns of a pass have in common — text, range, length, back halo — and one byte area that holds, for the
+// W = pass_width(m) patterns a pass of this length can take: u64 blob[W] (pattern + u16 tab[256], as launch_hor reads
+// it: read only where a window is completed in memory, m - 1 > halo) | u64 count[W] (the result slots) | W rows at
+// stride tail_stride(m).  Where the parts lie depends on m alone, not on np; entries np .. W-1 are not read.  The
+// kernel reads the pointers from the area AS NUMBERS (multi_blob, multi_count).
+constexpr uint32_t kMultiArea = 4032;
+struct alignas(16) MultiArgs {
     const uint8_t* text;        // device pointer to text byte 0
     uint64_t s_begin, s_end;    // start positions to count, as ScanArgs
     uint32_t m;                 // pattern length
     uint32_t halo;              // back halo H = min(m-1, kHaloMax)
-    uint32_t np;                // patterns in this pass, 1 <= np <= kMultiMax
-    const uint8_t* blob[kMultiMax];
-    unsigned long long* count[kMultiMax];
-    uint8_t tail[kMultiMax][kTailRow];
+    uint32_t np;                // patterns in this pass, 1 <= np <= width
+    uint32_t width;             // pass_width(m)
+    uint32_t stride;            // tail_stride(m)
+    uint32_t reserved;          // (the area starts at a multiple of 16: a thread copies 16 bytes of rows at a time)
+    uint8_t area[kMultiArea];
 };
 // the kernel takes MultiArgs and two more arguments, a u64 and a u32, by value: HIP passes at most 4096 bytes
 static_assert(sizeof(MultiArgs) + 8 + 4 <= 4096, "MultiArgs, tile_first and ntiles fit the kernel argument segment");
+static_assert(offsetof(MultiArgs, area) % 16 == 0 && sizeof(MultiArgs) == offsetof(MultiArgs, area) + kMultiArea, "the area is 16-byte aligned and ends the arguments");
 
-// The skip table that the patterns of a pass share (Wu-Manber, blocks of two bytes): one entry per slot, indexed by the
-// LAST TWO bytes of a window.  Low half: how far the window end may move — the least m-2-i over every pattern P of the
+// The skip table that the patterns of a pass share (Wu-Manber, blocks of two bytes): ONE BYTE per slot, indexed by the
+// LAST TWO bytes of a window.  Bits 0-6: how far the window end may move — the least m-2-i over every pattern P of the
 // pass and every position i <= m-3 whose gram (P[i], P[i+1]) falls into the slot; m-1 where no gram does (the next
-// window may still overlap this one by its last byte).  High half: bit g & 7 — the CLASS of pattern g — for every
-// pattern g whose LAST gram (P[m-2], P[m-1]) falls into the slot: a window that ends in such a slot is compared with
-// the patterns c, c + 8, c + 16, c + 24 below np of every class c whose bit is set.  A pass of at most eight has one
-// pattern per class, and the bit names the pattern.  Grams that collide in a slot, and class mates that are not the
-// pattern, only lower a shift or add a comparison (every comparison is a whole one), so any slot function counts right.  The rule is written once, for the kernel and for
-// the host program that checks it (tests/coalesce_gram_check.cpp).
-// 16 KB of LDS: with the tile and the tails of 32 patterns a workgroup takes 33.8 KB, and the four per CU that the pass
-// runs with (k_horm.hip: horm_wgs) stay below 160 KB.  32 patterns of m = 32 enter 37 % of 2048 slots and 20 % of 4096:
-// measured per pattern in a pass of 32, 0.0060 ms against 0.0063 at m = 32 and no slower at m = 16, 64, 256 or in a
-// pass of eight (profiles/coalesce/RESULTS.md, "Up to 32 patterns in a pass")
-constexpr uint32_t kGramSlots = 4096;
+// window may still overlap this one by its last byte); at most kGramCap = 64.  Bit 7 (kGramHit): the LAST gram
+// (P[m-2], P[m-1]) of some pattern of the pass falls into the slot.  A window that ends in such a slot follows the
+// chain of its gram's BUCKET (gram_bucket: kGramBuckets heads, a link per pattern) and is compared, whole, with every
+// pattern on it.  Grams that collide in a slot only lower a shift, and patterns that share a bucket only add a
+// comparison, so any slot and any bucket function counts right.  The rule is written once, for the kernel and for the
+// host program that checks it (tests/coalesce_pass_check.cpp).
+// 16384 byte slots take the 16 KB of LDS that 4096 u32 slots took.  The slot function is exact on symbols below 128, so
+// on such a text a slot hit is a gram hit and a shift is lowered only by a gram of the pass itself: a walk of the text
+// takes fewer steps with 84 patterns in these slots than with 32 in the 4096 (profiles/coalesce/RESULTS.md).
+constexpr uint32_t kGramSlots = 16384;
 constexpr uint32_t kGramCap = 64;      // a lane owns 64 window ends: a longer shift leaves its segment just the same
+constexpr uint32_t kGramHit = 0x80;    // a byte entry's bit 7
+constexpr uint32_t kGramBuckets = 512;
 
-// the slot of the gram (prev, last).  Injective for alphabets up to 37 symbols; byte pairs spread over all slots
-__host__ __device__ inline uint32_t gram_slot(uint32_t prev, uint32_t last) { return (prev * 37u + last) & (kGramSlots - 1u); }
+// The slot of the gram (prev, last): (f(prev) + last) mod kGramSlots, so that slot and prev determine last.  Injective
+// on symbols below 128 (128 prev + last); a prev of 128 or more is folded 85 slots away from prev - 128, so that a text
+// of both halves of the byte range does not put (prev, last) and (prev - 128, last) into one slot.
+__host__ __device__ inline uint32_t gram_slot(uint32_t prev, uint32_t last) { return (prev * 128u + (prev >> 7) * 85u + last) & (kGramSlots - 1u); }
+// the bucket of the gram: the top bits of a multiplicative hash of its slot (grams of one slot share a bucket)
+__host__ __device__ inline uint32_t gram_bucket(uint32_t prev, uint32_t last) { return (gram_slot(prev, last) * 0x9E3779B1u) >> 23; }
+static_assert(kGramBuckets == 1u << (32 - 23), "gram_bucket keeps the top nine bits");
+// a byte entry's parts
+__host__ __device__ inline uint32_t gram_byte_shift(uint32_t b) { return b & (kGramHit - 1u); }
+__host__ __device__ inline uint32_t gram_byte_hit(uint32_t b) { return b & kGramHit; }
 // the shift of a slot no gram reaches
-__host__ __device__ inline uint32_t gram_default(uint32_t m) { return m - 1u < kGramCap ? m - 1u : kGramCap; }
+__host__ __device__ constexpr uint32_t gram_default(uint32_t m) { return m - 1u < kGramCap ? m - 1u : kGramCap; }
 // the shift the gram at pattern position i allows, 0 <= i <= m - 3: at least 1
-__host__ __device__ inline uint32_t gram_shift(uint32_t m, uint32_t i) { return m - 2u - i; }
+__host__ __device__ constexpr uint32_t gram_shift(uint32_t m, uint32_t i) { return m - 2u - i; }
 // the first position whose gram is entered: those before it allow gram_default(m) or more
-__host__ __device__ inline uint32_t gram_first(uint32_t m) { return m - 1u > kGramCap ? m - 1u - kGramCap : 0u; }
-// an entry's parts: the shift in byte 0 (at most kGramCap), the class bits in byte 2
+__host__ __device__ constexpr uint32_t gram_first(uint32_t m) { return m - 1u > kGramCap ? m - 1u - kGramCap : 0u; }
+static_assert(kGramCap < kGramHit, "a shift fits the seven bits below the hit bit");
+
+// The FORMER entry, a u32 per slot: the shift in byte 0, eight class bits in byte 2, a tag of the last gram's first byte
+// in bytes 1 and 3.  hor_multi_scan no longer uses these; they are kept, self-consistent, for the committed host checks
+// (tests/coalesce_gram_check.cpp, coalesce_tail_check.cpp, coalesce_wide_check.cpp), which build u32 tables with them.
 __host__ __device__ inline uint32_t gram_entry_shift(uint32_t ent) { return ent & 0xFFu; }
 __host__ __device__ inline uint32_t gram_entry_patterns(uint32_t ent) { return (ent >> 16) & 0xFFu; }
 __host__ __device__ inline uint32_t gram_entry_pattern_bit(uint32_t g) { return 0x10000u << g; }  // g < 8
 __host__ __device__ inline uint32_t gram_entry_class_bit(uint32_t g) { return gram_entry_pattern_bit(g & 7u); }  // g < kMultiMax
 constexpr uint32_t kGramClasses = 8;  // the patterns of class c: c, c + kGramClasses, ... below np
-// Bytes 1 and 3 tell a slot hit from a gram hit without a compare: a pattern ORs gram_entry_tag(P[m-2]) into its slot
-// with its bit — `prev` in byte 1, its complement in byte 3 — and a window whose last two bytes fall into the slot is
-// compared only if every bit of ITS tag is there.  Slot and prev determine last (the slot is 37 prev + last mod
-// kGramSlots, and last < 256 <= kGramSlots), so with one last gram in a slot this asks for the gram itself; with
-// several, bits of both kinds add up and more windows pass, never fewer.  An entry without a pattern has no tag bit:
-// nothing passes.
 __host__ __device__ inline uint32_t gram_entry_tag(uint32_t prev) { return (prev << 8) | ((prev ^ 0xFFu) << 24); }
 __host__ __device__ inline uint32_t gram_entry_hit(uint32_t ent, uint32_t prev) { return (gram_entry_tag(prev) & ~ent) == 0 ? gram_entry_patterns(ent) : 0u; }
 
 
 // a row: how many bytes it holds, the fill rule, and the byte at pattern position i, gram_first(m) <= i <= m - 1
-__host__ __device__ inline uint32_t tail_stored(uint32_t m) { return m - gram_first(m); }
+__host__ __device__ constexpr uint32_t tail_stored(uint32_t m) { return m - gram_first(m); }
 static_assert(kGramCap + 1 <= kTailRow && kTailRow % 16 == 0, "a row holds kGramCap grams and is padded to 16 bytes");
 __host__ __device__ inline void tail_fill(uint8_t* row, const uint8_t* P, uint32_t m)
 {
     const uint32_t first = gram_first(m), n = tail_stored(m);
     for (uint32_t j = 0; j < kTailRow; ++j) row[j] = j < n ? P[first + j] : (uint8_t)0;
 }
+// (a row of any stride: what is stored lies at its front)
 __host__ __device__ inline uint32_t tail_at(const uint8_t* row, uint32_t m, uint32_t i) { return row[(int32_t)i - (int32_t)gram_first(m)]; }
 // the gram at pattern positions i and i + 1 in ONE read of two bytes (they are neighbours in the row, at any
 // alignment): position i in the low byte.  gram_first(m) <= i <= m - 2
@@ -89,6 +103,28 @@ __host__ __device__ inline uint32_t tail_gram_at(const uint8_t* row, uint32_t m,
     uint16_t two;
     __builtin_memcpy(&two, row + ((int32_t)i - (int32_t)gram_first(m)), 2);
     return two;
+}
+
+// A pass stores a row at its own length, rounded to 16, and takes as many patterns as the area has room for: two
+// pointers and a row each.  96 up to m = 16, 84 up to m = 32, 63 up to m = 48, 50 up to m = 64, 42 beyond.
+__host__ __device__ constexpr uint32_t tail_stride(uint32_t m) { return (tail_stored(m) + 15u) & ~15u; }
+__host__ __device__ constexpr uint32_t pass_width(uint32_t m)
+{
+    return kMultiArea / (16u + tail_stride(m)) < (uint32_t)kPassMax ? kMultiArea / (16u + tail_stride(m)) : (uint32_t)kPassMax;
+}
+static_assert(tail_stride(3) == 16 && tail_stride(4096) == kTailRow && pass_width(16) == 96 && pass_width(17) == 84 && pass_width(32) == 84 &&
+              pass_width(64) == 50 && pass_width(65) == 42 && pass_width(4096) == 42 && pass_width(65) >= (uint32_t)kMultiMax,
+              "every length has room for the 32 patterns smartgpu_coalesce_wide may ask for");
+// where the parts of the area lie for a pass of length m (W = pass_width(m)); g < W
+__host__ __device__ inline uint32_t multi_blob_at(uint32_t g) { return 8u * g; }
+__host__ __device__ inline uint32_t multi_count_at(uint32_t W, uint32_t g) { return 8u * W + 8u * g; }
+__host__ __device__ inline uint32_t multi_rows_at(uint32_t W) { return 16u * W; }
+// put pattern g's pointers and its row (kTailRow bytes, as tail_fill leaves them) into a pass's arguments
+inline void multi_set(MultiArgs& a, uint32_t g, const uint8_t* blob, unsigned long long* count, const uint8_t* row)
+{
+    __builtin_memcpy(a.area + multi_blob_at(g), &blob, 8);
+    __builtin_memcpy(a.area + multi_count_at(a.width, g), &count, 8);
+    __builtin_memcpy(a.area + multi_rows_at(a.width) + g * a.stride, row, a.stride);
 }
 
 // The launcher of k_horm.hip, reached through a pointer that the unit's own static initialiser sets: api.cpp holds

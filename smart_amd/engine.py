@@ -98,6 +98,7 @@ def _load(path):
         "smartgpu_tune": (i32, [i32, i32]),
         "smartgpu_coalesce": (i32, [i32]),
         "smartgpu_coalesce_wide": (i32, [i32]),
+        "smartgpu_coalesce_pass": (i32, [i32]),
         "smartgpu_coalesce_stats": (i32, [i32, C.POINTER(u64), C.POINTER(u64)]),
         "smartgpu_mtext_upload": (vp, [vp, u64, i32, vp]),
         "smartgpu_mtext_generate": (vp, [u64, i32, u64, i32, vp]),
@@ -819,8 +820,26 @@ def coalesce(max_group):
 
 
 def coalesce_wide(max_group):
-    """coalesce() over the setting's whole range (0: none, 2..32); returns the previous value as it was."""
+    """coalesce() up to 32 (0: none, 2..32); returns the previous value, a wider one (coalesce_pass) as 32."""
     prev = lib().smartgpu_coalesce_wide(max_group)
+    if prev < 0:
+        raise _err("coalesce")
+    return prev
+
+
+PASS_MAX = 96
+
+
+def pass_width(m):
+    """The most patterns of length m one pass takes: two pointers and the pattern's last min(m, 65) bytes, rounded
+    to 16, for each of them in 4032 bytes of kernel arguments (smart_amd/csrc/multi.hpp: pass_width)."""
+    return min(PASS_MAX, 4032 // (16 + (min(m, 65) + 15) // 16 * 16))
+
+
+def coalesce_pass(max_group):
+    """coalesce() over the setting's whole range (0: none, 2..96; clipped per pattern length to pass_width(m));
+    returns the previous value as it was."""
+    prev = lib().smartgpu_coalesce_pass(max_group)
     if prev < 0:
         raise _err("coalesce")
     return prev

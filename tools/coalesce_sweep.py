@@ -7,8 +7,11 @@
 Per cell: --plans Horspool plans (patterns cut from the text at bench.py's seeded offsets) are launched between two HIP
 events on the launch stream, --rounds times; the cell is the median round in ms per pattern, with the best and the worst.
 group 0 = smartgpu_coalesce(0): every launch a hor_scan of its own; wgs 0 = the library's default (smartgpu_tune(4, 0)).
-Groups above 8 go through smartgpu_coalesce_wide (a library without it skips them); give --plans a multiple of every
-group, 96 for 8, 16, 24 and 32, or the last pass of a round is a partial one.
+Groups above 8 go through smartgpu_coalesce_wide and groups above 32 through smartgpu_coalesce_pass (a library without the
+call skips them); a group above what a pass of the length takes (engine.pass_width(m)) is clipped by the library, so
+--groups 96 is the widest pass at every length.  Give --plans a multiple of every group, 96 for 8, 16, 24 and 32, 168
+for the widest pass at m = 32, or the last pass of a round is a partial one.  A cell also gives the kernels a round
+took (smartgpu_coalesce_stats; with groups above 32 a gathering key may be sent early) and the ms per kernel.
 One line per cell, and all cells as JSON in --out.  Every count is compared with the group-0 count of the same pattern."""
 import argparse
 import json
@@ -49,7 +52,8 @@ def main():
     text = Text.generate(SEED, args.sigma, n)
     engine.probe_read_gbs(text, reps=64)  # clocks
     wide = hasattr(engine.lib(), "smartgpu_coalesce_wide")
-    set_group = engine.coalesce_wide if wide else engine.coalesce
+    full = hasattr(engine.lib(), "smartgpu_coalesce_pass")
+    set_group = engine.coalesce_pass if full else engine.coalesce_wide if wide else engine.coalesce
     default_group = set_group(8)
     cells = []
     print("library %s, default group %d" % (engine.LIB_PATH, default_group))
@@ -67,13 +71,15 @@ def main():
             for wgs in ints(args.wgs):
                 if group == 0 and wgs != 0:
                     continue  # tune key 4 is the shared pass's
-                if group > 8 and not wide:
+                if (group > 8 and not wide) or (group > 32 and not full):
                     continue
                 set_group(group)
                 engine.tune(4, wgs)
                 for pl in plans:
                     pl.reset()
                 rounds = []
+                engine.device_sync(0)
+                passes0 = engine.coalesce_stats(0)[1]
                 for r in range(args.rounds + 1):  # round 0 warms up
                     engine.stream_mark(0, 0)
                     for pl in plans:
@@ -81,16 +87,18 @@ def main():
                     engine.stream_mark(0, 1)
                     rounds.append(engine.stream_elapsed_ms(0) / len(plans))
                 engine.device_sync(0)
+                passes = (engine.coalesce_stats(0)[1] - passes0) / (args.rounds + 1)
                 got = [pl.result(0)[0] for pl in plans]
                 if want is None:
                     want = got
                 ok = got == want and all(c >= args.rounds + 1 and c % (args.rounds + 1) == 0 for c in got)
                 rounds = sorted(rounds[1:])
                 cell = {"m": m, "group": group, "wgs": wgs, "ms": round(rounds[len(rounds) // 2], 5), "best": round(rounds[0], 5),
-                        "worst": round(rounds[-1], 5), "count_ok": ok}
+                        "worst": round(rounds[-1], 5), "passes": round(passes, 2), "count_ok": ok}
+                cell["ms_per_pass"] = round(cell["ms"] * len(plans) / passes, 5)
                 cells.append(cell)
-                print("m %-4d group %-2d wgs %d  %.5f ms per pattern (best %.5f worst %.5f)  %s"
-                      % (m, group, wgs, cell["ms"], cell["best"], cell["worst"], "ok" if ok else "COUNT MISMATCH"), flush=True)
+                print("m %-4d group %-2d wgs %d  %.5f ms per pattern (best %.5f worst %.5f)  %.2f passes, %.4f ms each  %s"
+                      % (m, group, wgs, cell["ms"], cell["best"], cell["worst"], passes, cell["ms_per_pass"], "ok" if ok else "COUNT MISMATCH"), flush=True)
         for pl in plans:
             pl.free()
     engine.tune(4, 0)
