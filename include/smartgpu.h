@@ -103,6 +103,12 @@ int smartgpu_text_read(const smartgpu_text *t, uint64_t off, uint64_t len, void 
  * once per run as well; a text is never written afterwards).  The runs kernels use it: on a text of at most four
  * distinct values they take four bytes per table step. */
 int smartgpu_text_alphabet(const smartgpu_text *t, uint32_t bits[8]);
+/* How often two symbols of the text are equal: sum c (c - 1) / (N (N - 1)) over the byte histogram of a sample of N
+ * bytes, taken on the device in the same pass as the alphabet — 16-byte chunks at an even stride, at most 2^20 of
+ * them; a text of up to 16 MiB is counted whole.  rand128 gives 1/128, rand32 1/32, English about 0.066.  *rate is -1
+ * where there is none: an empty or one-byte text, or one that the plugin-shape calls below upload for a single search.
+ * smartgpu_plan_launch() asks it before a pattern whose own symbols repeat may share a pass. */
+int smartgpu_text_repeat_rate(const smartgpu_text *t, double *rate);
 
 /* ---- searching -------------------------------------------------------- */
 /* Counts the occurrences of P[0..m) whose window lies inside text[off..off+n),
@@ -181,7 +187,12 @@ void smartgpu_plan_free(smartgpu_plan *p);
  * one pattern length may be held back until smartgpu_coalesce() of them have
  * gathered and then run as ONE pass over the text (hor_multi_scan); the counts
  * are the same; launches that are held back may run after later launches that are
- * not (counts are added, so the order decides nothing).  A launch is complete no later than the next
+ * not (counts are added, so the order decides nothing).  A pattern whose own symbols
+ * repeat (it would run on hor_scan's verifying form, alone) is held back as well where
+ * the TEXT's symbols do not — smartgpu_text_repeat_rate() at most 1/48 — and a key is
+ * already gathering for its text, range and length: it rides in that key's pass, opens
+ * none of its own and does not count toward smartgpu_coalesce(); with no such key, on
+ * any other text, or timed, it is sent at once as before.  A launch is complete no later than the next
  * smartgpu_device_sync(), smartgpu_plan_result() or smartgpu_stream_mark() on its
  * device; every other call that waits for, times, resets or frees what the launch
  * touches sends it first as well.  A caller who synchronises by other means (the
@@ -298,6 +309,11 @@ int smartgpu_coalesce_pass(int max_group);
 /* Of the launches on `device` that could share a pass: how many were seen, and how many kernels were sent for them
  * (equal when nothing was coalesced).  Either pointer may be NULL. */
 int smartgpu_coalesce_stats(int device, uint64_t *launches, uint64_t *passes);
+/* How many launches on `device` rode in a pass that was gathering beside them (smartgpu_plan_launch: a pattern whose
+ * symbols repeat, over a text whose symbols do not).  They are not among the `launches` above, and a pass that carries
+ * them is counted in `passes` once, as any kernel sent; a key is sent when its other launches reach the coalesce setting
+ * or when launches and riders together fill the room a pass of their length has. */
+int smartgpu_coalesce_riders(int device, uint64_t *riders);
 
 /* Host-side preprocessing exposed for tests (same tables the kernels stage in
  * LDS): writes up to `cap` 32-bit entries, returns the number written or <0.

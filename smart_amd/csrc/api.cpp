@@ -32,6 +32,7 @@
 #include "planes_host.hpp"
 #include "route.hpp"
 #include "tables.hpp"
+#include "text_rate.hpp"
 
 namespace {
 
@@ -175,6 +176,10 @@ struct smartgpu_text {
     uint32_t alphabet[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t four_shift = 7, four_symtab = 0, one_bit = 0xFF;
     sg::TextCodes codes() const { sg::TextCodes c; c.shift = four_shift; c.symtab = four_symtab; c.one = one_bit; return c; }
+    // how often two of its symbols are equal, from a byte histogram of a sample taken in the same pass (text_rate.hpp);
+    // -1: none (text_no_alphabet, a text of fewer than two bytes).  What queue_launch asks before a pattern whose own
+    // symbols repeat may ride in a shared pass.
+    double rate = -1.0;
 };
 
 struct smartgpu_plan {
@@ -240,14 +245,27 @@ constexpr size_t kAlphabetScratchOff = 64;
 static_assert(kAlphabetScratchOff + 32 <= sg::kFrontPad - (SMARTGPU_XSIZE + 256), "the scratch must lie below every byte a scan can read");
 static_assert(sg::kHitSlotsOff >= kAlphabetScratchOff + 32 && sg::kHitSlotsOff + sg::kHitSlots * 128 <= sg::kFrontPad - (SMARTGPU_XSIZE + 256),
               "flush_hits' staging slots lie between the scratch and the bytes a scan can read");
+// The byte histogram of the text's sample (text_rate.hpp) is taken behind it on the same stream and read back before the
+// same synchronisation.  Its 2 KB of counters do NOT fit the pad (the asserts above leave the scratch 32 bytes): they
+// are a device allocation of this call, released before it returns.
 bool text_alphabet(smartgpu_text* t, DeviceCtx* d)
 {
     uint32_t* dev = reinterpret_cast<uint32_t*>(t->base + kAlphabetScratchOff);
+    uint64_t hist[256] = {};
+    unsigned long long* dev_hist = nullptr;
+    const bool with_rate = sg::g_text_histogram && sg::rate_sample(t->n).bytes() >= 2;
     hipError_t e = hipMemsetAsync(dev, 0, 32, d->stream);
+    if (e == hipSuccess && with_rate) e = hipMalloc(reinterpret_cast<void**>(&dev_hist), sizeof hist);
+    if (e == hipSuccess && with_rate) e = hipMemsetAsync(dev_hist, 0, sizeof hist, d->stream);
     if (e == hipSuccess && t->n) e = sg::launch_text_alphabet(t->data(), t->n, dev, d->num_cus, d->stream);
+    if (e == hipSuccess && with_rate) e = static_cast<hipError_t>(sg::g_text_histogram(t->data(), t->n, dev_hist, d->num_cus, d->stream));
     if (e == hipSuccess) e = hipMemcpyAsync(t->alphabet, dev, 32, hipMemcpyDeviceToHost, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e == hipSuccess && with_rate) e = hipMemcpyAsync(hist, dev_hist, sizeof hist, hipMemcpyDeviceToHost, d->stream);
+    const hipError_t synced = hipStreamSynchronize(d->stream);  // (also after a failure: nothing may still write to hist)
+    if (e == hipSuccess) e = synced;
+    if (dev_hist) (void)hipFree(dev_hist);
     if (e != hipSuccess) { set_error("text_alphabet failed: %s", hipGetErrorString(e)); return false; }
+    t->rate = with_rate ? sg::text_repeat_rate(hist) : -1.0;
     if (!sg::four_symbol_codes(t->alphabet, &t->four_shift, &t->four_symtab)) t->four_shift = 7;
     // one-bit codes of a text of at most two byte values: the lowest bit in which they differ (one value: bit 0)
     t->one_bit = 0xFF;
@@ -282,6 +300,7 @@ bool text_no_alphabet(smartgpu_text* t, DeviceCtx* d)
     t->four_shift = 7;
     t->four_symtab = 0;
     t->one_bit = 0xFF;
+    t->rate = -1.0;  // not measured either: no pattern whose symbols repeat rides in a pass over this text
     for (uint32_t& wv : t->alphabet) wv = 0xFFFFFFFFu;  // unknown: every byte value may occur
     const uint32_t words[3] = {7u, 0u, 0xFFu};
     if (hipMemcpyAsync(t->base, words, 12, hipMemcpyHostToDevice, d->stream) != hipSuccess || hipStreamSynchronize(d->stream) != hipSuccess) {
@@ -680,14 +699,19 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // profiles/coalesce/RESULTS.md.)  Every
 // entry point that waits for, times, orders work on, or frees what is on the device's stream sends what is pending
 // first (flush_queue), in arrival order; a launch that is alone by then goes through launch_scan as it always did.
-// An untimed launch that cannot share a pass (another algorithm, a pattern whose symbols repeat) is no such entry point:
-// it is sent at once, ahead of what is pending, and a key goes on gathering its launches across it.
+// An untimed launch that cannot share a pass (another algorithm, a pattern whose symbols repeat over a text whose symbols
+// repeat as well, or with no key gathering for it) is no such entry point: it is sent at once, ahead of what is pending,
+// and a key goes on gathering its launches across it.  A pattern whose symbols repeat over a text where symbols do NOT
+// (the text's measured rate, text_rate.hpp) RIDES in the key that is gathering for its text, range and length: the rules
+// stand at queue_launch.  Such a launch used to read the whole text for one pattern, a quarter of the flagship's reads
+// and nearly all of them at m = 8 and 16 (profiles/coalesce/RESULTS.md).
 // The queue holds device pointers of plans and texts: smartgpu_plan_free, _plan_set_result_buffer and _text_free flush.
 // The plan's tail row is copied, not pointed to.
 struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; uint8_t tail[sg::kTailRow]; };
 struct QueuedKey {
     sg::ScanArgs key;  // text, s_begin, s_end, m, halo
-    uint32_t n = 0;
+    uint32_t n = 0;          // entries: streaming launches and riders
+    uint32_t streaming = 0;  // the streaming launches among them: what the coalesce setting counts
     QueuedScan scans[sg::kPassMax];
     bool holds(const sg::ScanArgs& a) const { return key.text == a.text && key.s_begin == a.s_begin && key.s_end == a.s_end && key.m == a.m && key.halo == a.halo; }
 };
@@ -699,6 +723,7 @@ struct LaunchQueue {
     void drop(uint32_t at) { for (--nkeys; at < nkeys; ++at) keys[at] = keys[at + 1]; }
     bool off = false;             // smartgpu_stream_handle gave the stream out: its holder orders their own work on it
     uint64_t launches = 0, passes = 0;  // eligible launches seen / kernels sent for them
+    uint64_t riders = 0;                // launches that rode in a key's pass (not among `launches`)
 };
 LaunchQueue g_queue[kMaxDevices];
 // launches per pass: 0 = off, 2..kPassMax.  ONE number with three calls: smartgpu_coalesce, the first, sets 0 or
@@ -716,9 +741,10 @@ hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
     hipError_t e = k.n ? hipSetDevice(d->device) : hipSuccess;
     if (e != hipSuccess) {
         k.n = 0;
+        k.streaming = 0;
         return e;
     }
-    if (k.n == 1) {
+    if (k.n == 1) {  // (a streaming launch: a rider never opens a key)
         e = sg::launch_scan(k.scans[0].algo, k.scans[0].a, d->num_cus, d->stream, k.scans[0].codes);
     } else if (k.n > 1) {
         sg::MultiArgs ma;  // (not zeroed: 4 KB, and the kernel reads the entries of np patterns only)
@@ -736,6 +762,7 @@ hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
     }
     if (k.n && e == hipSuccess) ++q.passes;
     k.n = 0;
+    k.streaming = 0;
     return e;
 }
 
@@ -780,25 +807,34 @@ DeviceCtx* device_ctx_flushed(int device)
 }
 
 // Queue the launch if it is one that can share a pass.  *queued = false: the caller launches it (after flush_queue).
+// A RIDER is a launch of the same route whose pattern's own symbols repeat (words.sparse == 0, m >= 8) over a text whose
+// measured rate says that they do not repeat THERE (text_rate: at most 1/48): its windows die on their first bytes like
+// a streaming pattern's, and hor_multi_scan compares whole windows, so it counts any pattern exactly.  A rider joins a
+// key that is already gathering for its (text, range, m, halo) and leaves with that key's pass; it never opens a key —
+// with none it is the caller's to launch, as before — so a text whose patterns all repeat never forms a pass of them.
+// It counts neither in `launches` nor toward the coalesce setting; it does take one of the pass_width(m) places a key has.
 hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words, const sg::ScanArgs& a, const sg::TextCodes& codes,
-                        const uint8_t (&tail)[sg::kTailRow], bool timed, bool* queued)
+                        double text_rate, const uint8_t (&tail)[sg::kTailRow], bool timed, bool* queued)
 {
     *queued = false;
-    if (a.s_end <= a.s_begin || !words.sparse) return hipSuccess;
+    if (a.s_end <= a.s_begin) return hipSuccess;
+    const bool rider = !words.sparse;
+    if (rider && (a.m < 8 || !sg::text_rate_streams(text_rate))) return hipSuccess;
     const sg::Route r = sg::route(algo, a.m, words, codes);
     if (r.to != sg::Launcher::hor || r.arg != 0) return hipSuccess;
     LaunchQueue& q = g_queue[d->device];
     std::lock_guard<std::mutex> lock(q.mu);
-    ++q.launches;
+    if (!rider) ++q.launches;
     const int G = g_coalesce.load(std::memory_order_relaxed);
     if (timed || G < 2 || q.off || !sg::g_hor_multi) {
-        ++q.passes;
+        if (!rider) ++q.passes;
         return hipSuccess;
     }
     hipError_t err = hipSuccess;
     uint32_t at = 0;
     while (at < q.nkeys && !q.keys[at].holds(a)) ++at;
     if (at == q.nkeys) {
+        if (rider) return hipSuccess;  // no key is gathering for it: alone, at once
         if (q.nkeys == LaunchQueue::kKeys) {
             err = send_key(d, q, q.keys[0]);
             q.drop(0);
@@ -806,16 +842,18 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
         at = q.nkeys++;
         q.keys[at].key = a;
         q.keys[at].n = 0;
+        q.keys[at].streaming = 0;
     }
-    QueuedKey& k = q.keys[at];
+    QueuedKey& k = q.keys[at];  // (has room: a key that reached its width was sent by the launch that filled it)
     QueuedScan& qs = k.scans[k.n++];
     qs.algo = algo;
     qs.a = a;
     qs.codes = codes;
     std::memcpy(qs.tail, tail, sg::kTailRow);
-    uint32_t width = sg::pass_width(a.m);  // (at most kPassMax, the room a key has)
-    if (static_cast<uint32_t>(G) < width) width = static_cast<uint32_t>(G);
-    if (k.n >= width) {
+    if (rider) ++q.riders; else ++k.streaming;
+    const uint32_t room = sg::pass_width(a.m);  // (at most kPassMax, the room a key has)
+    const uint32_t width = static_cast<uint32_t>(G) < room ? static_cast<uint32_t>(G) : room;
+    if (k.streaming >= width || k.n >= room) {
         const hipError_t e = send_key(d, q, k);
         if (e != hipSuccess && err == hipSuccess) err = e;
         q.drop(at);
@@ -829,6 +867,7 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
 namespace sg {
 hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // multi.hpp: set by k_horm.hip where that unit is linked
 hipError_t (*g_hor_preload)() = nullptr;  // launch_common.hpp: set by k_hor.hip where that unit is linked
+int (*g_text_histogram)(const uint8_t*, uint64_t, unsigned long long*, int, void*) = nullptr;  // text_rate.hpp: set by k_util.hip where that unit is linked
 // pedit.hpp: set by k_pedit.hip where that unit is linked
 hipError_t (*g_planes_edit_scan)(const PlaneEditArgs&, int, int, hipStream_t) = nullptr;
 hipError_t (*g_planes_edit_find)(const PlaneEditArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
@@ -970,6 +1009,13 @@ int smartgpu_text_alphabet(const smartgpu_text* t, uint32_t bits[8])
     return SMARTGPU_OK;
 }
 
+int smartgpu_text_repeat_rate(const smartgpu_text* t, double* rate)
+{
+    if (!t || !rate) { set_error("bad repeat_rate arguments"); return SMARTGPU_ERR_ARG; }
+    *rate = t->rate;
+    return SMARTGPU_OK;
+}
+
 int smartgpu_text_read(const smartgpu_text* t, uint64_t off, uint64_t len, void* host)
 {
     if (!t || !host || off > t->n || len > t->n - off) { set_error("bad text_read range"); return SMARTGPU_ERR_ARG; }
@@ -1044,13 +1090,14 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
     if (!d) return SMARTGPU_ERR_HIP;
     const sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(slot), text, off, n);
     bool queued = false;
-    HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), p->tail, timed != 0, &queued), return SMARTGPU_ERR_HIP);
+    HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), text->rate, p->tail, timed != 0, &queued), return SMARTGPU_ERR_HIP);
     if (queued) { p->timed[slot] = false; return SMARTGPU_OK; }
     HIP_TRY(hipSetDevice(p->device), return SMARTGPU_ERR_HIP);
     // A timed launch keeps its place behind what was queued before it: its events bracket this kernel alone.  Any other
     // launch that cannot share a pass goes ahead of what is pending: counts are ADDED to their slots, in any order, and
     // sending a half-filled key here costs its launches a pass of their own over the text.  (One m = 32 pattern in the
-    // 250 of bench.py repeats its symbols: it used to turn the 25 passes of the 200 timed launches into 26 and a solo scan.)
+    // 250 of bench.py repeats its symbols: it used to turn the 25 passes of the 200 timed launches into 26 and a solo scan;
+    // on that text it now rides in the pass that is gathering — queue_launch — and only without one comes here.)
     if (timed) HIP_TRY(flush_queue(d), return SMARTGPU_ERR_HIP);
     p->timed[slot] = timed != 0;
     if (timed) {
@@ -1199,6 +1246,14 @@ int smartgpu_coalesce_stats(int device, uint64_t* launches, uint64_t* passes)
     std::lock_guard<std::mutex> lock(g_queue[device].mu);
     if (launches) *launches = g_queue[device].launches;
     if (passes) *passes = g_queue[device].passes;
+    return SMARTGPU_OK;
+}
+
+int smartgpu_coalesce_riders(int device, uint64_t* riders)
+{
+    if (device < 0 || device >= kMaxDevices || !riders) { set_error("bad coalesce_riders arguments (device %d)", device); return SMARTGPU_ERR_ARG; }
+    std::lock_guard<std::mutex> lock(g_queue[device].mu);
+    *riders = g_queue[device].riders;
     return SMARTGPU_OK;
 }
 

@@ -34,10 +34,19 @@ namespace sg {
 // from the prologue to the end; blob[g] is read by the rare lane that completes a window in memory.
 // One instantiation; completion in memory (m - 1 > H) is a run-time branch of it, taken by rare candidates only: the
 // product library has a size to keep (tests/test_abi.py holds it below 0.7 of the A/B build).
-// Counts: an occurrence is rare for a streaming pattern (the only kind that gets here), so a lane adds each one straight
-// to its pattern's LDS counter, and at the end the workgroup adds every non-zero counter to that pattern's result slot.
-// A counter is a u32: a workgroup counts at most one occurrence per window end, and the launcher gives no workgroup
-// more than 2^17 tiles of 2^14 window ends (launch_hor_multi).
+// Counts: a lane adds each occurrence straight to its pattern's LDS counter, and at the end the workgroup adds every
+// non-zero counter to that pattern's result slot.  For a streaming pattern an occurrence is rare.  Not every pattern
+// of a pass is one: a RIDER (api.cpp queue_launch) is a pattern whose own symbols repeat, over a text whose symbols do
+// not, and it may occur often — a planted periodic run gives an occurrence every period, several to a lane's 64 window
+// ends and in every lane of a wave.  Nothing here needs occurrences to be rare for the count to be right:
+//  * A counter is a u32 PER PATTERN: a workgroup counts at most one occurrence per window end and pattern, and the
+//    launcher gives no workgroup more than 2^17 tiles of 2^14 window ends (launch_hor_multi), so 2^31 bounds it however
+//    often the pattern occurs.  The same pattern twice in a pass has two counters.
+//  * A lane parks ONE candidate per tile for the wave-wide compare (the first whose end matched in LDS) and completes
+//    every further one itself (global_equal): parking is a choice of who does the compare, no candidate is dropped.
+//  * horm_wave_verify takes the parked lanes one at a time, each with its own text and pattern pointer, so a wave in
+//    which all 64 lanes have parked does 64 compares; frequent occurrences cost time there, not correctness.
+// Many adds to one LDS counter serialise, which is what a frequent rider pays (tests/test_coalesce_ride_gpu.py has one).
 // Not through the staging slots of flush_hits: those assume ONE flush per grid, and here a grid flushes np sums.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kHormHead = kGramSlots + 4 * (kGramBuckets + 2 * kPassMax);  // the table, the heads, the links and the sums

@@ -1,7 +1,8 @@
-// k_util.hip — corpus kernels: generate_text, tile_fill, text_alphabet, probe_read
+// k_util.hip — corpus kernels: generate_text, tile_fill, text_alphabet, text_histogram, probe_read
 // (one translation unit per kernel family: dev_common.hpp)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
+#include "text_rate.hpp"
 
 namespace sg {
 
@@ -89,6 +90,47 @@ hipError_t launch_text_alphabet(const uint8_t* text, uint64_t n, uint32_t* out, 
     hipLaunchKernelGGL(text_alphabet, dim3(grid), dim3(256), 0, stream, text, n, out);
     return hipGetLastError();
 }
+
+// How often each byte value occurs in a SAMPLE of the text (text_rate.hpp: `chunks` chunks of 16 bytes, chunk_step / 2^20 chunks
+// apart, and `tail` bytes from tail_at on where the text is counted whole): taken with the alphabet, when a text is
+// created.  Every workgroup counts in LDS — at most 2^20 chunks in all, so a u32 counter holds — and adds each non-zero
+// counter to out[256] with one 64-bit atomic.  (A text of ONE byte value puts all 64 lanes of every LDS add on one
+// counter; the sample is 16 MiB at the most, and creating such a text was measured: profiles/coalesce/RESULTS.md.)
+__global__ __launch_bounds__(256) void text_histogram(const uint8_t* text, uint64_t chunks, uint64_t chunk_step, uint64_t tail_at, uint32_t tail,
+                                                      unsigned long long* out)
+{
+    __shared__ uint32_t hist[256];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < chunks; i += step) {
+        const uint4 v = ld_stream16(text + 16 * rate_chunk_at(i, chunk_step));
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 16; ++q) atomicAdd(hist + ((d[q >> 2] >> (8 * (q & 3))) & 0xFFu), 1u);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < tail) atomicAdd(hist + text[tail_at + threadIdx.x], 1u);
+    __syncthreads();
+    if (hist[threadIdx.x] != 0) atomicAdd(out + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
+}
+
+static int launch_text_histogram(const uint8_t* text, uint64_t n, unsigned long long* out, int num_cus, void* stream)
+{
+    const RateSample s = rate_sample(n);
+    if (s.bytes() == 0) return hipSuccess;
+    const uint64_t want = (s.chunks + 255) / 256;
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)num_cus * 8));
+    hipLaunchKernelGGL(text_histogram, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), text, s.chunks, s.step,
+                       s.chunks * kRateChunk, s.tail, out);
+    return hipGetLastError();
+}
+
+// api.cpp measures a text's rate only once this unit is part of the program (as k_horm.hip registers its launcher)
+namespace {
+struct RegisterTextHistogram {
+    RegisterTextHistogram() { g_text_histogram = &launch_text_histogram; }
+} g_register_text_histogram;
+}  // namespace
 
 // Streaming-read probe: the practical HBM read ceiling of this device for the
 // access pattern the scan kernels use (coalesced 16 B/lane, 8 loads in flight per

@@ -76,6 +76,7 @@ def _load(path):
         "smartgpu_text_device": (i32, [vp]),
         "smartgpu_text_read": (i32, [vp, u64, u64, vp]),
         "smartgpu_text_alphabet": (i32, [vp, vp]),
+        "smartgpu_text_repeat_rate": (i32, [vp, C.POINTER(C.c_double)]),
         "smartgpu_search64": (i32, [i32, vp, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_search_batch64": (i32, [i32, vp, u32, u32, vp, u64, u64, vp, vp, vp, C.POINTER(C.c_double)]),
         "smartgpu_search_batch64_each": (i32, [i32, vp, u32, u32, vp, u64, u64, vp, vp, vp, C.POINTER(C.c_double)]),
@@ -100,6 +101,7 @@ def _load(path):
         "smartgpu_coalesce_wide": (i32, [i32]),
         "smartgpu_coalesce_pass": (i32, [i32]),
         "smartgpu_coalesce_stats": (i32, [i32, C.POINTER(u64), C.POINTER(u64)]),
+        "smartgpu_coalesce_riders": (i32, [i32, C.POINTER(u64)]),
         "smartgpu_mtext_upload": (vp, [vp, u64, i32, vp]),
         "smartgpu_mtext_generate": (vp, [u64, i32, u64, i32, vp]),
         "smartgpu_mtext_free": (None, [vp]),
@@ -226,6 +228,14 @@ class Text:
         if lib().smartgpu_text_alphabet(self._h, bits.ctypes.data) != 0:
             raise _err("text_alphabet")
         return [c for c in range(256) if (int(bits[c >> 5]) >> (c & 31)) & 1]
+
+    def repeat_rate(self):
+        """How often two symbols of the text are equal (from a byte histogram of a sample, taken on the device when the
+        text was created), or None where the text has no rate."""
+        rate = C.c_double(-1.0)
+        if lib().smartgpu_text_repeat_rate(self._h, C.byref(rate)) != 0:
+            raise _err("text_repeat_rate")
+        return rate.value if rate.value >= 0 else None
 
     def pattern(self, k, m):
         """P = T[k..k+m), as setOfRandomPatterns cuts it (smart.c:148-158)."""
@@ -851,6 +861,15 @@ def coalesce_stats(device=0):
     if lib().smartgpu_coalesce_stats(device, C.byref(launches), C.byref(passes)) != 0:
         raise _err("coalesce_stats")
     return int(launches.value), int(passes.value)
+
+
+def coalesce_riders(device=0):
+    """Launches on `device` so far that rode in a pass gathering beside them: patterns whose own symbols repeat, over a
+    text whose symbols do not (Text.repeat_rate() at most 1/48).  They are not among coalesce_stats()' launches."""
+    riders = C.c_uint64(0)
+    if lib().smartgpu_coalesce_riders(device, C.byref(riders)) != 0:
+        raise _err("coalesce_riders")
+    return int(riders.value)
 
 
 def kernel_for(algo, P):

@@ -19,7 +19,7 @@ UNITS = {
     "k_so": ("k_so.hip", "runs_common.hpp"),
     "k_kmp": ("k_kmp.hip", "runs_common.hpp"),
     "k_packed": ("k_packed.hip",),
-    "k_util": ("k_util.hip",),
+    "k_util": ("k_util.hip", "text_rate.hpp"),
     "k_planes": ("k_planes.hip", "planes.hpp"),
     "k_pedit": ("k_pedit.hip", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_peditl": ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp"),
@@ -28,7 +28,7 @@ UNITS = {
 KERNEL_UNIT = {
     "hor_scan": "k_hor", "hor_multi_scan": "k_horm", "hor_scan_bp": "k_hor", "hor_scan_gram": "k_horg", "bm_scan_gram": "k_bmg", "bm_scan": "k_bm", "bndm_scan": "k_bndm", "sbndm_scan": "k_bndmx",
     "bndml_scan": "k_bndmx", "so_runs": "k_so", "kmp_runs": "k_kmp", "packed_scan": "k_packed", "packed_find": "k_packed",
-    "generate_text": "k_util", "tile_fill": "k_util", "text_alphabet": "k_util", "probe_read": "k_util",
+    "generate_text": "k_util", "tile_fill": "k_util", "text_alphabet": "k_util", "text_histogram": "k_util", "probe_read": "k_util",
     "planes_pack": "k_planes", "planes_scan": "k_planes", "planes_find": "k_planes",
     "planes_sets_scan": "k_planes", "planes_sets_find": "k_planes",
     "planes_mis_scan": "k_planes", "planes_mis_find": "k_planes",

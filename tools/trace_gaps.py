@@ -31,8 +31,11 @@ def main():
     order = sorted(region, key=lambda t: t[1])
     gaps = sorted((b[1] - a[2]) / 1e3 for a, b in zip(order, order[1:]))
     q = lambda f: gaps[min(len(gaps) - 1, int(f * len(gaps)))]  # noqa: E731
-    print("end(k) -> begin(k+1) over %d boundaries, us: min %.2f  p25 %.2f  median %.2f  p75 %.2f  max %.2f  sum %.1f"
-          % (len(gaps), gaps[0], q(0.25), statistics.median(gaps), q(0.75), gaps[-1], sum(gaps)))
+    if gaps:
+        print("end(k) -> begin(k+1) over %d boundaries, us: min %.2f  p25 %.2f  median %.2f  p75 %.2f  max %.2f  sum %.1f"
+              % (len(gaps), gaps[0], q(0.25), statistics.median(gaps), q(0.75), gaps[-1], sum(gaps)))
+    else:
+        print("end(k) -> begin(k+1): no boundary, the region is one dispatch")
     span = (max(e for _, _, e, _ in region) - order[0][1]) / 1e3
     total = sum(e - s for _, s, e, _ in region) / 1e3
     print("sum of durations %.1f us, first begin -> last end %.1f us (%.1f us of it with no scan kernel; negative: dispatches overlap)" % (total, span, span - total))
