@@ -358,7 +358,7 @@ smartgpu_ptext *smartgpu_ptext_upload(const void *host, uint64_t n, int device);
 void smartgpu_ptext_free(smartgpu_ptext *t);
 uint64_t smartgpu_ptext_length(const smartgpu_ptext *t); /* symbols */
 int smartgpu_ptext_device(const smartgpu_ptext *t);
-int smartgpu_ptext_planes(const smartgpu_ptext *t);      /* 1 or 2 */
+int smartgpu_ptext_planes(const smartgpu_ptext *t);      /* 1 or 2 (3: a text of the ...8 constructors below) */
 uint64_t smartgpu_ptext_bytes(const smartgpu_ptext *t);  /* HBM bytes of the planes, pads excluded */
 /* returns k, the number of distinct values; values[code] = the byte value of each code, ascending */
 int smartgpu_ptext_symbols(const smartgpu_ptext *t, uint8_t values[4]);
@@ -401,7 +401,7 @@ int smartgpu_pfind_batch64(const uint8_t *const *P, uint32_t m, uint32_t K, cons
  * (ascending, relative to symbol 0) are those of smartgpu_psearch64 / smartgpu_pfind64.
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: sets == NULL, m = 0 or m > SMARTGPU_XSIZE, a NULL text,
  * a range outside the text, count == NULL, positions == NULL with cap > 0, and a set with a bit at or above the text's
- * number of values (bits 4..7 always are; the message names the position).
+ * number of values (bits 4..7 always are on one and two planes; the message names the position).
  * No launch: a position with the empty set (count 0, SMARTGPU_OK), m > n (count 0), a pattern of full sets (every start
  * position of the range; the find writes them when count <= cap).
  * MEASURED on an MI355X, 1 Gi symbols of rand4 and of rand2, m = 8 .. 256 (profiles/packed/RESULTS.md, "Set patterns"):
@@ -471,7 +471,7 @@ int smartgpu_pfind_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgp
  * count), mismatches == NULL and the order of the positions are those of smartgpu_psearch_mis64 / smartgpu_pfind_mis64.
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: sets == NULL, k > SMARTGPU_PMIS_MAX, m = 0 or
  * m > SMARTGPU_XSIZE, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0, and a set with a
- * bit at or above the text's number of values (bits 4..7 always are; the message names the position).
+ * bit at or above the text's number of values (bits 4..7 always are on one and two planes; the message names the position).
  * No launch: m > n (count 0), more empty sets than k (count 0).
  * NOT offered: a batch call, k > 7, byte texts.  (Insertions and deletions: smartgpu_psearch_sets_edit64 below.)
  * NOT measured: everything — no timing of these calls has been taken (tools/sets_mis_probe.py takes the three comparisons:
@@ -628,6 +628,58 @@ int smartgpu_pfind_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, uin
 int smartgpu_iupac_revcomp(const char *P, uint32_t m, char *out);
 /* smartgpu_probe_read_ms on the planes: the streaming-read time of the bytes a packed search reads (the plane roofline) */
 int smartgpu_ptext_probe_read_ms(const smartgpu_ptext *t, int reps, double *ms_per_pass);
+
+/* ---- packed texts of five to eight distinct byte values: THREE bit planes ---------------------------------------
+ * An assembly with N (ACGNT: five values), a multi-record text with a separator, RNA/DNA mixes and reduced protein
+ * alphabets do not fit two planes.  The ...8 constructors below pack such a text on three planes — plane b holds bit b of
+ * the code, codes are the ranks of the byte values that occur, ascending, as above — at 3/8 of the byte text's HBM bytes.
+ * For a text of at most FOUR values they produce exactly what smartgpu_ptext_pack / smartgpu_ptext_upload produce (one or
+ * two planes, served by the same kernels afterwards).  More than eight values: NULL, and a message that names the number.
+ * smartgpu_ptext_pack, smartgpu_ptext_upload, smartgpu_ptext_layout and smartgpu_iupac_sets are unchanged: they still
+ * refuse more than four values.
+ * The allocation is the two-plane one with a third plane, [front pad | plane 0 | back pad | plane 1 | back pad | plane 2 |
+ * back pad], every plane 256-byte aligned, zero-filled before the pack: pad and tail bits look like code 0 and are never
+ * counted.  smartgpu_ptext_planes answers 3, smartgpu_ptext_bytes 3 x the plane bytes; smartgpu_ptext_read and
+ * smartgpu_ptext_probe_read_ms work on three planes.  smartgpu_ptext_symbols (four entries) answers SMARTGPU_ERR_ARG on a
+ * three-plane text and names smartgpu_ptext_symbols8, which works on every packed text.
+ *
+ * OFFERED on a three-plane text, contract unchanged (ranges, count widths, times, cap / count / SMARTGPU_ERR_NOMEM,
+ * ascending positions relative to symbol 0 with distances, the no-launch cases, the SMARTGPU_ERR_ARG cases decided before
+ * any HIP call): smartgpu_psearch64, smartgpu_psearch_batch64, smartgpu_pfind64, smartgpu_pfind_batch64,
+ * smartgpu_psearch_sets64, smartgpu_pfind_sets64, smartgpu_psearch_mis64, smartgpu_pfind_mis64, smartgpu_psearch_sets_mis64,
+ * smartgpu_pfind_sets_mis64.  A set may carry bits up to nvalues - 1 <= 7; a bit at or above the text's number of values is
+ * refused and the message names the position.  All ten go through ONE kernel pair, planes3_scan / planes3_find
+ * (smart_amd/csrc/k_planes3.hip): an exact pattern travels as singleton sets; a set position costs three v_alignbit and
+ * three three-input bit operations per 32 start positions (five instructions for a singleton, two or three for a set that
+ * does not depend on plane 2, none for a position that accepts every value) where planes_scan takes three in all.
+ * BATCH calls on a three-plane text: a pattern takes eight membership planes (4256 bytes) in the staging buffer and the
+ * device arena instead of two code planes, so K <= 7884 per call (32 MiB / 4256); beyond: SMARTGPU_ERR_ARG before any HIP
+ * call, the message names the bound.
+ * NOT offered on a three-plane text: edit distance and alignments — the smartgpu_p*_edit64, smartgpu_p*_editl64 and
+ * smartgpu_palign_* calls answer SMARTGPU_ERR_ARG before any HIP call, and the message says so.  (The obvious follow-up:
+ * their match masks are per code already.)  Also not offered: more than eight values, byte texts.
+ * MEASURED on an MI355X, 1 Gi symbols, m = 8 .. 256 (profiles/packed/RESULTS.md, "Three planes"; tools/wide_probe.py), no
+ * threshold set in advance: exact count on rand4 over ACGT with one N takes 1.98-2.08 x the per-call time of the two-plane
+ * text of the same symbols (planes3_scan 2.15-2.37 x planes_scan's kernel time), smartgpu_psearch_mis64 at k = 1 / 3 / 7
+ * 1.88-2.06 / 1.80-1.97 / 1.68-1.87 x per call, outside the run-to-run spread in every cell.  Against the byte text's best of
+ * SO / BNDM / HOR for the same pattern on the same text: 1.27-1.42 x the symbols per second on ACGNT, 1.29-1.33 x on rand8 —
+ * the byte text is faster in no measured cell, but a three-plane text is NOT at the two-plane text's 2.7-3.9 x.  Packing:
+ * 0.66-0.68 ms per GiB of text.
+ * NOT measured: the find forms' speed, set patterns proper (the cells are byte patterns: singleton sets), six and seven
+ * values, texts beyond 1 Gi symbols, texts with long partial matches, other occupancies (every planes3 kernel is bounded for
+ * 128 VGPRs and launched at 5-7 workgroups per CU). */
+#define SMARTGPU_PTEXT_MAXVALUES 8
+/* smartgpu_ptext_layout for 1..8 values: 1 / 2 / 3 planes for at most 2 / 4 / 8.  SMARTGPU_ERR_ARG for nvalues < 1 or > 8. */
+int smartgpu_ptext_layout8(uint64_t n, int nvalues, int *planes, uint64_t *plane_bytes);   /* 1..8 values: 1 / 2 / 3 planes */
+smartgpu_ptext *smartgpu_ptext_pack8(const smartgpu_text *t);
+smartgpu_ptext *smartgpu_ptext_upload8(const void *host, uint64_t n, int device);
+/* returns k <= 8, the number of distinct values; values[code] = the byte value of each code, ascending (entries from k on: 0) */
+int smartgpu_ptext_symbols8(const smartgpu_ptext *t, uint8_t values[8]);
+/* smartgpu_iupac_sets, rule for rule, for 1 to 8 values.  A value of the text that is no base letter — 'N', a separator —
+ * stands for NO base, so no letter accepts it, pattern letter N included: AN UNKNOWN BASE OF THE TEXT MATCHES NOTHING (a
+ * pattern N accepts A, C, G and T; it does not accept the text's N).  Allow it with a mismatch (smartgpu_psearch_sets_mis64)
+ * or by setting its bit in sets[j] yourself. */
+int smartgpu_iupac_sets8(const uint8_t values[8], int nvalues, const char *P, uint32_t m, uint8_t *sets);
 
 #ifdef __cplusplus
 }

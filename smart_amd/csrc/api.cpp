@@ -30,6 +30,8 @@
 #include "palign.hpp"
 #include "planes.hpp"
 #include "planes_host.hpp"
+#include "planes3.hpp"
+#include "planes3_host.hpp"
 #include "route.hpp"
 #include "tables.hpp"
 #include "text_rate.hpp"
@@ -876,6 +878,10 @@ hipError_t (*g_planes_editl_scan)(const PlaneEditlArgs&, int, int, hipStream_t) 
 hipError_t (*g_planes_editl_find)(const PlaneEditlArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
 // palign.hpp: set by k_palign.hip where that unit is linked
 hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
+// planes3.hpp: set by k_planes3.hip where that unit is linked
+hipError_t (*g_planes3_pack)(const uint8_t*, uint64_t, uint32_t*, uint32_t*, uint32_t*, const uint8_t[7], hipStream_t) = nullptr;
+hipError_t (*g_planes3_scan)(const Plane3Args&, int, int, hipStream_t) = nullptr;
+hipError_t (*g_planes3_find)(const Plane3Args&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
 }
 
 extern "C" {
@@ -2012,13 +2018,14 @@ int smartgpu_build_table(int which, const uint8_t* P, uint32_t m, int32_t* out, 
 
 }  // extern "C"
 
-/* ---- packed texts: at most four byte values as bit planes (planes.hpp, k_planes.hip) ------------------------------ */
+/* ---- packed texts: at most four byte values as bit planes (planes.hpp, k_planes.hip), five to eight on three
+ * (planes3.hpp, k_planes3.hip) ------------------------------------------------------------------------------------- */
 struct smartgpu_ptext {
     int device = 0;
     uint64_t n = 0;            // symbols
-    int planes = 1;            // 1: at most two values, 2: three or four
+    int planes = 1;            // 1: at most two values, 2: three or four, 3: five to eight
     int nvalues = 0;
-    uint8_t values[4] = {0, 0, 0, 0};  // values[code], ascending
+    uint8_t values[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // values[code], ascending
     uint8_t* base = nullptr;   // allocation start; plane b at base + kFrontPad + b * plane_stride(n)
     uint32_t* plane(int b) const { return reinterpret_cast<uint32_t*>(base + sg::kFrontPad + static_cast<uint64_t>(b) * sg::plane_stride(n)); }
     uint64_t alloc_bytes() const { return sg::kFrontPad + static_cast<uint64_t>(planes) * sg::plane_stride(n); }
@@ -2048,6 +2055,33 @@ void plane_head(Args& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_
     a.count = d->batch_counts + k;
 }
 
+// plane_head for a three-plane text (Plane3Args: planes3.hpp)
+void plane_head(sg::Plane3Args& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint64_t off, uint64_t n, uint32_t k = 0)
+{
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(1);
+    a.p2 = text->plane(2);
+    a.s_begin = off;
+    a.s_end = off + n - m + 1;
+    a.m = m;
+    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
+    a.count = d->batch_counts + k;
+}
+
+// a.y of Plane3Args: the first dword of each of the eight membership planes at Y
+void set_words8(sg::Plane3Args& a, const uint32_t* Y)
+{
+    for (uint32_t c = 0; c < 8; ++c) a.y[c] = Y[c * sg::kPatWords];
+}
+
+// The calls on a three-plane text need k_planes3.hip in the program: a missing kernel is an error, never a fall-back.
+bool planes3_linked(const char* call)
+{
+    if (sg::g_planes3_scan && sg::g_planes3_find) return true;
+    set_error("%s: this program holds no planes3_scan / planes3_find kernel (k_planes3.hip is not linked)", call);
+    return false;
+}
+
 // What the kernels receive for pattern k of a set staged at host_pat (encode_pattern, 2 * kPatWords dwords per pattern)
 // and, for m > 32, at the same stride in the device's arena.
 sg::PlaneArgs plane_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* host_pat, uint32_t k, uint32_t m, uint64_t off, uint64_t n)
@@ -2060,11 +2094,73 @@ sg::PlaneArgs plane_args(const DeviceCtx* d, const smartgpu_ptext* text, const u
     return a;
 }
 
+// What planes3_scan / planes3_find receive for pattern k of a set staged at host_pat (encode_pattern8, kSet8Words dwords per
+// pattern) and, for m > 32, at the same stride in the device's arena: an exact pattern, singleton sets, budget 0.
+sg::Plane3Args plane3_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* host_pat, uint32_t k, uint32_t m, uint64_t off, uint64_t n)
+{
+    sg::Plane3Args a;
+    plane_head(a, d, text, m, off, n, k);
+    set_words8(a, host_pat + sg::kSet8Words * k);
+    a.budget = a.foreign = a.shift = 0;
+    a.pat += sg::kSet8Words * k;
+    return a;
+}
+
+// psearch_impl on a three-plane text (K <= kBatch3Max: checked by the callers before any HIP call): eight membership planes
+// per pattern in place of two code planes.
+int psearch3_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+                  uint64_t* counts, double* pre_ms, double* run_ms)
+{
+    if (!planes3_linked("psearch64")) return SMARTGPU_ERR_HIP;
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const double t_pre = now_ms();
+    constexpr size_t kPatBytes = 4 * sg::kSet8Words;
+    if (static_cast<size_t>(K) * kPatBytes > d->pinned_bytes) { set_error("psearch_batch: %u patterns exceed the staging buffer", K); return SMARTGPU_ERR_ARG; }
+    if (!batch_reserve(d, static_cast<size_t>(K) * kPatBytes, K)) return SMARTGPU_ERR_NOMEM;
+    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
+    uint32_t* host_pat = reinterpret_cast<uint32_t*>(d->pinned);
+    std::vector<uint8_t> present(K, 0);
+    for (uint32_t k = 0; k < K; ++k) {
+        if (!P[k]) { set_error("pattern %u is NULL", k); return SMARTGPU_ERR_ARG; }
+        present[k] = sg::encode_pattern8(text->values, text->nvalues, P[k], m, false, host_pat + sg::kSet8Words * k) == 0;
+    }
+    const bool fits = n >= m;  // m > n: no window fits, count 0
+    if (m > 32 && fits)
+        HIP_TRY(hipMemcpyAsync(d->arena, host_pat, static_cast<size_t>(K) * kPatBytes, hipMemcpyHostToDevice, d->stream), return SMARTGPU_ERR_HIP);
+    if (pre_ms) *pre_ms = now_ms() - t_pre;
+    const double t0 = now_ms();
+    HIP_TRY(hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream), return SMARTGPU_ERR_HIP);
+    for (uint32_t k = 0; k < K && fits; ++k) {
+        if (!present[k]) continue;
+        const sg::Plane3Args a = plane3_args(d, text, host_pat, k, m, off, n);
+        HIP_TRY(sg::g_planes3_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+    }
+    HIP_TRY(hipMemcpyAsync(d->pinned_counts, d->batch_counts, static_cast<size_t>(K) * 8, hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+    if (run_ms) *run_ms = now_ms() - t0;
+    for (uint32_t k = 0; k < K; ++k) {
+        // more occurrences than start positions: refused like a poisoned count, never reported
+        if (d->pinned_counts[k] > (fits ? n - m + 1 : 0)) { set_error("planes3_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[k], (unsigned long long)(fits ? n - m + 1 : 0)); return SMARTGPU_ERR_HIP; }
+        counts[k] = d->pinned_counts[k];
+    }
+    return SMARTGPU_OK;
+}
+
+// The batch calls' bound on a three-plane text (planes3.hpp: kBatch3Max), decided before any HIP call.
+int check_batch3(const char* call, const smartgpu_ptext* text, uint32_t K)
+{
+    if (text->planes != 3 || K <= sg::kBatch3Max) return SMARTGPU_OK;
+    set_error("%s: %u patterns on a three-plane text, at most %u per call (eight membership planes per pattern in the staging buffer)", call, K, sg::kBatch3Max);
+    return SMARTGPU_ERR_ARG;
+}
+
 // K patterns of m symbols: their planes to the device's arena (m > 32 only: shorter patterns travel as kernel arguments),
 // K launches back to back on the device's stream, ONE read-back.  A pattern with a byte the text does not hold: no launch.
 int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                  uint64_t* counts, double* pre_ms, double* run_ms)
 {
+    if (text->planes == 3) return psearch3_impl(P, m, K, text, off, n, counts, pre_ms, run_ms);
     DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     const double t_pre = now_ms();
@@ -2288,6 +2384,87 @@ uint32_t mis_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint3
     return foreign;
 }
 
+// ---- three-plane texts (planes3.hpp): the exact, set, mismatch and set-with-mismatch calls, count and find, through ONE
+// kernel pair.  The callers have made their own checks (check_psearch_args / check_pext_args) ----
+
+// The pattern — bytes, or sets when `sets` — as eight membership planes at Y[kSet8Words] and as a.y, a.foreign, a.budget for
+// k mismatches.  *none: more positions that accept nothing (empty sets, foreign bytes) than k, no start position is an
+// occurrence; *full: every position accepts every value.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
+int plane3_pattern(const smartgpu_ptext* t, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t* Y, sg::Plane3Args* a, bool* none,
+                   bool* full)
+{
+    uint32_t empty = 0;
+    *full = false;
+    if (sets) {
+        const int bad = sg::encode_sets8(t->nvalues, pat, m, true, Y, &empty, full);
+        if (bad >= 0) {
+            set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, pat[bad], t->nvalues);
+            return SMARTGPU_ERR_ARG;
+        }
+    } else {
+        empty = sg::encode_pattern8(t->values, t->nvalues, pat, m, true, Y);
+    }
+    *none = empty > k;
+    a->foreign = empty;
+    a->budget = *none ? 0 : k - empty;
+    a->shift = 0;
+    set_words8(*a, Y);
+    return SMARTGPU_OK;
+}
+
+// mis: the call takes k and reports distances (its no-launch cases are those of the two-plane mismatch calls: a pattern of
+// full sets is launched there, and answered without a launch by the set calls).
+int p3_count(const char* call, const uint8_t* pat, bool sets, bool mis, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+             uint64_t* count, double* pre_ms, double* run_ms)
+{
+    uint32_t Y[sg::kSet8Words];
+    sg::Plane3Args a;
+    bool none = false, full = false;
+    const int rc = plane3_pattern(text, pat, sets, m, k, Y, &a, &none, &full);
+    if (rc != SMARTGPU_OK) return rc;
+    if (none || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);
+    if (full && !mis) return pcount_done(n - m + 1, 0.0, 0.0, count, pre_ms, run_ms);
+    if (!planes3_linked(call)) return SMARTGPU_ERR_HIP;
+    return pcount_run(call, "planes3_scan", sg::g_planes3_scan, a, text, Y, sizeof Y, m, off, n, count, pre_ms, run_ms);
+}
+
+int p3_find(const char* call, const uint8_t* pat, bool sets, bool mis, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+            uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
+{
+    uint32_t Y[sg::kSet8Words];
+    sg::Plane3Args a;
+    bool none = false, full = false;
+    const int rc = plane3_pattern(text, pat, sets, m, k, Y, &a, &none, &full);
+    if (rc != SMARTGPU_OK) return rc;
+    if (none || m > n) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    if (full && !mis) {  // every start position of the range: no launch
+        const uint64_t total = n - m + 1;
+        *count = total;
+        if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+        for (uint64_t i = 0; i < total; ++i) positions[i] = off + i;
+        return SMARTGPU_OK;
+    }
+    if (!planes3_linked(call)) return SMARTGPU_ERR_HIP;
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, sizeof Y, 1)) return SMARTGPU_ERR_NOMEM;
+    a.shift = mis ? sg::kMisShift : 0u;
+    const int r = pfind_run(d, call, "planes3_find", sg::g_planes3_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count, a.shift);
+    if (mis && r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
+    return r;
+}
+
+// The edit-distance and alignment calls do not read a third plane.
+int refuse_planes3(const char* call, const smartgpu_ptext* text)
+{
+    if (text->planes != 3) return SMARTGPU_OK;
+    set_error("%s: three-plane texts (five to eight values) are not offered here: edit distance and alignments read one or two planes", call);
+    return SMARTGPU_ERR_ARG;
+}
+
 // ---- edit distance (pedit.hpp): END positions, n of them whatever m is, and m > n is legal — its own run path, so that
 // no bound of pcount_run / pfind_run (n - m + 1 start positions) changes ----
 
@@ -2299,6 +2476,7 @@ int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint3
     if (m < 1 || m > SMARTGPU_PEDIT_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_PEDIT_MAXM); return SMARTGPU_ERR_ARG; }
     if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
     if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
+    if (refuse_planes3(call, text) != SMARTGPU_OK) return SMARTGPU_ERR_ARG;
     if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
     if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
     return SMARTGPU_OK;
@@ -2424,6 +2602,7 @@ int check_peditl_args(const char* call, const char* what, const uint8_t* P, uint
     if (k > SMARTGPU_PEDITL_MAXK) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PEDITL_MAXK); return SMARTGPU_ERR_ARG; }
     if (flags & ~SMARTGPU_PEDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_PEDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_PEDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
     if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
+    if (refuse_planes3(call, text) != SMARTGPU_OK) return SMARTGPU_ERR_ARG;
     if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
     if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
     return SMARTGPU_OK;
@@ -2641,23 +2820,34 @@ int smartgpu_ptext_layout(uint64_t n, int nvalues, int* planes, uint64_t* plane_
     return SMARTGPU_OK;
 }
 
-smartgpu_ptext* smartgpu_ptext_pack(const smartgpu_text* t)
+int smartgpu_ptext_layout8(uint64_t n, int nvalues, int* planes, uint64_t* plane_bytes)
+{
+    if (nvalues < 1 || nvalues > SMARTGPU_PTEXT_MAXVALUES) { set_error("a packed text of the ...8 constructors holds 1 to %d distinct byte values, not %d", SMARTGPU_PTEXT_MAXVALUES, nvalues); return SMARTGPU_ERR_ARG; }
+    if (planes) *planes = nvalues <= 2 ? 1 : nvalues <= 4 ? 2 : 3;
+    if (plane_bytes) *plane_bytes = sg::plane_bytes(n);
+    return SMARTGPU_OK;
+}
+
+// smartgpu_ptext_pack (most = 4) and smartgpu_ptext_pack8 (most = 8): at most four values give one or two planes through
+// planes_pack either way, five to eight three planes through planes3_pack.
+static smartgpu_ptext* ptext_pack_impl(const smartgpu_text* t, int most)
 {
     if (!t) { set_error("text handle is NULL"); return nullptr; }
-    uint8_t values[4] = {255, 255, 255, 255};
+    uint8_t values[8] = {255, 255, 255, 255, 255, 255, 255, 255};
     int k = 0;
     for (int c = 0; c < 256; ++c)
         if (t->alphabet[c >> 5] >> (c & 31) & 1u) {
-            if (k < 4) values[k] = static_cast<uint8_t>(c);
+            if (k < 8) values[k] = static_cast<uint8_t>(c);
             ++k;
         }
-    if (k > 4) { set_error("the text holds %d distinct byte values: a packed text holds at most 4", k); return nullptr; }
+    if (k > most) { set_error("the text holds %d distinct byte values: a packed text holds at most %d", k, most); return nullptr; }
+    if (k > 4 && !sg::g_planes3_pack) { set_error("ptext_pack8: this program holds no planes3_pack kernel (k_planes3.hip is not linked)"); return nullptr; }
     DeviceCtx* d = device_ctx_flushed(t->device);
     if (!d) return nullptr;
     smartgpu_ptext* p = new smartgpu_ptext;
     p->device = t->device;
     p->n = t->n;
-    p->planes = k <= 2 ? 1 : 2;
+    p->planes = k <= 2 ? 1 : k <= 4 ? 2 : 3;
     p->nvalues = k;
     for (int i = 0; i < k; ++i) p->values[i] = values[i];
     if (hipMalloc(reinterpret_cast<void**>(&p->base), p->alloc_bytes()) != hipSuccess) {
@@ -2665,23 +2855,37 @@ smartgpu_ptext* smartgpu_ptext_pack(const smartgpu_text* t)
         delete p;
         return nullptr;
     }
-    const uint8_t above[3] = {values[0], values[1], values[2]};  // code = number of these below the byte (255: none is)
+    // code = number of these below the byte (255: none is)
     hipError_t e = hipMemsetAsync(p->base, 0, p->alloc_bytes(), d->stream);  // pads and tail bits are zero
-    if (e == hipSuccess) e = sg::launch_planes_pack(t->data(), t->n, p->plane(0), p->plane(p->planes - 1), p->planes, above, d->stream);
+    if (e == hipSuccess)
+        e = p->planes == 3 ? sg::g_planes3_pack(t->data(), t->n, p->plane(0), p->plane(1), p->plane(2), values, d->stream)
+                           : sg::launch_planes_pack(t->data(), t->n, p->plane(0), p->plane(p->planes - 1), p->planes, values, d->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
     if (e != hipSuccess) {
-        set_error("planes_pack failed: %s", hipGetErrorString(e));
+        set_error("%s failed: %s", p->planes == 3 ? "planes3_pack" : "planes_pack", hipGetErrorString(e));
         smartgpu_ptext_free(p);
         return nullptr;
     }
     return p;
 }
 
+smartgpu_ptext* smartgpu_ptext_pack(const smartgpu_text* t) { return ptext_pack_impl(t, 4); }
+smartgpu_ptext* smartgpu_ptext_pack8(const smartgpu_text* t) { return ptext_pack_impl(t, SMARTGPU_PTEXT_MAXVALUES); }
+
 smartgpu_ptext* smartgpu_ptext_upload(const void* host, uint64_t n, int device)
 {
     smartgpu_text* t = smartgpu_text_upload(host, n, device);
     if (!t) return nullptr;
     smartgpu_ptext* p = smartgpu_ptext_pack(t);
+    smartgpu_text_free(t);
+    return p;
+}
+
+smartgpu_ptext* smartgpu_ptext_upload8(const void* host, uint64_t n, int device)
+{
+    smartgpu_text* t = smartgpu_text_upload(host, n, device);
+    if (!t) return nullptr;
+    smartgpu_ptext* p = smartgpu_ptext_pack8(t);
     smartgpu_text_free(t);
     return p;
 }
@@ -2704,7 +2908,15 @@ uint64_t smartgpu_ptext_bytes(const smartgpu_ptext* t) { return t ? static_cast<
 int smartgpu_ptext_symbols(const smartgpu_ptext* t, uint8_t values[4])
 {
     if (!t || !values) { set_error("bad ptext_symbols arguments"); return SMARTGPU_ERR_ARG; }
+    if (t->planes == 3) { set_error("ptext_symbols: a three-plane text holds %d values, more than the four entries of this call: use smartgpu_ptext_symbols8", t->nvalues); return SMARTGPU_ERR_ARG; }
     std::memcpy(values, t->values, 4);
+    return t->nvalues;
+}
+
+int smartgpu_ptext_symbols8(const smartgpu_ptext* t, uint8_t values[8])
+{
+    if (!t || !values) { set_error("bad ptext_symbols8 arguments"); return SMARTGPU_ERR_ARG; }
+    std::memcpy(values, t->values, 8);
     return t->nvalues;
 }
 
@@ -2716,7 +2928,7 @@ int smartgpu_ptext_read(const smartgpu_ptext* t, uint64_t off, uint64_t len, voi
     if (!d) return SMARTGPU_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
     const uint64_t w0 = off / 32, nw = (off + len + 31) / 32 - w0;
-    std::vector<uint32_t> w[2];
+    std::vector<uint32_t> w[3];
     for (int b = 0; b < t->planes; ++b) {
         w[b].resize(nw);
         HIP_TRY(hipMemcpy(w[b].data(), t->plane(b) + w0, nw * 4, hipMemcpyDeviceToHost), return SMARTGPU_ERR_HIP);
@@ -2725,7 +2937,8 @@ int smartgpu_ptext_read(const smartgpu_ptext* t, uint64_t off, uint64_t len, voi
     for (uint64_t i = 0; i < len; ++i) {
         const uint64_t s = off + i - 32 * w0;
         uint32_t code = w[0][s >> 5] >> (s & 31) & 1u;
-        if (t->planes == 2) code |= (w[1][s >> 5] >> (s & 31) & 1u) << 1;
+        if (t->planes >= 2) code |= (w[1][s >> 5] >> (s & 31) & 1u) << 1;
+        if (t->planes == 3) code |= (w[2][s >> 5] >> (s & 31) & 1u) << 2;
         out[i] = t->values[code];
     }
     return SMARTGPU_OK;
@@ -2761,8 +2974,9 @@ int smartgpu_psearch_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, co
                              uint64_t* counts, double* batch_ms)
 {
     if (!P || K < 1 || !counts) { set_error("psearch_batch: P/counts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
-    const int rc = check_psearch_args(P[0], m, text, off, n);
+    int rc = check_psearch_args(P[0], m, text, off, n);
     if (rc != SMARTGPU_OK) return rc;
+    if ((rc = check_batch3("psearch_batch", text, K)) != SMARTGPU_OK) return rc;
     double pre = 0.0, run = 0.0;
     const int r = psearch_impl(P, m, K, text, off, n, counts, &pre, &run);
     if (r != SMARTGPU_OK) return r;
@@ -2779,6 +2993,7 @@ int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, u
     const int rc = check_psearch_args(P, m, text, off, n);
     if (rc != SMARTGPU_OK) return rc;
     if (!count || (cap && !positions)) { set_error("pfind64: count must not be NULL, positions only with cap = 0"); return SMARTGPU_ERR_ARG; }
+    if (text->planes == 3) return p3_find("pfind64", P, false, false, m, 0, text, off, n, positions, nullptr, cap, count);
     DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     uint32_t X[2 * sg::kPatWords];
@@ -2797,9 +3012,10 @@ int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, cons
                            uint64_t* positions, uint64_t cap, uint64_t* starts)
 {
     if (!P || K < 1 || !starts) { set_error("pfind_batch: P/starts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
-    const int rc = check_psearch_args(P[0], m, text, off, n);
+    int rc = check_psearch_args(P[0], m, text, off, n);
     if (rc != SMARTGPU_OK) return rc;
     if (cap && !positions) { set_error("pfind_batch: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
+    if ((rc = check_batch3("pfind_batch", text, K)) != SMARTGPU_OK) return rc;
     // pass 1: the K counts (the planes are read twice: a one-pass ordered batch is not built)
     std::vector<uint64_t> counts(K);
     const int r1 = psearch_impl(P, m, K, text, off, n, counts.data(), nullptr, nullptr);
@@ -2820,6 +3036,11 @@ int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, cons
     bool ok = hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream) == hipSuccess;
     for (uint32_t k = 0; k < K && ok; ++k) {
         if (counts[k] == 0) continue;
+        if (text->planes == 3) {  // (linked: psearch3_impl has counted)
+            const sg::Plane3Args a = plane3_args(d, text, host_pat, k, m, off, n);
+            ok = sg::g_planes3_find(a, out + starts[k], counts[k], text->planes, d->num_cus, d->stream) == hipSuccess;
+            continue;
+        }
         const sg::PlaneArgs a = plane_args(d, text, host_pat, k, m, off, n);
         ok = sg::launch_planes_find(a, out + starts[k], counts[k], text->planes, d->num_cus, d->stream) == hipSuccess;
     }
@@ -2849,6 +3070,7 @@ int smartgpu_psearch_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptex
 {
     int rc = check_pext_args("psearch_sets64", "sets", sets, m, 0, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
+    if (text->planes == 3) return p3_count("psearch_sets64", sets, true, false, m, 0, text, off, n, count, pre_ms, run_ms);
     uint32_t Y[sg::kSetWords], empty = 0;
     bool full = false;
     if ((rc = sets_planes(text, sets, m, false, Y, &empty, &full)) != SMARTGPU_OK) return rc;
@@ -2865,6 +3087,7 @@ int smartgpu_pfind_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext*
     if (cap && !positions) { set_error("pfind_sets64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
     int rc = check_pext_args("pfind_sets64", "sets", sets, m, 0, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
+    if (text->planes == 3) return p3_find("pfind_sets64", sets, true, false, m, 0, text, off, n, positions, nullptr, cap, count);
     uint32_t Y[sg::kSetWords], empty = 0;
     bool full = false;
     if ((rc = sets_planes(text, sets, m, false, Y, &empty, &full)) != SMARTGPU_OK) return rc;
@@ -2893,6 +3116,7 @@ int smartgpu_psearch_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smart
 {
     const int rc = check_pext_args("psearch_mis64", "P", P, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
+    if (text->planes == 3) return p3_count("psearch_mis64", P, false, true, m, k, text, off, n, count, pre_ms, run_ms);
     uint32_t X[kMisWords];
     sg::PlaneMisArgs a;
     a.foreign = mis_planes(text, P, m, X, &a);
@@ -2908,6 +3132,7 @@ int smartgpu_pfind_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgp
     if (cap && !positions) { set_error("pfind_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
     const int rc = check_pext_args("pfind_mis64", "P", P, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
+    if (text->planes == 3) return p3_find("pfind_mis64", P, false, true, m, k, text, off, n, positions, mismatches, cap, count);
     uint32_t X[kMisWords];
     sg::PlaneMisArgs a;
     a.foreign = mis_planes(text, P, m, X, &a);
@@ -2931,6 +3156,7 @@ int smartgpu_psearch_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, con
 {
     int rc = check_pext_args("psearch_sets_mis64", "sets", sets, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
+    if (text->planes == 3) return p3_count("psearch_sets_mis64", sets, true, true, m, k, text, off, n, count, pre_ms, run_ms);
     uint32_t Y[sg::kSetWords];
     bool full = false;
     sg::PlaneSetMisArgs a;
@@ -2948,6 +3174,7 @@ int smartgpu_pfind_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const
     if (cap && !positions) { set_error("pfind_sets_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
     int rc = check_pext_args("pfind_sets_mis64", "sets", sets, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
+    if (text->planes == 3) return p3_find("pfind_sets_mis64", sets, true, true, m, k, text, off, n, positions, mismatches, cap, count);
     uint32_t Y[sg::kSetWords];
     bool full = false;
     sg::PlaneSetMisArgs a;
@@ -3030,10 +3257,11 @@ int smartgpu_palign_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, con
     return palign_run("palign_sets_edit64", sets, true, m, k, text, off, n, ends, count, starts, distances, ops);
 }
 
-int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)
+// smartgpu_iupac_sets (most = 4) and smartgpu_iupac_sets8 (most = 8): one set of rules
+static int iupac_sets_impl(const char* call, int most, const uint8_t* values, int nvalues, const char* P, uint32_t m, uint8_t* sets)
 {
-    if (!values || (m && (!P || !sets))) { set_error("iupac_sets: NULL argument"); return SMARTGPU_ERR_ARG; }
-    if (nvalues < 1 || nvalues > 4) { set_error("iupac_sets: a packed text holds 1 to 4 distinct byte values, not %d", nvalues); return SMARTGPU_ERR_ARG; }
+    if (!values || (m && (!P || !sets))) { set_error("%s: NULL argument", call); return SMARTGPU_ERR_ARG; }
+    if (nvalues < 1 || nvalues > most) { set_error("%s: a packed text holds 1 to %d distinct byte values, not %d", call, most, nvalues); return SMARTGPU_ERR_ARG; }
     // the bases a letter accepts, bit 0..3 = A C G T
     static const struct { char letter; uint8_t bases; } kIupac[] = {
         {'A', 1}, {'C', 2}, {'G', 4}, {'T', 8}, {'U', 8}, {'R', 1 | 4}, {'Y', 2 | 8}, {'S', 2 | 4}, {'W', 1 | 8}, {'K', 4 | 8}, {'M', 1 | 2},
@@ -3041,14 +3269,14 @@ int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uin
     int bases_of[256];
     for (int c = 0; c < 256; ++c) bases_of[c] = -1;
     for (const auto& e : kIupac) bases_of[(uint8_t)e.letter] = bases_of[(uint8_t)(e.letter | 0x20)] = e.bases;
-    uint8_t base_of_code[4] = {0, 0, 0, 0};  // the base (one bit) value v stands for; 0: none
+    uint8_t base_of_code[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the base (one bit) value v stands for; 0: none (N, a separator)
     for (int v = 0; v < nvalues; ++v) {
         const int b = bases_of[values[v]];
         if (b == 1 || b == 2 || b == 4 || b == 8) base_of_code[v] = static_cast<uint8_t>(b);
     }
     for (uint32_t j = 0; j < m; ++j)
         if (bases_of[(uint8_t)P[j]] < 0) {
-            set_error("iupac_sets: position %u: byte 0x%02x is no IUPAC nucleotide letter", j, (unsigned)(uint8_t)P[j]);
+            set_error("%s: position %u: byte 0x%02x is no IUPAC nucleotide letter", call, j, (unsigned)(uint8_t)P[j]);
             return SMARTGPU_ERR_ARG;
         }
     for (uint32_t j = 0; j < m; ++j) {
@@ -3058,6 +3286,16 @@ int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uin
         sets[j] = s;
     }
     return SMARTGPU_OK;
+}
+
+int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)
+{
+    return iupac_sets_impl("iupac_sets", 4, values, nvalues, P, m, sets);
+}
+
+int smartgpu_iupac_sets8(const uint8_t values[8], int nvalues, const char* P, uint32_t m, uint8_t* sets)
+{
+    return iupac_sets_impl("iupac_sets8", SMARTGPU_PTEXT_MAXVALUES, values, nvalues, P, m, sets);
 }
 
 int smartgpu_iupac_revcomp(const char* P, uint32_t m, char* out)

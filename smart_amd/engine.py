@@ -145,6 +145,12 @@ def _load(path):
         "smartgpu_palign_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_palign_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
+        # packed texts of five to eight values (three bit planes)
+        "smartgpu_ptext_layout8": (i32, [u64, i32, C.POINTER(i32), C.POINTER(u64)]),
+        "smartgpu_ptext_pack8": (vp, [vp]),
+        "smartgpu_ptext_upload8": (vp, [vp, u64, i32]),
+        "smartgpu_ptext_symbols8": (i32, [vp, vp]),
+        "smartgpu_iupac_sets8": (i32, [vp, i32, vp, u32, vp]),
     }
     for a in ALGOS:
         sig["smartgpu_%s_search" % a] = (i32, [vp, i32, vp, i32])
@@ -262,8 +268,17 @@ def ptext_layout(n, nvalues):
     return int(planes.value), int(nbytes.value)
 
 
+def ptext_layout8(n, nvalues):
+    """ptext_layout for 1 to 8 values — smartgpu_ptext_layout8: 1 / 2 / 3 planes for at most 2 / 4 / 8 values."""
+    planes, nbytes = C.c_int(0), C.c_uint64(0)
+    if lib().smartgpu_ptext_layout8(n, nvalues, C.byref(planes), C.byref(nbytes)) != 0:
+        raise _err("ptext_layout8")
+    return int(planes.value), int(nbytes.value)
+
+
 class PackedText:
-    """A text of at most four distinct byte values resident in one GPU's HBM as bit planes (smartgpu_ptext_*)."""
+    """A text of at most four distinct byte values resident in one GPU's HBM as bit planes (smartgpu_ptext_*); with
+    wide=True at most eight, five to eight of them on three planes (smartgpu_ptext_pack8 / smartgpu_ptext_upload8)."""
 
     def __init__(self, handle):
         if not handle:
@@ -272,14 +287,14 @@ class PackedText:
         self._L = lib()  # the library that made the handle frees it
 
     @classmethod
-    def pack(cls, text):
+    def pack(cls, text, wide=False):
         """Packs a resident Text on the device; the Text stays valid and independent."""
-        return cls(lib().smartgpu_ptext_pack(text._h))
+        return cls((lib().smartgpu_ptext_pack8 if wide else lib().smartgpu_ptext_pack)(text._h))
 
     @classmethod
-    def upload(cls, data, device=0):
+    def upload(cls, data, device=0, wide=False):
         data = _u8(data)
-        return cls(lib().smartgpu_ptext_upload(data.ctypes.data, len(data), device))
+        return cls((lib().smartgpu_ptext_upload8 if wide else lib().smartgpu_ptext_upload)(data.ctypes.data, len(data), device))
 
     def __len__(self):
         return int(lib().smartgpu_ptext_length(self._h))
@@ -299,8 +314,8 @@ class PackedText:
 
     def symbols(self):
         """The byte values the text holds, ascending: symbols()[code] is the value of a code."""
-        vals = np.zeros(4, dtype=np.uint8)
-        k = lib().smartgpu_ptext_symbols(self._h, vals.ctypes.data)
+        vals = np.zeros(8, dtype=np.uint8)
+        k = lib().smartgpu_ptext_symbols8(self._h, vals.ctypes.data)
         if k < 0:
             raise _err("ptext_symbols")
         return [int(v) for v in vals[:k]]
@@ -313,7 +328,7 @@ class PackedText:
 
     def iupac(self, pattern):
         """The sets of an IUPAC nucleotide pattern over this text's values: iupac_sets(pattern, self.symbols())."""
-        return iupac_sets(pattern, self.symbols())
+        return iupac_sets(pattern, self.symbols(), wide=True)
 
     def probe_read_gbs(self, reps=20):
         """Practical streaming-read rate (GB/s) of the device over the planes: the packed layout's roofline."""
@@ -721,17 +736,22 @@ def iupac_revcomp(pattern):
     return out.tobytes().decode() if is_str else out.tobytes()
 
 
-def iupac_sets(pattern, values):
+def iupac_sets(pattern, values, wide=False):
     """The uint8 sets of an IUPAC nucleotide pattern (A C G T U R Y S W K M B D H V N, either case) over a packed text's
-    `values` (PackedText.symbols()): bit c of sets[j] = position j accepts values[c].  No device needed."""
+    `values` (PackedText.symbols()): bit c of sets[j] = position j accepts values[c].  No device needed.
+    At most four values; with wide=True up to eight, the values of a three-plane text (smartgpu_iupac_sets8).  A value that
+    is no base letter — N, a separator — is accepted by no letter, pattern letter N included."""
     if isinstance(pattern, str):
         pattern = pattern.encode()
     P = _u8(pattern)
-    vals = np.zeros(4, dtype=np.uint8)
+    vals = np.zeros(8, dtype=np.uint8)
     k = len(values)
-    vals[:min(k, 4)] = np.asarray(list(values)[:4], dtype=np.uint8)
+    vals[:min(k, 8)] = np.asarray(list(values)[:8], dtype=np.uint8)
     sets = np.zeros(len(P), dtype=np.uint8)
-    if lib().smartgpu_iupac_sets(vals.ctypes.data, k, P.ctypes.data, len(P), sets.ctypes.data) != 0:
+    # more than four values: a three-plane text's (smartgpu_iupac_sets8); with at most four, or without `wide`, the call is
+    # smartgpu_iupac_sets as ever, refusals included
+    call = lib().smartgpu_iupac_sets8 if wide and k > 4 else lib().smartgpu_iupac_sets
+    if call(vals.ctypes.data, k, P.ctypes.data, len(P), sets.ctypes.data) != 0:
         raise _err("iupac_sets")
     return sets
 

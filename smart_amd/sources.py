@@ -21,6 +21,7 @@ UNITS = {
     "k_packed": ("k_packed.hip",),
     "k_util": ("k_util.hip", "text_rate.hpp"),
     "k_planes": ("k_planes.hip", "planes.hpp"),
+    "k_planes3": ("k_planes3.hip", "planes3.hpp", "planes3_host.hpp", "planes.hpp"),
     "k_pedit": ("k_pedit.hip", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_peditl": ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_palign": ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
@@ -33,6 +34,7 @@ KERNEL_UNIT = {
     "planes_sets_scan": "k_planes", "planes_sets_find": "k_planes",
     "planes_mis_scan": "k_planes", "planes_mis_find": "k_planes",
     "planes_sets_mis_scan": "k_planes", "planes_sets_mis_find": "k_planes",
+    "planes3_pack": "k_planes3", "planes3_scan": "k_planes3", "planes3_find": "k_planes3",
     "planes_edit_scan": "k_pedit", "planes_edit_find": "k_pedit",
     "planes_editl_scan": "k_peditl", "planes_editl_find": "k_peditl",
     "planes_edit_align": "k_palign",
