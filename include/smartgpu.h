@@ -306,6 +306,16 @@ int smartgpu_coalesce_wide(int max_group);
  * 63 up to m = 48, 50 up to m = 64, 42 beyond; a wider setting is clipped to that per length, not refused.  The
  * library starts with 96 (profiles/coalesce/RESULTS.md has the measurements). */
 int smartgpu_coalesce_pass(int max_group);
+/* LONG passes.  What the 96 / 84 / 63 / 50 / 42 above bound is the room in the kernel's arguments; a pass that carries
+ * pointers only, and reads the ends of its patterns from their plans, takes 252 up to m = 16, 152 up to m = 32, 108 up
+ * to m = 48, 84 up to m = 64 and 68 beyond.  Under the widest setting (96) a key that reaches the width above is still
+ * sent at once, unless its range holds at least `min_range_bytes` start positions AND the previous pass over the same
+ * text, range and length left because it was full, with nothing since that sent what was pending (a sync, a result, a
+ * mark, a setting): then the launches arrive faster than the GPU reads the text, and the key gathers up to the long
+ * width, or until the next such call, and saves a read of the text.  -1: no long passes; 0: any range.  Returns the
+ * previous value (-1 or more), SMARTGPU_ERR_ARG for a value below -1.  Needs no device; what is pending is sent first.
+ * The library starts with 64 MiB (profiles/coalesce/RESULTS.md has the measurements). */
+long long smartgpu_coalesce_long(long long min_range_bytes);
 /* Of the launches on `device` that could share a pass: how many were seen, and how many kernels were sent for them
  * (equal when nothing was coalesced).  Either pointer may be NULL. */
 int smartgpu_coalesce_stats(int device, uint64_t *launches, uint64_t *passes);

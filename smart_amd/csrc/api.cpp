@@ -709,25 +709,68 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // and nearly all of them at m = 8 and 16 (profiles/coalesce/RESULTS.md).
 // The queue holds device pointers of plans and texts: smartgpu_plan_free, _plan_set_result_buffer and _text_free flush.
 // The plan's tail row is copied, not pointed to.
+// LONG passes.  pass_width(m) is what the kernel's arguments hold BY VALUE, not what the kernel can walk: its LDS has
+// room for sg::long_width(m) patterns (152 at m = 32 against 84) when a pass carries pointers only and reads its rows
+// from the plans' blobs (multi.hpp).  When launches keep arriving, the read of the text a wider pass saves is worth far
+// more than the dependent read its prologue adds; what a wider pass costs is the WAIT until it is full, and that wait
+// is free only while the GPU has something to do.  The queue cannot ask the GPU (a HIP call in a launch that is only
+// queued was measured and left out, above), so the rule is one it can decide alone: a key that reaches pass_width(m)
+// is sent at once, as ever, UNLESS (a) its range is at least g_coalesce_long bytes and (b) the previous pass of the same
+// (text, range, m, halo) was sent because it was full — not by a flush — and no flush has happened since.  Then a
+// pass of that key is on the stream or was a moment ago, the launches come faster than the GPU reads, and the key goes on
+// gathering to long_width(m); it is sent there, or by the next flush, in the long layout if it holds more than
+// pass_width(m) entries.  After any flush the GPU is presumably idle, and the first pass of a key leaves at
+// pass_width(m) again: waiting longer would only lengthen the lead-in.  (a): below 64 MiB a read of the range takes
+// some 10 us, the host's 1.3 us per launch bounds the run and not the GPU, and a second read costs nothing that a longer
+// wait would win back.  Long passes exist under the widest setting (kPassMax) only: a narrower one asks for exactly
+// that many launches per pass.
 struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; uint8_t tail[sg::kTailRow]; };
+bool same_key(const sg::ScanArgs& x, const sg::ScanArgs& a) { return x.text == a.text && x.s_begin == a.s_begin && x.s_end == a.s_end && x.m == a.m && x.halo == a.halo; }
 struct QueuedKey {
     sg::ScanArgs key;  // text, s_begin, s_end, m, halo
     uint32_t n = 0;          // entries: streaming launches and riders
     uint32_t streaming = 0;  // the streaming launches among them: what the coalesce setting counts
-    QueuedScan scans[sg::kPassMax];
-    bool holds(const sg::ScanArgs& a) const { return key.text == a.text && key.s_begin == a.s_begin && key.s_end == a.s_end && key.m == a.m && key.halo == a.halo; }
+    QueuedScan scans[sg::kLongMax];
+    bool holds(const sg::ScanArgs& a) const { return same_key(key, a); }
+    void take(const QueuedKey& o)  // (the entries it holds, not all kLongMax)
+    {
+        key = o.key;
+        n = o.n;
+        streaming = o.streaming;
+        std::memcpy(static_cast<void*>(scans), static_cast<const void*>(o.scans), o.n * sizeof(QueuedScan));
+    }
 };
+static_assert(std::is_trivially_copyable<QueuedScan>::value, "QueuedKey::take copies entries as bytes");
+static_assert(SMARTGPU_XSIZE - 1 - sg::kGramCap + sg::kTailRow <= sg::kPatternBytes, "a long pass reads whole rows from a blob's pattern slot");
 struct LaunchQueue {
     std::mutex mu;
     static constexpr uint32_t kKeys = 8;  // a ninth key sends the oldest
     uint32_t nkeys = 0;
     QueuedKey keys[kKeys];  // in arrival order
-    void drop(uint32_t at) { for (--nkeys; at < nkeys; ++at) keys[at] = keys[at + 1]; }
+    void drop(uint32_t at) { for (--nkeys; at < nkeys; ++at) keys[at].take(keys[at + 1]); }
+    // the keys whose last pass was sent because it was full, since the last flush (a ninth replaces the oldest)
+    uint32_t nfull = 0, full_next = 0;
+    sg::ScanArgs full[kKeys];
+    bool was_full(const sg::ScanArgs& a) const
+    {
+        for (uint32_t i = 0; i < nfull; ++i)
+            if (same_key(full[i], a)) return true;
+        return false;
+    }
+    void note_full(const sg::ScanArgs& a)
+    {
+        if (was_full(a)) return;
+        if (nfull < kKeys) { full[nfull++] = a; return; }
+        full[full_next] = a;
+        full_next = (full_next + 1) % kKeys;
+    }
     bool off = false;             // smartgpu_stream_handle gave the stream out: its holder orders their own work on it
     uint64_t launches = 0, passes = 0;  // eligible launches seen / kernels sent for them
     uint64_t riders = 0;                // launches that rode in a key's pass (not among `launches`)
 };
 LaunchQueue g_queue[kMaxDevices];
+// the least range, in bytes of start positions, whose keys gather long passes; -1: none do (smartgpu_coalesce_long)
+std::atomic<long long> g_coalesce_long{64ll << 20};
 // launches per pass: 0 = off, 2..kPassMax.  ONE number with three calls: smartgpu_coalesce, the first, sets 0 or
 // 2..kCoalesceNarrow and reports a wider value as kCoalesceNarrow; smartgpu_coalesce_wide sets 0 or 2..kMultiMax and
 // reports a wider value as kMultiMax; smartgpu_coalesce_pass sets and reports all of it.
@@ -756,10 +799,16 @@ hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
         ma.m = k.key.m;
         ma.halo = k.key.halo & 0xFFu;  // as prepare_scan_args: H without the plan's marks
         ma.np = k.n;
-        ma.width = sg::pass_width(k.key.m);
         ma.stride = sg::tail_stride(k.key.m);
-        ma.reserved = 0;
-        for (uint32_t j = 0; j < k.n; ++j) sg::multi_set(ma, j, k.scans[j].a.blob, k.scans[j].a.count, k.scans[j].tail);
+        if (k.n <= sg::pass_width(k.key.m)) {
+            ma.width = sg::pass_width(k.key.m);
+            ma.reserved = sg::kMultiByValue;
+            for (uint32_t j = 0; j < k.n; ++j) sg::multi_set(ma, j, k.scans[j].a.blob, k.scans[j].a.count, k.scans[j].tail);
+        } else {  // a long pass: the pointers alone, the rows are read from the blobs
+            ma.width = sg::long_width(k.key.m);
+            ma.reserved = sg::kMultiLong;
+            for (uint32_t j = 0; j < k.n; ++j) sg::multi_set_long(ma, j, k.scans[j].a.blob, k.scans[j].a.count);
+        }
         e = sg::g_hor_multi(ma, d->num_cus, d->stream);
     }
     if (k.n && e == hipSuccess) ++q.passes;
@@ -779,6 +828,7 @@ hipError_t flush_queue(const DeviceCtx* d)
         if (e != hipSuccess && err == hipSuccess) err = e;
     }
     q.nkeys = 0;
+    q.nfull = q.full_next = 0;  // whatever comes next finds, presumably, an idle GPU: its first pass leaves at pass_width(m)
     return err;
 }
 
@@ -855,7 +905,11 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
     if (rider) ++q.riders; else ++k.streaming;
     const uint32_t room = sg::pass_width(a.m);  // (at most kPassMax, the room a key has)
     const uint32_t width = static_cast<uint32_t>(G) < room ? static_cast<uint32_t>(G) : room;
-    if (k.streaming >= width || k.n >= room) {
+    // a long pass (the rule stands above the queue): launches and riders together, up to long_width(m)
+    const long long least = g_coalesce_long.load(std::memory_order_relaxed);
+    const bool gather_on = G == sg::kPassMax && least >= 0 && a.s_end - a.s_begin >= static_cast<uint64_t>(least) && q.was_full(a);
+    if (gather_on ? k.n >= sg::long_width(a.m) : (k.streaming >= width || k.n >= room)) {
+        q.note_full(k.key);
         const hipError_t e = send_key(d, q, k);
         if (e != hipSuccess && err == hipSuccess) err = e;
         q.drop(at);
@@ -1244,6 +1298,13 @@ int smartgpu_coalesce_wide(int max_group)
 int smartgpu_coalesce_pass(int max_group)
 {
     return set_coalesce(max_group, sg::kPassMax);
+}
+
+long long smartgpu_coalesce_long(long long min_range_bytes)
+{
+    if (min_range_bytes < -1) { set_error("coalesce_long: the least range of a long pass is 0 or more bytes (-1: no long passes), not %lld", min_range_bytes); return SMARTGPU_ERR_ARG; }
+    flush_all_queues();
+    return g_coalesce_long.exchange(min_range_bytes);
 }
 
 int smartgpu_coalesce_stats(int device, uint64_t* launches, uint64_t* passes)

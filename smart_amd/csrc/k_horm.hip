@@ -29,6 +29,12 @@ namespace sg {
 // the stride of their own length; thread x copies 16 bytes of them to LDS with ONE read, sent before the first tile is
 // asked for, and the table is built from LDS while the tile is on the way.  A row in LDS is also what a lane compares a
 // window with (its last H + 1 stored bytes).  A narrow pass sends few reads: np x stride / 16.
+// A LONG pass (multi.hpp: MultiArgs::reserved == kMultiLong) holds more patterns than the arguments have room for by
+// value — up to long_width(m): 252 up to m = 16, 152 up to m = 32, 108, 84, 68 beyond — and carries pointers only:
+// its prologue reads each row from the front of the pattern's blob, one dependent read (the pointer from the
+// arguments, then 16 bytes of the pattern), still sent before the first tile is asked for.  Its links and sums take np
+// entries each, behind the rows: u8 gram | u32 heads | np rows | u32 next[np] | u32 sums[np] | text.  From the first
+// barrier on the two kinds of pass run the same code over pointers that differ.
 // The arguments are 4080 bytes, with tile_first and ntiles 4092 of the 4096 a kernel may take (multi.hpp asserts it).
 // The pointers in the area are read as numbers and cast to GLOBAL memory: thread g < np keeps count[g] in registers
 // from the prologue to the end; blob[g] is read by the rare lane that completes a window in memory.
@@ -54,6 +60,9 @@ static_assert(kHormHead % 64 == 0, "the rows stay 16-byte aligned and the tile 6
 // four workgroups per CU: 160 KB of LDS, allocated in blocks of at most 2 KB
 static_assert(kHormHead + ((kPassMax * 16u + 63u) & ~63u) + 16448u <= 40960u && kHormHead + ((50u * 64u + 63u) & ~63u) + 16448u <= 40960u &&
               kHormHead + ((42u * kTailRow + 63u) & ~63u) + 16448u <= 40960u, "the widest pass of every row stride leaves four workgroups per CU resident");
+
+// (a long pass: multi.hpp asserts the same of long_head at every long_width, with this tile)
+static_assert(kHaloMax == 16 && kMultiTileLds == ((16u + (uint32_t)kHorT * kHorL + 16u + 63u) & ~63u) && kMultiLdsBudget == 40960u, "the tile that multi.hpp's LDS budget counts");
 
 // a pointer into global memory from the number an LDS slot holds (per lane: lanes may ask for different patterns)
 __device__ __forceinline__ const uint8_t* horm_global(unsigned long long v)
@@ -116,29 +125,60 @@ __device__ __forceinline__ unsigned long long horm_area64(const MultiArgs& a, ui
     return *reinterpret_cast<const unsigned long long*>(a.area + at);
 }
 
+// 16 bytes of a pattern in global memory, at any alignment, in one read
+__device__ __forceinline__ uint4 horm_row16(const uint8_t* p)
+{
+    uint4 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
 template <int THREADS, int L>
 __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t tile_first, uint32_t ntiles)
 {
     constexpr int TB = THREADS * L;
     static_assert(kPassMax <= THREADS && THREADS % (int)kGramCap == 0, "a thread per pattern; the grams of THREADS / kGramCap patterns in a round");
+    static_assert(THREADS == (int)kMultiThreads && kLongMax <= (uint32_t)THREADS && kMultiLdsBudget - kMultiTileLds - kGramSlots - 4u * kGramBuckets <= 2u * THREADS * 16u,
+                  "a long pass: a thread per pattern, and the rows that the LDS has room for in two pieces per thread");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t m = a.m, H = a.halo, H16 = round16(H), np = a.np, W = a.width, stride = a.stride;
     const bool in_memory = m - 1 > H;  // windows are completed in HBM
+    const bool by_value = a.reserved == kMultiByValue;  // the area's layout (multi.hpp): rows in the arguments, or a long pass
     const uint32_t rlast = m - 1 - gram_first(m);  // P[m-1-k] is byte rlast - k of a row
+    const uint32_t row_bytes = np * stride;        // a multiple of 16
+    const uint32_t nlink = by_value ? (uint32_t)kPassMax : np;  // links and sums: kHormHead's by value, np each in a long pass
     uint8_t* gram = smem;
     uint32_t* heads = reinterpret_cast<uint32_t*>(smem + kGramSlots);
-    uint32_t* next = heads + kGramBuckets;
-    uint32_t* sums = next + kPassMax;
-    uint8_t* rows = smem + kHormHead;
-    const uint32_t row_bytes = np * stride;              // a multiple of 16
-    uint8_t* txt = rows + ((row_bytes + 63u) & ~63u);  // txt[H16 + x] == T[tile0 + x]
+    uint8_t* rows = by_value ? smem + kHormHead : smem + kGramSlots + 4 * kGramBuckets;
+    uint32_t* next = by_value ? heads + kGramBuckets : reinterpret_cast<uint32_t*>(rows + row_bytes);
+    uint32_t* sums = next + nlink;
+    uint8_t* txt = by_value ? rows + ((row_bytes + 63u) & ~63u) : smem + long_head(np, stride);  // txt[H16 + x] == T[tile0 + x]
 
     // What this thread takes of the arguments' area (multi.hpp), read before anything else: 16 bytes of the rows, and
     // (thread g < np) the result slot of pattern g as a number.  Loads come back in the order they were sent, so these
     // go out in front of the tile's and the table is built while the tile is on the way.
+    // A long pass has no rows in its area: the thread reads blob[g] there and its 16 bytes from the pattern at the front
+    // of that blob, blob[g] + gram_first(m) + offset — at no alignment from m = 66 on — and, where np rows are more
+    // than THREADS pieces, a second piece THREADS further on.  A row's last piece reaches up to 15 bytes behind the
+    // pattern's end: still inside the blob's pattern slot (api.cpp asserts it), and no byte behind tail_stored(m) is
+    // ever looked at (the grams end at m - 1, a compare starts there and goes left).
     const bool row_mine = threadIdx.x * 16u < row_bytes;
-    uint4 row16 = {};
-    if (row_mine) row16 = *reinterpret_cast<const uint4*>(a.area + multi_rows_at(W) + threadIdx.x * 16u);
+    bool row_mine2 = false;
+    uint4 row16 = {}, row16b = {};
+    if (by_value) {
+        if (row_mine) row16 = *reinterpret_cast<const uint4*>(a.area + multi_rows_at(W) + threadIdx.x * 16u);
+    } else {
+        const uint32_t pieces = stride / 16u, second = threadIdx.x + THREADS;
+        row_mine2 = second * 16u < row_bytes;
+        if (row_mine) {
+            const uint32_t g = threadIdx.x / pieces;
+            row16 = horm_row16(horm_global(horm_area64(a, multi_blob_at(g))) + gram_first(m) + (threadIdx.x - g * pieces) * 16u);
+        }
+        if (row_mine2) {
+            const uint32_t g = second / pieces;
+            row16b = horm_row16(horm_global(horm_area64(a, multi_blob_at(g))) + gram_first(m) + (second - g * pieces) * 16u);
+        }
+    }
     unsigned long long head_count = 0;
     if (threadIdx.x < np) head_count = horm_area64(a, multi_count_at(W, threadIdx.x));
 
@@ -165,8 +205,9 @@ __global__ __launch_bounds__(THREADS) void hor_multi_scan(MultiArgs a, uint64_t 
         const uint4 dflt16 = {dflt, dflt, dflt, dflt};
         for (uint32_t j = threadIdx.x * 16u; j < kGramSlots; j += THREADS * 16u) *reinterpret_cast<uint4*>(gram + j) = dflt16;
         for (uint32_t j = threadIdx.x; j < kGramBuckets; j += THREADS) heads[j] = 0;
-        if (threadIdx.x < (uint32_t)kPassMax) sums[threadIdx.x] = 0;
+        if (threadIdx.x < nlink) sums[threadIdx.x] = 0;
         if (row_mine) *reinterpret_cast<uint4*>(rows + threadIdx.x * 16u) = row16;
+        if (row_mine2) *reinterpret_cast<uint4*>(rows + (threadIdx.x + THREADS) * 16u) = row16b;
     }
     __syncthreads();
     {
@@ -273,11 +314,14 @@ static int horm_wgs(uint32_t m)
 hipError_t launch_hor_multi(const MultiArgs& a, int num_cus, hipStream_t stream)
 {
     if (a.m < 3 || a.halo < 1 || a.halo > kHaloMax || a.halo > a.m - 1) return hipErrorInvalidValue;  // (a gram and the byte before a lane's first window end exist)
-    if (a.width != pass_width(a.m) || a.stride != tail_stride(a.m) || a.np < 1 || a.np > a.width) return hipErrorInvalidValue;
+    if (a.reserved != kMultiByValue && a.reserved != kMultiLong) return hipErrorInvalidValue;
+    const bool by_value = a.reserved == kMultiByValue;
+    if (a.width != (by_value ? pass_width(a.m) : long_width(a.m)) || a.stride != tail_stride(a.m) || a.np < 1 || a.np > a.width) return hipErrorInvalidValue;
     const uint32_t m = a.m, H = a.halo;
+    const size_t head = by_value ? kHormHead + (((size_t)a.np * a.stride + 63) & ~(size_t)63) : long_head(a.np, a.stride);
     const TileRange tr = tiles_for(a.s_begin + m - 1, a.s_end + m - 1, (uint64_t)kHorT * kHorL);
     if (tr.count == 0) return hipSuccess;
-    const size_t lds = kHormHead + (((size_t)a.np * a.stride + 63) & ~(size_t)63) + ((r16(H) + (size_t)kHorT * kHorL + 16 + 63) & ~(size_t)63);  // whole 64-byte blocks: tile_at() permutes inside them
+    const size_t lds = head + ((r16(H) + (size_t)kHorT * kHorL + 16 + 63) & ~(size_t)63);  // whole 64-byte blocks: tile_at() permutes inside them
     const int wgs_per_cu = g_tune[4] ? g_tune[4] : horm_wgs(m);  // smartgpu_tune(4, .) applies
     uint32_t grid = (uint32_t)num_cus * (uint32_t)wgs_per_cu;
     if (grid > tr.count) grid = tr.count;

@@ -30,9 +30,9 @@ struct alignas(16) MultiArgs {
     uint32_t m;                 // pattern length
     uint32_t halo;              // back halo H = min(m-1, kHaloMax)
     uint32_t np;                // patterns in this pass, 1 <= np <= width
-    uint32_t width;             // pass_width(m)
+    uint32_t width;             // pass_width(m); long_width(m) in a long pass (below)
     uint32_t stride;            // tail_stride(m)
-    uint32_t reserved;          // (the area starts at a multiple of 16: a thread copies 16 bytes of rows at a time)
+    uint32_t reserved;          // the area's layout: kMultiByValue or kMultiLong (the area starts at a multiple of 16: a thread copies 16 bytes of rows at a time)
     uint8_t area[kMultiArea];
 };
 // the kernel takes MultiArgs and two more arguments, a u64 and a u32, by value: HIP passes at most 4096 bytes
@@ -125,6 +125,53 @@ inline void multi_set(MultiArgs& a, uint32_t g, const uint8_t* blob, unsigned lo
     __builtin_memcpy(a.area + multi_blob_at(g), &blob, 8);
     __builtin_memcpy(a.area + multi_count_at(a.width, g), &count, 8);
     __builtin_memcpy(a.area + multi_rows_at(a.width) + g * a.stride, row, a.stride);
+}
+
+// A LONG pass: more patterns than the arguments have room for by value.  The two pointers of a pattern are 16 bytes, so
+// the area alone holds 252 pairs; the bytes of a row already lie in memory, at the front of every plan's blob
+// ([pattern, kPatternBytes][tables]): a long pass carries u64 blob[LW] | u64 count[LW], LW = long_width(m), and NO rows,
+// and the kernel's prologue reads each row from blob[g] + gram_first(m) — one dependent read per workgroup, before the
+// first tile is asked for.  MultiArgs::reserved says which layout the area has; width is LW, so multi_blob_at and
+// multi_count_at hold for both.  What bounds LW: the area, a thread per pattern, and the LDS of a workgroup when four
+// are resident on a CU (40960 bytes each): the table, the heads, a link and a sum per pattern, the rows, the tile.
+constexpr uint32_t kMultiByValue = 0, kMultiLong = 1;  // MultiArgs::reserved
+constexpr uint32_t kMultiThreads = 256;                // hor_multi_scan's workgroup (k_horm.hip asserts it)
+constexpr uint32_t kMultiTileLds = 16448;              // a tile with its halo: round64(48 + 16384 + 16)
+constexpr uint32_t kMultiLdsBudget = 40960;
+__host__ __device__ constexpr uint32_t round64(uint32_t x) { return (x + 63u) & ~63u; }
+__host__ __device__ constexpr bool long_fits(uint32_t m, uint32_t np)
+{
+    return np * 16u <= kMultiArea && np + 4u <= kMultiThreads &&
+           kGramSlots + 4u * kGramBuckets + 8u * np + round64(np * tail_stride(m)) + kMultiTileLds <= kMultiLdsBudget;
+}
+__host__ __device__ constexpr uint32_t long_search(uint32_t m)
+{
+    uint32_t np = 0;
+    while (long_fits(m, np + 1u)) ++np;  // (what fits is monotone in np)
+    return np;
+}
+// (the search runs when this is compiled, once per row stride: the queue asks for the width at every launch)
+constexpr uint32_t kLongWidth[5] = {long_search(16), long_search(32), long_search(48), long_search(64), long_search(65)};
+constexpr uint32_t long_width(uint32_t m) { return kLongWidth[tail_stride(m) / 16u - 1u]; }
+static_assert(tail_stride(16) == 16 && tail_stride(32) == 32 && tail_stride(48) == 48 && tail_stride(64) == 64 && tail_stride(65) == 80, "one width per stride");
+static_assert(long_width(3) == 252 && long_width(16) == 252 && long_width(17) == 152 && long_width(32) == 152 && long_width(33) == 108 &&
+              long_width(48) == 108 && long_width(49) == 84 && long_width(64) == 84 && long_width(65) == 68 && long_width(4096) == 68,
+              "the long width of every row stride");
+static_assert(long_width(16) > pass_width(16) && long_width(32) > pass_width(32) && long_width(48) > pass_width(48) &&
+              long_width(64) > pass_width(64) && long_width(65) > pass_width(65), "a long pass is wider than a by-value pass at every length");
+constexpr uint32_t kLongMax = long_width(3);  // the most entries a key gathers
+// The LDS of a long pass: u8 gram[kGramSlots] | u32 heads[kGramBuckets] | np rows | u32 next[np] | u32 sums[np] | pad to
+// 64 | tile.  The rows come first so that they stay 16-byte aligned for any np; rounding the sum of rows, links and
+// sums takes no more than long_fits allows (both are multiples of 64, and this one rounds once).
+__host__ __device__ constexpr uint32_t long_head(uint32_t np, uint32_t stride) { return kGramSlots + 4u * kGramBuckets + round64(np * (stride + 8u)); }
+static_assert(long_head(252, 16) + kMultiTileLds <= kMultiLdsBudget && long_head(152, 32) + kMultiTileLds <= kMultiLdsBudget &&
+              long_head(108, 48) + kMultiTileLds <= kMultiLdsBudget && long_head(84, 64) + kMultiTileLds <= kMultiLdsBudget &&
+              long_head(68, 80) + kMultiTileLds <= kMultiLdsBudget, "the widest long pass of every row stride leaves four workgroups per CU resident");
+// put pattern g's pointers into a long pass's arguments (a.width == long_width(a.m))
+inline void multi_set_long(MultiArgs& a, uint32_t g, const uint8_t* blob, unsigned long long* count)
+{
+    __builtin_memcpy(a.area + multi_blob_at(g), &blob, 8);
+    __builtin_memcpy(a.area + multi_count_at(a.width, g), &count, 8);
 }
 
 // The launcher of k_horm.hip, reached through a pointer that the unit's own static initialiser sets: api.cpp holds

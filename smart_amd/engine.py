@@ -100,6 +100,7 @@ def _load(path):
         "smartgpu_coalesce": (i32, [i32]),
         "smartgpu_coalesce_wide": (i32, [i32]),
         "smartgpu_coalesce_pass": (i32, [i32]),
+        "smartgpu_coalesce_long": (C.c_longlong, [C.c_longlong]),
         "smartgpu_coalesce_stats": (i32, [i32, C.POINTER(u64), C.POINTER(u64)]),
         "smartgpu_coalesce_riders": (i32, [i32, C.POINTER(u64)]),
         "smartgpu_mtext_upload": (vp, [vp, u64, i32, vp]),
@@ -872,6 +873,30 @@ def coalesce_pass(max_group):
     prev = lib().smartgpu_coalesce_pass(max_group)
     if prev < 0:
         raise _err("coalesce")
+    return prev
+
+
+LONG_DEFAULT = 64 << 20
+
+
+def long_width(m):
+    """The most patterns of length m a LONG pass takes (smart_amd/csrc/multi.hpp: long_width): such a pass carries two
+    pointers per pattern in the 4032 bytes and reads the rows from the plans, so what bounds it is a thread per pattern
+    (252) and the LDS of a workgroup at four per CU: 40960 bytes for the table (16384), the heads (2048), a link and a
+    sum per pattern, the rows rounded to 64, and the tile (16448)."""
+    stride = (min(m, 65) + 15) // 16 * 16
+    np = 0
+    while 16 * (np + 1) <= 4032 and np + 1 <= 256 - 4 and 16384 + 2048 + 8 * (np + 1) + (((np + 1) * stride + 63) & ~63) + 16448 <= 40960:
+        np += 1
+    return np
+
+
+def coalesce_long(min_range_bytes):
+    """The least range, in bytes, over which a key whose previous pass left full goes on gathering beyond pass_width(m),
+    up to long_width(m) (-1: never, 0: any range; the library starts with LONG_DEFAULT); returns the previous value."""
+    prev = lib().smartgpu_coalesce_long(min_range_bytes)
+    if prev < -1:
+        raise _err("coalesce_long")
     return prev
 
 

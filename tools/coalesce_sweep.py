@@ -31,6 +31,67 @@ def splitmix64(x):
     return x ^ (x >> 31)
 
 
+def long_sweep(args):
+    """--long: per length, W + 2 LW plans a round (W = engine.pass_width(m), LW = engine.long_width(m)) under the widest
+    setting, once with smartgpu_coalesce_long(-1) — ceil((W + 2 LW) / W) by-value passes — and once with
+    smartgpu_coalesce_long(0): the pass of W that leaves after the mark's flush, then two long passes of LW.  The same
+    plans and the same events in both cells: ms per pattern, the kernels of a round, every count against the first cell's."""
+    import smart_amd
+    from smart_amd import Plan, Text, engine
+    if smart_amd.device_count() < 1:
+        raise SystemExit("no GPU: " + engine.lib().smartgpu_last_error().decode())
+    n = int(args.gib * (1 << 30))
+    text = Text.generate(SEED, args.sigma, n)
+    engine.probe_read_gbs(text, reps=64)  # clocks
+    default_group, default_long = engine.coalesce_pass(engine.PASS_MAX), engine.coalesce_long(-1)
+    cells = []
+    print("library %s, default group %d, default long threshold %d" % (engine.LIB_PATH, default_group, default_long))
+    for m in [int(x) for x in args.ms.split(",")]:
+        W, LW = engine.pass_width(m), engine.long_width(m)
+        pats, j = [], 0
+        while len(pats) < W + 2 * LW:
+            p = text.pattern(splitmix64(PATTERN_SALT + 4096 * j + m) % (n - m), m)
+            j += 1
+            if engine.kernel_for("hor", p) == "hor_scan":
+                pats.append(p)
+        plans = [Plan("hor", p) for p in pats]
+        want = None
+        for least in (-1, 0):
+            engine.coalesce_long(least)
+            for pl in plans:
+                pl.reset()
+            rounds = []
+            engine.device_sync(0)
+            passes0 = engine.coalesce_stats(0)[1]
+            for r in range(args.rounds + 1):  # round 0 warms up
+                engine.stream_mark(0, 0)
+                for pl in plans:
+                    pl.launch(text, slot=0)
+                engine.stream_mark(0, 1)
+                rounds.append(engine.stream_elapsed_ms(0) / len(plans))
+            engine.device_sync(0)
+            passes = (engine.coalesce_stats(0)[1] - passes0) / (args.rounds + 1)
+            got = [pl.result(0)[0] for pl in plans]
+            want = want or got
+            ok = got == want and all(c >= args.rounds + 1 and c % (args.rounds + 1) == 0 for c in got)
+            rounds = sorted(rounds[1:])
+            cell = {"m": m, "long": least, "width": LW if least == 0 else W, "plans": len(plans), "ms": round(rounds[len(rounds) // 2], 5),
+                    "best": round(rounds[0], 5), "worst": round(rounds[-1], 5), "passes": round(passes, 2), "count_ok": ok}
+            cells.append(cell)
+            print("m %-4d long %-2d width %-3d plans %-3d  %.5f ms per pattern (best %.5f worst %.5f)  %.2f passes  %s"
+                  % (m, least, cell["width"], len(plans), cell["ms"], cell["best"], cell["worst"], passes, "ok" if ok else "COUNT MISMATCH"), flush=True)
+        for pl in plans:
+            pl.free()
+    engine.coalesce_long(default_long)
+    engine.coalesce_pass(default_group)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"library": engine.LIB_PATH, "cells": cells}, f, indent=1)
+    if not all(c["count_ok"] for c in cells):
+        raise SystemExit("COUNT MISMATCH")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ms", default="16,32,256")
@@ -40,8 +101,11 @@ def main():
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--plans", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--long", action="store_true", help="long passes against by-value passes: see long_sweep")
     ap.add_argument("--out")
     args = ap.parse_args()
+    if args.long:
+        return long_sweep(args)
     ints = lambda s: [int(x) for x in s.split(",")]  # noqa: E731
 
     import smart_amd
