@@ -324,6 +324,24 @@ int smartgpu_coalesce_stats(int device, uint64_t *launches, uint64_t *passes);
  * them is counted in `passes` once, as any kernel sent; a key is sent when its other launches reach the coalesce setting
  * or when launches and riders together fill the room a pass of their length has. */
 int smartgpu_coalesce_riders(int device, uint64_t *riders);
+/* SAMPLED passes.  A text created by smartgpu_text_upload(), _upload_tiled() or _generate() with at least `min_bytes`
+ * bytes gets a SAMPLE: the 4 bytes at every 28th position, n / 7 bytes of device memory, written once behind the
+ * alphabet pass and freed with the text.  -1: no text created from now on gets one; 0: every text does.  Returns the
+ * previous value, SMARTGPU_ERR_ARG for a value below -1; texts that exist keep what they have.  A failed allocation of
+ * the sample is no error: the text has none.  The library starts with 64 MiB. */
+long long smartgpu_text_sampling(long long min_bytes);
+int smartgpu_text_has_sample(const smartgpu_text *t);
+/* A shared pass over a text that has a sample, for patterns of 31 bytes or more, reads the sample instead of the text
+ * (hor_sample_scan): every window that long holds one sampled 4-byte gram whole, so the pass filters on the sample
+ * and compares, in the text, only the windows whose gram equals a gram of one of its patterns.  Counts are exact.
+ * Such a pass takes 84 patterns at every length, 252 as a long pass.  on = 0 sends every pass to hor_multi_scan as
+ * before; returns the previous value.  Needs no device; what is pending is sent first.  The library starts with 1. */
+int smartgpu_coalesce_sample(int on);
+/* How many passes on `device` went to hor_sample_scan (they are among the `passes` of smartgpu_coalesce_stats). */
+int smartgpu_coalesce_sampled(int device, uint64_t *passes);
+/* The workgroups of a sampled pass: 0 = one per compute unit (the default), 1..65536 = that many, fewer where the
+ * range has fewer rows of 4096 samples.  For measurements and tests; returns the previous value. */
+int smartgpu_coalesce_sample_grid(int workgroups);
 
 /* Host-side preprocessing exposed for tests (same tables the kernels stage in
  * LDS): writes up to `cap` 32-bit entries, returns the number written or <0.

@@ -33,6 +33,7 @@
 #include "planes3.hpp"
 #include "planes3_host.hpp"
 #include "route.hpp"
+#include "sample.hpp"
 #include "tables.hpp"
 #include "text_rate.hpp"
 
@@ -182,6 +183,9 @@ struct smartgpu_text {
     // -1: none (text_no_alphabet, a text of fewer than two bytes).  What queue_launch asks before a pattern whose own
     // symbols repeat may ride in a shared pass.
     double rate = -1.0;
+    // the 4 bytes at every 28th position (sample.hpp), written once behind the alphabet pass; null: the text has none
+    // (smartgpu_text_sampling, a one-search upload, or no memory for it) and its passes read the text itself
+    uint32_t* sample = nullptr;
 };
 
 struct smartgpu_plan {
@@ -191,6 +195,7 @@ struct smartgpu_plan {
     sg::PlanWords words;  // see build_blob
     uint8_t* blob = nullptr;               // device: pattern + tables
     uint8_t tail[sg::kTailRow] = {};       // host: the pattern's end as a shared pass takes it by value (multi.hpp)
+    uint8_t head[sg::kSampleRow] = {};     // host: its first 31 bytes as a sampled pass takes them by value (sample.hpp)
     unsigned long long* results = nullptr; // device: kResultSlots counters (library-owned)
     unsigned long long* ext_results = nullptr; // caller-owned device buffer, if set
     int ext_slots = 0;
@@ -310,6 +315,29 @@ bool text_no_alphabet(smartgpu_text* t, DeviceCtx* d)
         return false;
     }
     return true;
+}
+
+// The least text, in bytes, that gets a sample when it is created; -1: none does (smartgpu_text_sampling).  The sample
+// costs a read of the text when it is made and n / 7 bytes while the text lives (profiles/coalesce/RESULTS.md).
+std::atomic<long long> g_text_sampling{64ll << 20};
+
+// The sample of a text that has just been written, built on the text's stream behind the alphabet pass.  Nothing here
+// is an error: a text without a sample is searched as before.
+void text_sample(smartgpu_text* t, DeviceCtx* d)
+{
+    const long long least = g_text_sampling.load(std::memory_order_relaxed);
+    if (least < 0 || t->n < static_cast<uint64_t>(least) || !sg::g_sample_build) return;
+    uint32_t* s = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&s), sg::sample_alloc_dwords(t->n) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    if (sg::g_sample_build(t->data(), t->n, s, d->num_cus, d->stream) != hipSuccess || hipStreamSynchronize(d->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(s);
+        return;
+    }
+    t->sample = s;
 }
 
 // Build the device blob (pattern + tables) for (algo, P, m) in `blob` (cleared first; a caller that builds many
@@ -724,7 +752,12 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // some 10 us, the host's 1.3 us per launch bounds the run and not the GPU, and a second read costs nothing that a longer
 // wait would win back.  Long passes exist under the widest setting (kPassMax) only: a narrower one asks for exactly
 // that many launches per pass.
-struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; uint8_t tail[sg::kTailRow]; };
+// SAMPLED passes.  A key whose text has a sample (sample.hpp) and whose patterns have at least kSampleMinM = 31 bytes is
+// sent to hor_sample_scan (k_hors.hip) while smartgpu_coalesce_sample is on: the same arguments in both layouts with the
+// patterns' FIRST bytes for rows, 84 by value at every length and 252 in a long pass, and the room a key has follows the
+// kernel it will be sent to.  Which launches are eligible, the riders, the rule for long passes and the key of one
+// launch are as they were.  An entry carries its text's sample pointer and its plan's head row.
+struct QueuedScan { int algo; sg::ScanArgs a; sg::TextCodes codes; uint8_t tail[sg::kTailRow]; uint8_t head[sg::kSampleRow]; const uint32_t* sample; };
 bool same_key(const sg::ScanArgs& x, const sg::ScanArgs& a) { return x.text == a.text && x.s_begin == a.s_begin && x.s_end == a.s_end && x.m == a.m && x.halo == a.halo; }
 struct QueuedKey {
     sg::ScanArgs key;  // text, s_begin, s_end, m, halo
@@ -767,6 +800,7 @@ struct LaunchQueue {
     bool off = false;             // smartgpu_stream_handle gave the stream out: its holder orders their own work on it
     uint64_t launches = 0, passes = 0;  // eligible launches seen / kernels sent for them
     uint64_t riders = 0;                // launches that rode in a key's pass (not among `launches`)
+    uint64_t sampled = 0;               // the passes among `passes` that went to hor_sample_scan
 };
 LaunchQueue g_queue[kMaxDevices];
 // the least range, in bytes of start positions, whose keys gather long passes; -1: none do (smartgpu_coalesce_long)
@@ -779,6 +813,14 @@ std::atomic<long long> g_coalesce_long{64ll << 20};
 // 256 as well (profiles/coalesce/RESULTS.md), so no length gets a cap beyond what its rows leave room for.
 constexpr int kCoalesceNarrow = 8;
 std::atomic<int> g_coalesce{sg::kPassMax};
+// sampled passes on / off (smartgpu_coalesce_sample), and the workgroups of one (smartgpu_coalesce_sample_grid; 0: one per CU)
+std::atomic<int> g_coalesce_sample{1};
+std::atomic<int> g_sample_grid{0};
+// does a pass of length m over a text with this sample go to hor_sample_scan?
+bool pass_sampled(const uint32_t* sample, uint32_t m)
+{
+    return sample && m >= sg::kSampleMinM && sg::g_hor_sample && g_coalesce_sample.load(std::memory_order_relaxed) != 0;
+}
 
 // send one key's launches (q.mu held); makes the device current
 hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
@@ -799,17 +841,31 @@ hipError_t send_key(const DeviceCtx* d, LaunchQueue& q, QueuedKey& k)
         ma.m = k.key.m;
         ma.halo = k.key.halo & 0xFFu;  // as prepare_scan_args: H without the plan's marks
         ma.np = k.n;
-        ma.stride = sg::tail_stride(k.key.m);
-        if (k.n <= sg::pass_width(k.key.m)) {
-            ma.width = sg::pass_width(k.key.m);
-            ma.reserved = sg::kMultiByValue;
-            for (uint32_t j = 0; j < k.n; ++j) sg::multi_set(ma, j, k.scans[j].a.blob, k.scans[j].a.count, k.scans[j].tail);
-        } else {  // a long pass: the pointers alone, the rows are read from the blobs
-            ma.width = sg::long_width(k.key.m);
-            ma.reserved = sg::kMultiLong;
-            for (uint32_t j = 0; j < k.n; ++j) sg::multi_set_long(ma, j, k.scans[j].a.blob, k.scans[j].a.count);
+        const uint32_t* sample = k.scans[0].sample;  // (a key has one text)
+        if (pass_sampled(sample, k.key.m)) {  // over the sample: the patterns' heads by value, or the pointers alone
+            const bool by_value = k.n <= sg::kSampleWidth;
+            ma.stride = sg::kSampleRow;
+            ma.width = by_value ? sg::kSampleWidth : sg::kSampleLongWidth;
+            ma.reserved = by_value ? sg::kMultiByValue : sg::kMultiLong;
+            for (uint32_t j = 0; j < k.n; ++j) {
+                if (by_value) sg::sample_set(ma, j, k.scans[j].a.blob, k.scans[j].a.count, k.scans[j].head);
+                else sg::multi_set_long(ma, j, k.scans[j].a.blob, k.scans[j].a.count);
+            }
+            e = sg::g_hor_sample(ma, sample, d->num_cus, g_sample_grid.load(std::memory_order_relaxed), d->stream);
+            if (e == hipSuccess) ++q.sampled;
+        } else {
+            ma.stride = sg::tail_stride(k.key.m);
+            if (k.n <= sg::pass_width(k.key.m)) {
+                ma.width = sg::pass_width(k.key.m);
+                ma.reserved = sg::kMultiByValue;
+                for (uint32_t j = 0; j < k.n; ++j) sg::multi_set(ma, j, k.scans[j].a.blob, k.scans[j].a.count, k.scans[j].tail);
+            } else {  // a long pass: the pointers alone, the rows are read from the blobs
+                ma.width = sg::long_width(k.key.m);
+                ma.reserved = sg::kMultiLong;
+                for (uint32_t j = 0; j < k.n; ++j) sg::multi_set_long(ma, j, k.scans[j].a.blob, k.scans[j].a.count);
+            }
+            e = sg::g_hor_multi(ma, d->num_cus, d->stream);
         }
-        e = sg::g_hor_multi(ma, d->num_cus, d->stream);
     }
     if (k.n && e == hipSuccess) ++q.passes;
     k.n = 0;
@@ -866,7 +922,8 @@ DeviceCtx* device_ctx_flushed(int device)
 // with none it is the caller's to launch, as before — so a text whose patterns all repeat never forms a pass of them.
 // It counts neither in `launches` nor toward the coalesce setting; it does take one of the pass_width(m) places a key has.
 hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words, const sg::ScanArgs& a, const sg::TextCodes& codes,
-                        double text_rate, const uint8_t (&tail)[sg::kTailRow], bool timed, bool* queued)
+                        double text_rate, const uint8_t (&tail)[sg::kTailRow], const uint8_t (&head)[sg::kSampleRow], const uint32_t* sample,
+                        bool timed, bool* queued)
 {
     *queued = false;
     if (a.s_end <= a.s_begin) return hipSuccess;
@@ -902,13 +959,18 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
     qs.a = a;
     qs.codes = codes;
     std::memcpy(qs.tail, tail, sg::kTailRow);
+    std::memcpy(qs.head, head, sg::kSampleRow);
+    qs.sample = sample;
     if (rider) ++q.riders; else ++k.streaming;
-    const uint32_t room = sg::pass_width(a.m);  // (at most kPassMax, the room a key has)
+    // the room a key has follows the kernel it will be sent to (at most kPassMax by value)
+    const bool sampled = pass_sampled(sample, a.m);
+    const uint32_t room = sampled ? sg::kSampleWidth : sg::pass_width(a.m);
+    const uint32_t long_room = sampled ? sg::kSampleLongWidth : sg::long_width(a.m);
     const uint32_t width = static_cast<uint32_t>(G) < room ? static_cast<uint32_t>(G) : room;
     // a long pass (the rule stands above the queue): launches and riders together, up to long_width(m)
     const long long least = g_coalesce_long.load(std::memory_order_relaxed);
     const bool gather_on = G == sg::kPassMax && least >= 0 && a.s_end - a.s_begin >= static_cast<uint64_t>(least) && q.was_full(a);
-    if (gather_on ? k.n >= sg::long_width(a.m) : (k.streaming >= width || k.n >= room)) {
+    if (gather_on ? k.n >= long_room : (k.streaming >= width || k.n >= room)) {
         q.note_full(k.key);
         const hipError_t e = send_key(d, q, k);
         if (e != hipSuccess && err == hipSuccess) err = e;
@@ -922,6 +984,9 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
 
 namespace sg {
 hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // multi.hpp: set by k_horm.hip where that unit is linked
+// sample.hpp: set by k_hors.hip where that unit is linked
+hipError_t (*g_hor_sample)(const MultiArgs&, const uint32_t*, int, int, hipStream_t) = nullptr;
+hipError_t (*g_sample_build)(const uint8_t*, uint64_t, uint32_t*, int, hipStream_t) = nullptr;
 hipError_t (*g_hor_preload)() = nullptr;  // launch_common.hpp: set by k_hor.hip where that unit is linked
 int (*g_text_histogram)(const uint8_t*, uint64_t, unsigned long long*, int, void*) = nullptr;  // text_rate.hpp: set by k_util.hip where that unit is linked
 // pedit.hpp: set by k_pedit.hip where that unit is linked
@@ -1002,6 +1067,7 @@ static smartgpu_text* text_upload_impl(const void* host, uint64_t n, int device,
     }
     hipStreamSynchronize(d->stream);
     if (!(alphabet ? text_alphabet(t, d) : text_no_alphabet(t, d))) { smartgpu_text_free(t); return nullptr; }
+    if (alphabet) text_sample(t, d);
     return t;
 }
 
@@ -1025,6 +1091,7 @@ smartgpu_text* smartgpu_text_upload_tiled(const void* unit, uint64_t unit_len, u
         return nullptr;
     }
     if (!text_alphabet(t, d)) { smartgpu_text_free(t); return nullptr; }
+    text_sample(t, d);
     return t;
 }
 
@@ -1042,6 +1109,7 @@ smartgpu_text* smartgpu_text_generate(uint64_t seed, int sigma, uint64_t off, ui
         return nullptr;
     }
     if (!text_alphabet(t, d)) { smartgpu_text_free(t); return nullptr; }
+    text_sample(t, d);
     return t;
 }
 
@@ -1055,6 +1123,7 @@ void smartgpu_text_free(smartgpu_text* t)
             if (e != hipSuccess) set_error("text_free: a queued launch failed: %s", hipGetErrorString(e));
         }
         hipFree(t->base);
+        if (t->sample) hipFree(t->sample);
     }
     delete t;
 }
@@ -1100,6 +1169,7 @@ smartgpu_plan* smartgpu_plan_create(int algo, const uint8_t* P, uint32_t m, int 
     std::vector<uint8_t> blob;
     p->words = build_blob(blob, algo, P, m);
     sg::tail_fill(p->tail, P, m);
+    sg::sample_head_fill(p->head, P, m);
     if ((algo == SMARTGPU_HOR || algo == SMARTGPU_TUNEDBM) && sg::g_hor_preload && !d->hor_preloaded) {
         // hor_scan's code object and kernels now, not at the first launch that cannot share a pass (k_hor.hip)
         d->hor_preloaded = true;
@@ -1150,7 +1220,7 @@ int smartgpu_plan_launch(smartgpu_plan* p, const smartgpu_text* text, uint64_t o
     if (!d) return SMARTGPU_ERR_HIP;
     const sg::ScanArgs a = make_args(p->words, p->m, p->blob, p->slot_ptr(slot), text, off, n);
     bool queued = false;
-    HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), text->rate, p->tail, timed != 0, &queued), return SMARTGPU_ERR_HIP);
+    HIP_TRY(queue_launch(d, p->algo, p->words, a, text->codes(), text->rate, p->tail, p->head, text->sample, timed != 0, &queued), return SMARTGPU_ERR_HIP);
     if (queued) { p->timed[slot] = false; return SMARTGPU_OK; }
     HIP_TRY(hipSetDevice(p->device), return SMARTGPU_ERR_HIP);
     // A timed launch keeps its place behind what was queued before it: its events bracket this kernel alone.  Any other
@@ -1315,6 +1385,35 @@ int smartgpu_coalesce_stats(int device, uint64_t* launches, uint64_t* passes)
     if (passes) *passes = g_queue[device].passes;
     return SMARTGPU_OK;
 }
+
+int smartgpu_coalesce_sample(int on)
+{
+    flush_all_queues();
+    return g_coalesce_sample.exchange(on != 0 ? 1 : 0);
+}
+
+int smartgpu_coalesce_sample_grid(int workgroups)
+{
+    if (workgroups < 0 || workgroups > 65536) { set_error("coalesce_sample_grid: 1..65536 workgroups (0: one per compute unit), not %d", workgroups); return SMARTGPU_ERR_ARG; }
+    flush_all_queues();
+    return g_sample_grid.exchange(workgroups);
+}
+
+int smartgpu_coalesce_sampled(int device, uint64_t* passes)
+{
+    if (device < 0 || device >= kMaxDevices || !passes) { set_error("bad coalesce_sampled arguments (device %d)", device); return SMARTGPU_ERR_ARG; }
+    std::lock_guard<std::mutex> lock(g_queue[device].mu);
+    *passes = g_queue[device].sampled;
+    return SMARTGPU_OK;
+}
+
+long long smartgpu_text_sampling(long long min_bytes)
+{
+    if (min_bytes < -1) { set_error("text_sampling: the least text that gets a sample has 0 or more bytes (-1: none gets one), not %lld", min_bytes); return SMARTGPU_ERR_ARG; }
+    return g_text_sampling.exchange(min_bytes);
+}
+
+int smartgpu_text_has_sample(const smartgpu_text* t) { return t && t->sample ? 1 : 0; }
 
 int smartgpu_coalesce_riders(int device, uint64_t* riders)
 {

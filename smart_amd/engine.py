@@ -103,6 +103,11 @@ def _load(path):
         "smartgpu_coalesce_long": (C.c_longlong, [C.c_longlong]),
         "smartgpu_coalesce_stats": (i32, [i32, C.POINTER(u64), C.POINTER(u64)]),
         "smartgpu_coalesce_riders": (i32, [i32, C.POINTER(u64)]),
+        "smartgpu_text_sampling": (C.c_longlong, [C.c_longlong]),
+        "smartgpu_text_has_sample": (i32, [vp]),
+        "smartgpu_coalesce_sample": (i32, [i32]),
+        "smartgpu_coalesce_sampled": (i32, [i32, C.POINTER(u64)]),
+        "smartgpu_coalesce_sample_grid": (i32, [i32]),
         "smartgpu_mtext_upload": (vp, [vp, u64, i32, vp]),
         "smartgpu_mtext_generate": (vp, [u64, i32, u64, i32, vp]),
         "smartgpu_mtext_free": (None, [vp]),
@@ -915,6 +920,47 @@ def coalesce_riders(device=0):
     if lib().smartgpu_coalesce_riders(device, C.byref(riders)) != 0:
         raise _err("coalesce_riders")
     return int(riders.value)
+
+
+SAMPLING_DEFAULT = 64 << 20
+SAMPLE_STRIDE, SAMPLE_GRAM, SAMPLE_MIN_M = 28, 4, 31
+SAMPLE_WIDTH, SAMPLE_LONG_WIDTH = 84, 252
+
+
+def text_sampling(min_bytes):
+    """The least text, in bytes, that gets a sample when it is created — the 4 bytes at every 28th position, n / 7 bytes
+    (-1: none, 0: every text; the library starts with SAMPLING_DEFAULT); returns the previous value."""
+    prev = lib().smartgpu_text_sampling(min_bytes)
+    if prev < -1:
+        raise _err("text_sampling")
+    return prev
+
+
+def text_has_sample(text):
+    """Does this Text carry a sample?"""
+    return bool(lib().smartgpu_text_has_sample(text._h))
+
+
+def coalesce_sample(on):
+    """Shared passes of patterns of 31 bytes or more over a text that has a sample read the sample, not the text
+    (hor_sample_scan); False sends them to hor_multi_scan as before.  Returns the previous setting."""
+    return bool(lib().smartgpu_coalesce_sample(1 if on else 0))
+
+
+def coalesce_sampled(device=0):
+    """Passes on `device` so far that went to hor_sample_scan (they are among coalesce_stats()' passes)."""
+    passes = C.c_uint64(0)
+    if lib().smartgpu_coalesce_sampled(device, C.byref(passes)) != 0:
+        raise _err("coalesce_sampled")
+    return int(passes.value)
+
+
+def coalesce_sample_grid(workgroups):
+    """The workgroups of a sampled pass (0: one per compute unit); for measurements and tests.  Returns the previous value."""
+    prev = lib().smartgpu_coalesce_sample_grid(workgroups)
+    if prev < 0:
+        raise _err("coalesce_sample_grid")
+    return prev
 
 
 def kernel_for(algo, P):

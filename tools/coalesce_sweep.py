@@ -92,8 +92,96 @@ def long_sweep(args):
         raise SystemExit("COUNT MISMATCH")
 
 
+def sample_sweep(args):
+    """--sample: sampled passes (hor_sample_scan) against hor_multi_scan, per text size (--mib) and length (--ms), in passes
+    of --widths patterns (0: the long width — a round launches the by-value width and then the long width, two passes).
+    Every text is created with smartgpu_text_sampling(0); a cell is measured with smartgpu_coalesce_sample on and off over
+    the same text, plans and events: ms per pattern, the kernels of a round, how many of them were sampled, every count
+    against the first cell's.  A library without the calls (the parent's, through SMARTGPU_LIB) measures the `off` cells
+    only.  Also the host time of Text.generate per size, which holds the sample's build where the library has one."""
+    import time
+    import smart_amd
+    from smart_amd import Plan, Text, engine
+    if smart_amd.device_count() < 1:
+        raise SystemExit("no GPU: " + engine.lib().smartgpu_last_error().decode())
+    has = hasattr(engine.lib(), "smartgpu_coalesce_sample")
+    default_group, default_long = engine.coalesce_pass(engine.PASS_MAX), engine.coalesce_long(0)
+    default_sampling = engine.text_sampling(0) if has else None
+    cells = []
+    print("library %s, sampled passes %s" % (engine.LIB_PATH, "yes" if has else "no"))
+    for mib in [int(x) for x in args.mib.split(",")]:
+        n = mib << 20
+        made = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            text = Text.generate(SEED, args.sigma, n)
+            made.append((time.perf_counter() - t0) * 1e3)
+            text.free()
+        text = Text.generate(SEED, args.sigma, n)
+        engine.probe_read_gbs(text, reps=16)  # clocks
+        print("%d MiB: Text.generate %.3f ms (best of 3), sample %s" % (mib, min(made), "yes" if has and engine.text_has_sample(text) else "no"), flush=True)
+        for m in [int(x) for x in args.ms.split(",")]:
+            for width in [int(x) for x in args.widths.split(",")]:
+                want = None
+                for on in ((True, False) if has else (False,)):
+                    if has:
+                        engine.coalesce_sample(on)
+                    W = engine.SAMPLE_WIDTH if on else engine.pass_width(m)
+                    LW = engine.SAMPLE_LONG_WIDTH if on else engine.long_width(m)
+                    count = W + LW if width == 0 else min(width, W)
+                    engine.coalesce_pass(engine.PASS_MAX if width == 0 or count >= W else max(2, count))
+                    pats, j = [], 0
+                    while len(pats) < count:
+                        p = text.pattern(splitmix64(PATTERN_SALT + 4096 * j + m) % (n - m), m)
+                        j += 1
+                        if engine.kernel_for("hor", p) == "hor_scan":
+                            pats.append(p)
+                    plans = [Plan("hor", p) for p in pats]
+                    rounds = []
+                    engine.device_sync(0)
+                    passes0, sampled0 = engine.coalesce_stats(0)[1], engine.coalesce_sampled(0) if has else 0
+                    for r in range(args.rounds + 1):  # round 0 warms up
+                        engine.stream_mark(0, 0)
+                        for pl in plans:
+                            pl.launch(text, slot=0)
+                        engine.stream_mark(0, 1)
+                        rounds.append(engine.stream_elapsed_ms(0))
+                    engine.device_sync(0)
+                    passes = (engine.coalesce_stats(0)[1] - passes0) / (args.rounds + 1)
+                    sampled = ((engine.coalesce_sampled(0) if has else 0) - sampled0) / (args.rounds + 1)
+                    got = [pl.result(0)[0] for pl in plans]
+                    for pl in plans:
+                        pl.free()
+                    want = want or got
+                    k = min(len(got), len(want))  # (the long widths differ: the patterns both cells hold)
+                    ok = got[:k] == want[:k] and all(c >= args.rounds + 1 and c % (args.rounds + 1) == 0 for c in got)
+                    rounds = sorted(rounds[1:])
+                    cell = {"mib": mib, "m": m, "width": width, "sampled_on": bool(on), "plans": count, "ms_round": round(rounds[len(rounds) // 2], 5),
+                            "best": round(rounds[0], 5), "worst": round(rounds[-1], 5), "ms_per_pattern": round(rounds[len(rounds) // 2] / count, 6),
+                            "passes": round(passes, 2), "sampled": round(sampled, 2), "count_ok": ok}
+                    cells.append(cell)
+                    print("%5d MiB m %-4d width %-3d sample %-3s plans %-3d  %.4f ms a round (best %.4f worst %.4f) %.5f ms per pattern  %.2f passes, %.2f sampled  %s"
+                          % (mib, m, width, "on" if on else "off", count, cell["ms_round"], cell["best"], cell["worst"], cell["ms_per_pattern"], passes, sampled,
+                             "ok" if ok else "COUNT MISMATCH"), flush=True)
+        text.free()
+    if has:
+        engine.coalesce_sample(True)
+        engine.text_sampling(default_sampling)
+    engine.coalesce_long(default_long)
+    engine.coalesce_pass(default_group)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"library": engine.LIB_PATH, "cells": cells}, f, indent=1)
+    if not all(c["count_ok"] for c in cells):
+        raise SystemExit("COUNT MISMATCH")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sample", action="store_true", help="sampled passes against hor_multi_scan per text size: see sample_sweep")
+    ap.add_argument("--mib", default="1,4,16,64,256,1024", help="with --sample: text sizes in MiB")
+    ap.add_argument("--widths", default="8,32,84,0", help="with --sample: patterns per pass (0: the long width)")
     ap.add_argument("--ms", default="16,32,256")
     ap.add_argument("--groups", default="0,2,4,8")
     ap.add_argument("--wgs", default="0,4,5,6,7")
@@ -106,6 +194,8 @@ def main():
     args = ap.parse_args()
     if args.long:
         return long_sweep(args)
+    if args.sample:
+        return sample_sweep(args)
     ints = lambda s: [int(x) for x in s.split(",")]  # noqa: E731
 
     import smart_amd

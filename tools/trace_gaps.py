@@ -4,7 +4,7 @@
     rocprofv3 --kernel-trace --output-format csv -d DIR -o trace -- python bench.py --steps 200 --warmup 50 > DIR/bench.json
     python tools/trace_gaps.py DIR/trace_kernel_trace.csv [DIR/bench.json]
 
-The timed region is the last run of scan dispatches (hor_multi_scan, hor_scan) that no other kernel interrupts.  Printed:
+The timed region is the last run of scan dispatches (hor_multi_scan, hor_sample_scan, hor_scan) that no other kernel interrupts.  Printed:
 the dispatches of the region by kernel, the distribution of end(k) -> begin(k + 1) over its boundaries, the sum of the
 durations against the span from the first begin to the last end, and — with bench.py's result line — the span between
 the two events (kernel_ms x steps) against that, which is what lies before the first dispatch and after the last."""
@@ -17,7 +17,7 @@ import sys
 
 def main():
     rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
-    scan = lambda r: "hor_multi_scan" in r["Kernel_Name"] or "hor_scan" in r["Kernel_Name"]  # noqa: E731
+    scan = lambda r: any(k in r["Kernel_Name"] for k in ("hor_multi_scan", "hor_sample_scan", "hor_scan"))  # noqa: E731
     last = max(i for i, r in enumerate(rows) if scan(r))
     first = last
     while first > 0 and scan(rows[first - 1]):
