@@ -312,7 +312,9 @@ int smartgpu_coalesce_pass(int max_group);
  * sent at once, unless its range holds at least `min_range_bytes` start positions AND the previous pass over the same
  * text, range and length left because it was full, with nothing since that sent what was pending (a sync, a result, a
  * mark, a setting): then the launches arrive faster than the GPU reads the text, and the key gathers up to the long
- * width, or until the next such call, and saves a read of the text.  -1: no long passes; 0: any range.  Returns the
+ * width, or until the next such call, and saves a read of the text.  The same holds for the first pass of a key whose
+ * launches came so fast (the host clock at its first launch and at the one that fills it) that gathering on idles the
+ * GPU for less than a pass over the range takes, where that is 10 us or more.  -1: no long passes; 0: any range.  Returns the
  * previous value (-1 or more), SMARTGPU_ERR_ARG for a value below -1.  Needs no device; what is pending is sent first.
  * The library starts with 64 MiB (profiles/coalesce/RESULTS.md has the measurements). */
 long long smartgpu_coalesce_long(long long min_range_bytes);

@@ -748,7 +748,15 @@ sg::ScanArgs make_args(const sg::PlanWords& pw, uint32_t m, const uint8_t* blob,
 // pass of that key is on the stream or was a moment ago, the launches come faster than the GPU reads, and the key goes on
 // gathering to long_width(m); it is sent there, or by the next flush, in the long layout if it holds more than
 // pass_width(m) entries.  After any flush the GPU is presumably idle, and the first pass of a key leaves at
-// pass_width(m) again: waiting longer would only lengthen the lead-in.  (a): below 64 MiB a read of the range takes
+// pass_width(m) again: waiting longer would only lengthen the lead-in, UNLESS (c) the launches arrive faster than that:
+// (b) was chosen when a launch cost the host a microsecond (ctypes) and pass_width(m) of them took longer than a pass.
+// Through the native binding (fastcall.cpp) a launch takes 40 ns, 84 of them 3 us, and a first pass sent at 84 only
+// makes the second wait behind it: on the flagship 34 + 34 us in two passes against 42 us in one of 200
+// (profiles/coalesce/RESULTS.md).  So the key notes the host clock when it is opened, and the launch that fills it to
+// pass_width(m) reads it once more: what the GPU would idle while the key gathers on to long_width(m), at the rate its
+// launches came so far, against what a pass over the range takes (pass_estimate_ns; a pass estimated below 10 us, 44 MB
+// of text or 308 MB under a sample, is sent as ever).  Shorter: the key goes on gathering as under (b).  Two reads of the clock per key, none in any other launch, and still no HIP call.
+// (a): below 64 MiB a read of the range takes
 // some 10 us, the host's 1.3 us per launch bounds the run and not the GPU, and a second read costs nothing that a longer
 // wait would win back.  Long passes exist under the widest setting (kPassMax) only: a narrower one asks for exactly
 // that many launches per pass.
@@ -763,6 +771,8 @@ struct QueuedKey {
     sg::ScanArgs key;  // text, s_begin, s_end, m, halo
     uint32_t n = 0;          // entries: streaming launches and riders
     uint32_t streaming = 0;  // the streaming launches among them: what the coalesce setting counts
+    int64_t opened_ns = 0;   // the host clock when the key was opened (rule (c) of the long passes)
+    bool fast = false;       // (c) held when the key reached pass_width(m): it gathers on to long_width(m)
     QueuedScan scans[sg::kLongMax];
     bool holds(const sg::ScanArgs& a) const { return same_key(key, a); }
     void take(const QueuedKey& o)  // (the entries it holds, not all kLongMax)
@@ -770,6 +780,8 @@ struct QueuedKey {
         key = o.key;
         n = o.n;
         streaming = o.streaming;
+        opened_ns = o.opened_ns;
+        fast = o.fast;
         std::memcpy(static_cast<void*>(scans), static_cast<const void*>(o.scans), o.n * sizeof(QueuedScan));
     }
 };
@@ -820,6 +832,22 @@ std::atomic<int> g_sample_grid{0};
 bool pass_sampled(const uint32_t* sample, uint32_t m)
 {
     return sample && m >= sg::kSampleMinM && sg::g_hor_sample && g_coalesce_sample.load(std::memory_order_relaxed) != 0;
+}
+
+int64_t host_ns()
+{
+    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+// What a pass over `range` start positions takes, for rule (c) of the long passes: the bytes it reads (a sampled pass
+// 4 of every 28) at 4.4 TB/s, the rate of hor_sample_scan on 1 GiB (35 us; hor_multi_scan reads 1 GiB in 180 us, 5.9 TB/s:
+// the estimate is a third too long there, on the side of gathering).  A rule of thumb for a choice between one pass and
+// two, not a model.
+// Below 10 us the estimate decides nothing: such a pass is mostly its prologue and the dispatch, which it leaves out.
+constexpr int64_t kFastLeastNs = 10000;
+int64_t pass_estimate_ns(uint64_t range, bool sampled)
+{
+    const uint64_t bytes = sampled ? range / (sg::kSampleStride / sg::kSampleGram) : range;
+    return static_cast<int64_t>(bytes / 4400u);
 }
 
 // send one key's launches (q.mu held); makes the device current
@@ -952,6 +980,8 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
         q.keys[at].key = a;
         q.keys[at].n = 0;
         q.keys[at].streaming = 0;
+        q.keys[at].fast = false;
+        q.keys[at].opened_ns = host_ns();
     }
     QueuedKey& k = q.keys[at];  // (has room: a key that reached its width was sent by the launch that filled it)
     QueuedScan& qs = k.scans[k.n++];
@@ -969,8 +999,15 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
     const uint32_t width = static_cast<uint32_t>(G) < room ? static_cast<uint32_t>(G) : room;
     // a long pass (the rule stands above the queue): launches and riders together, up to long_width(m)
     const long long least = g_coalesce_long.load(std::memory_order_relaxed);
-    const bool gather_on = G == sg::kPassMax && least >= 0 && a.s_end - a.s_begin >= static_cast<uint64_t>(least) && q.was_full(a);
-    if (gather_on ? k.n >= long_room : (k.streaming >= width || k.n >= room)) {
+    const bool may_gather = G == sg::kPassMax && least >= 0 && a.s_end - a.s_begin >= static_cast<uint64_t>(least);
+    const bool full = k.streaming >= width || k.n >= room;
+    if (may_gather && full && !k.fast && k.n < long_room && !q.was_full(a)) {  // (c), asked once: by the launch that fills the key
+        const int64_t waited = host_ns() - k.opened_ns;  // for k.n launches; long_room - k.n more would take about as long each
+        const int64_t pass_ns = pass_estimate_ns(a.s_end - a.s_begin, sampled);
+        k.fast = pass_ns >= kFastLeastNs && waited >= 0 && waited / k.n * (long_room - k.n) < pass_ns;
+    }
+    const bool gather_on = may_gather && (k.fast || q.was_full(a));
+    if (gather_on ? k.n >= long_room : full) {
         q.note_full(k.key);
         const hipError_t e = send_key(d, q, k);
         if (e != hipSuccess && err == hipSuccess) err = e;

@@ -1,4 +1,5 @@
-"""ctypes binding of libsmartgpu.so (include/smartgpu.h).
+"""ctypes binding of libsmartgpu.so (include/smartgpu.h); Plan.launch, the call that sits in a caller's loop, goes
+through the native extension smart_amd._fastcall (csrc/fastcall.cpp) where that was built.
 
 Mirrors SMART's plugin surface: a *text* loaded once (smart.c:553-568,95-138),
 *patterns* cut from it (smart.c:148-158), and per-algorithm `search` calls that
@@ -26,6 +27,42 @@ _lib = None
 
 class SmartGpuError(RuntimeError):
     pass
+
+
+# Plan.launch without ctypes: base types of Text and Plan that hold the handle (and the text's length) and call
+# smartgpu_plan_launch through a pointer from the library that made the plan.  Where the extension is missing (no
+# Python.h when the library was built, another interpreter) or SMARTGPU_BINDING=ctypes is set, launch is the
+# pure-Python one below; nothing else depends on which of them runs.
+_fastcall = None
+if os.environ.get("SMARTGPU_BINDING", "native") != "ctypes":
+    try:
+        from . import _fastcall
+    except ImportError:
+        _fastcall = None
+if _fastcall is not None:
+    _fastcall.set_error_class(SmartGpuError)
+_TextBase = _fastcall.TextBase if _fastcall else object
+_PlanBase = _fastcall.PlanBase if _fastcall else object
+
+
+def binding():
+    """"native": Plan.launch is smart_amd._fastcall's; "ctypes": it is the pure-Python one."""
+    return "native" if _fastcall else "ctypes"
+
+
+def _addr(fn):
+    return C.cast(fn, C.c_void_p).value
+
+
+def _bind_text(text):
+    """Hand a Text's base the entry point it needs, from the library that made the text; before `_h` is set."""
+    if _fastcall:
+        text._bind(_addr(text._L.smartgpu_text_length))
+
+
+def _bind_plan(plan):
+    if _fastcall:
+        plan._bind(_addr(plan._L.smartgpu_plan_launch), _addr(plan._L.smartgpu_last_error))
 
 
 def build():
@@ -198,14 +235,15 @@ def _u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
-class Text:
+class Text(_TextBase):
     """A text resident in one GPU's HBM (the shmget/getText replacement)."""
 
     def __init__(self, handle):
         if not handle:
             raise _err("text")
-        self._h = handle
         self._L = lib()  # the library that made the handle frees it
+        _bind_text(self)
+        self._h = handle
 
     @classmethod
     def upload(cls, data, device=0):
@@ -361,22 +399,26 @@ class PackedText:
             pass
 
 
-class Plan:
+class Plan(_PlanBase):
     """One (algorithm, pattern) preprocessed and resident on a device."""
 
     def __init__(self, algo, P, device=0):
         self.P = _u8(P)
         self.algo = algo
         self._L = lib()
+        _bind_plan(self)
         self._h = self._L.smartgpu_plan_create(algo_id(algo), self.P.ctypes.data, len(self.P), device)
         if not self._h:
             raise _err("plan_create")
 
-    def launch(self, text, slot=0, timed=False, off=0, n=None):
+    def _launch_ctypes(self, text, slot=0, timed=False, off=0, n=None):
         if n is None:
             n = len(text) - off
         if lib().smartgpu_plan_launch(self._h, text._h, off, n, slot, 1 if timed else 0) != 0:
             raise _err("plan_launch")
+
+    if _fastcall is None:
+        launch = _launch_ctypes  # (otherwise _fastcall.PlanBase.launch, same signature)
 
     def result(self, slot=0):
         c = C.c_uint64(0)
@@ -898,7 +940,8 @@ def long_width(m):
 
 def coalesce_long(min_range_bytes):
     """The least range, in bytes, over which a key whose previous pass left full goes on gathering beyond pass_width(m),
-    up to long_width(m) (-1: never, 0: any range; the library starts with LONG_DEFAULT); returns the previous value."""
+    up to long_width(m) (-1: never, 0: any range; the library starts with LONG_DEFAULT); returns the previous value.
+    A key whose launches arrive faster than the GPU could use an early pass gathers on in the same way (api.cpp, rule (c))."""
     prev = lib().smartgpu_coalesce_long(min_range_bytes)
     if prev < -1:
         raise _err("coalesce_long")
