@@ -538,7 +538,7 @@ int smartgpu_pfind_sets_mis64(const uint8_t *sets, uint32_t m, uint32_t k, const
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / sets == NULL, m = 0 or m > SMARTGPU_PEDIT_MAXM (the
  * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
  * cap > 0, and — the sets calls — a set with a bit at or above the text's number of values (the message names the position).
- * NOT offered: affine or weighted costs, a batch call, byte texts.  (m > 64 and k > 7: smartgpu_psearch_editl64 below, up to
+ * NOT offered: affine or weighted costs, a batch call, byte texts.  (Byte texts: smartgpu_search_edit64 below.  m > 64 and k > 7: smartgpu_psearch_editl64 below, up to
  * 256 symbols and 31 edits.  Start positions and alignments: smartgpu_palign_edit64 below.)
  * MEASURED on an MI355X, 1 Gi symbols, m = 8 .. 64, k = 0 .. 7 (profiles/packed/RESULTS.md, "Edit distance"; tools/edit_probe.py):
  * on rand4 planes_edit_scan takes 0.90-1.06 ms for m <= 32 (one dword per column: 1.0-1.2 T symbols/s) and 1.49-1.81 ms for
@@ -651,6 +651,52 @@ int smartgpu_psearch_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, u
                                   uint64_t off, uint64_t n, uint64_t *count, double *pre_ms, double *run_ms);
 int smartgpu_pfind_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext *text,
                                 uint64_t off, uint64_t n, uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+/* EDIT DISTANCE ON A BYTE TEXT: smartgpu_psearch_edit64 / smartgpu_pfind_edit64 asked of a smartgpu_text, whatever number of
+ * byte values it holds — English, protein sequences, rand32 .. rand256, a log file ("where does `recieve` occur within one
+ * edit?").  The contract is that of those calls with "byte" for "symbol": for the range [off, off+n) and every off <= e <
+ * off+n, D(e) is the last row of Sellers' programme on the range alone — D[0][*] = 0, the column before off is D[i] = i —; an
+ * OCCURRENCE is an END position e with D(e) <= k; ends are ascending and relative to text byte 0, distances[i] = D(ends[i]).
+ * 1 <= m <= SMARTGPU_EDIT_MAXM, 0 <= k <= SMARTGPU_PMIS_MAX.  k >= m is legal: every end of the range is an occurrence and its
+ * distance is still reported.  m > n is legal; only n + k < m is "count 0, no launch".  cap / count / SMARTGPU_ERR_NOMEM,
+ * cap == 0 with NULL buffers as a count, distances == NULL and the meaning of pre_ms / run_ms are those of the packed calls
+ * (pre_ms holds the masks' construction and staging).  A pattern byte the text does not hold needs no bookkeeping: it has a bit
+ * in no mask that a text byte selects.  With k = 0 the ends are smartgpu_find64's positions plus m - 1.
+ * CLASSES: position j accepts a SET of byte values, a 256-bit row: classes[32 * j + v / 8] bit v % 8 set means it accepts byte
+ * v (32 * m bytes in all) — case-insensitive search, the protein codes B, Z and X.  An empty row accepts nothing, a full row
+ * everything.  With one bit per row the answers are those of the byte-pattern calls.
+ * One pass over the text (text_edit_scan, text_edit_find; smart_amd/csrc/k_tedit.hip): Myers' bit-vector recurrence in Hyyrö's
+ * search form, one byte per step and lane.  The pattern is 256 masks, one per byte value (1 or 2 KiB, built on the host, read
+ * from LDS by the kernels: they do not know classes from bytes); a workgroup brings 32 KiB of text into LDS with coalesced
+ * loads and every lane walks its 128 end positions, and up to m + k bytes before them without counting, out of LDS.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / classes == NULL, m outside [1, SMARTGPU_EDIT_MAXM] (the
+ * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
+ * cap > 0.  The calls are synchronous: launches pending in the coalescing queue are sent first, and they never enter it.
+ * NOT offered: m > 64 and k > 7, start positions and alignments, Hamming-only search on byte texts, a batch call, MultiText
+ * shards and the `smart` harness.
+ * MEASURED on an MI355X, 1 GiB texts, m = 8, 20, 32, 33, 64, k = 0, 3, 7 (profiles/tedit/RESULTS.md; tools/tedit_probe.py; kernel
+ * times from a kernel trace, call times by the host clock, medians of 5 / 7, run-to-run spread at most 3 % of the median but for the
+ * first cell measured — rand4, m = 8, k = 0: 5-8 % per call): on rand4, rand128 and the English corpus alike text_edit_scan takes 0.71-0.82 ms for m <= 32 (one dword per column:
+ * 1.31-1.52 TB/s of text) and 1.20-1.44 ms for m = 33, 64 (two dwords: 0.75-0.90 TB/s), per call 0.72-0.83 / 1.22-1.46 ms; the time
+ * grows with the warm-up factor (128 + m + k) / 128 and neither with the alphabet nor with the number of occurrences.
+ * AGAINST smartgpu_psearch_edit64 on the same rand4 bytes packed, same P and k: 0.75-0.77 x its kernel time for m <= 32, 0.82-0.84 x
+ * for m = 33, 64 (per call 0.75-0.77 / 0.82-0.84 x), outside the run-to-run spread in every cell: bytes cost nothing, the walk out
+ * of LDS is faster than the walk out of two bit planes.  MASK-LOOKUP CONFLICTS: rand256 (all-distinct lookups) against a text of
+ * one value (all-broadcast lookups) at the same m and k: 0.99-1.00 x, inside the spread in 14 of 15 cells (the kernel trace at
+ * m = 20, k = 0: 0.99 x) — the data-dependent bank conflicts of the mask table are hidden behind the recurrence's arithmetic.
+ * THE PADDED ROW (132 bytes in LDS per 128 of text) against an unpadded build, rand256, k = 3, per call: the unpadded one takes
+ * 1.13-1.15 x for m <= 32 and 1.06 x for m = 33, 64, outside the spread in every cell.
+ * NOT measured: the four workgroups per CU, the run of 128 positions per lane, a
+ * double-buffered tile, the find form's speed, the classes calls (the same kernels, another table), texts beyond 1 GiB, hardware
+ * counters (the conflicts above are inferred from times, not counted). */
+#define SMARTGPU_EDIT_MAXM 64
+int smartgpu_search_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                           uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_find_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                         uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+int smartgpu_search_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                                   uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_find_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                                 uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
 /* No device: the reverse complement of an IUPAC nucleotide pattern — a primer is searched on both strands.  P[0..m): the
  * letters smartgpu_iupac_sets accepts; out[j] = the complement of P[m-1-j]: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and
  * N stay; U reads as T (its complement is A; no U is ever written).  Case is preserved.  out has m bytes (no terminator is

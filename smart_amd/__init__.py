@@ -8,4 +8,5 @@ from .engine import (ALGOS, MIN_M, MultiText, PackedText, Plan, SmartGpuError, T
                      edit_cigar, find, iupac_revcomp, iupac_sets, lib, palign_edit, palign_sets_edit, pfind, pfind_batch, pfind_edit, pfind_edit_align, pfind_mis, pfind_sets, pfind_sets_edit,
                      pfind_editl, pfind_sets_editl, psearch_editl, psearch_sets_editl,
                      pfind_sets_mis, psearch, psearch_batch, psearch_edit, psearch_mis, psearch_sets, psearch_sets_edit, psearch_sets_mis,
-                     ptext_layout, ptext_layout8, search, search_batch, search_host, version)
+                     ptext_layout, ptext_layout8, search,
+                     byte_classes, find_edit, find_edit_classes, search_edit, search_edit_classes, search_batch, search_host, version)

@@ -27,6 +27,7 @@
 #include "multi.hpp"
 #include "pedit.hpp"
 #include "peditl.hpp"
+#include "tedit.hpp"
 #include "palign.hpp"
 #include "planes.hpp"
 #include "planes_host.hpp"
@@ -1032,6 +1033,9 @@ hipError_t (*g_planes_edit_find)(const PlaneEditArgs&, unsigned long long*, unsi
 // peditl.hpp: set by k_peditl.hip where that unit is linked
 hipError_t (*g_planes_editl_scan)(const PlaneEditlArgs&, int, int, hipStream_t) = nullptr;
 hipError_t (*g_planes_editl_find)(const PlaneEditlArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
+// tedit.hpp: set by k_tedit.hip where that unit is linked
+hipError_t (*g_text_edit_scan)(const TextEditArgs&, int, hipStream_t) = nullptr;
+hipError_t (*g_text_edit_find)(const TextEditArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
 // palign.hpp: set by k_palign.hip where that unit is linked
 hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
 // planes3.hpp: set by k_planes3.hip where that unit is linked
@@ -2787,6 +2791,128 @@ int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
     return SMARTGPU_OK;
 }
 
+// ---- edit distance on BYTE texts (tedit.hpp): the contract of the calls above with a smartgpu_text in place of the planes;
+// the pattern is 256 masks (tedit_host.hpp), too many for kernel arguments: they travel through the staging buffer to the
+// arena, as psearch_impl's patterns do ----
+
+// The checks of the four calls that need no device; `what` names the pattern argument.
+int check_tedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off,
+                     uint64_t n, const uint64_t* count)
+{
+    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
+    if (m < 1 || m > SMARTGPU_EDIT_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_EDIT_MAXM); return SMARTGPU_ERR_ARG; }
+    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
+    if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
+    if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
+    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
+    return SMARTGPU_OK;
+}
+
+// The pattern's masks (bytes, or classes) as the kernel's table in the staging buffer, on their way to the arena
+// (batch_reserve has made room).  The staging buffer is free: every call that fills it ends with a synchronisation.
+bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, sg::TextEditArgs* a)
+{
+    uint32_t peq[256][sg::kTEditWords];
+    if (classes) sg::edit_peq_classes(pat, m, peq); else sg::edit_peq_bytes(pat, m, peq);
+    const uint32_t words = m <= 32 ? 1u : 2u;
+    sg::edit_peq_table(peq, words, reinterpret_cast<uint32_t*>(d->pinned));
+    a->peq = reinterpret_cast<const uint32_t*>(d->arena);
+    return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+}
+
+void tedit_head(sg::TextEditArgs& a, const DeviceCtx* d, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
+{
+    a.text = text->data();
+    a.e_begin = off;
+    a.e_end = off + n;
+    a.m = m;
+    a.k = k;
+    a.count = d->batch_counts;
+}
+
+// One count of end positions, n + k >= m.  pre: the device's buffers, the masks and their staging; run: the slot's memset,
+// the kernel, the read-back.
+int tedit_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                uint64_t* count, double* pre_ms, double* run_ms)
+{
+    const int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
+    if (!sg::g_text_edit_scan) { set_error("%s: this program holds no text_edit_scan kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const double t_pre = now_ms();
+    sg::TextEditArgs a;
+    if (!batch_reserve(d, sizeof(uint32_t) * 256 * sg::kTEditWords, 1)) return SMARTGPU_ERR_NOMEM;
+    if (!tedit_stage(d, pat, classes, m, &a)) { set_error("%s: %s", call, hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
+    const double pre = now_ms() - t_pre;
+    const double t0 = now_ms();
+    tedit_head(a, d, text, m, k, off, n);
+    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(sg::g_text_edit_scan(a, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
+    const double run = now_ms() - t0;
+    // more occurrences than end positions: refused like a poisoned count, never reported
+    if (d->pinned_counts[0] > n) { set_error("text_edit_scan: count %llu exceeds the %llu end positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)n); return SMARTGPU_ERR_HIP; }
+    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
+}
+
+// One find of end positions: pedit_find's steps and return codes.
+int tedit_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+               uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
+    const int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    if (n + k < m) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    if (!sg::g_text_edit_find) { set_error("%s: this program holds no text_edit_find kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, sizeof(uint32_t) * 256 * sg::kTEditWords, 1)) return SMARTGPU_ERR_NOMEM;
+    sg::TextEditArgs a;
+    tedit_head(a, d, text, m, k, off, n);
+    const uint64_t room = cap < n ? cap : n;  // no more entries than end positions
+    bool own = false;
+    unsigned long long* out = nullptr;
+    uint64_t room_got = room;
+    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
+    const bool ok = tedit_stage(d, pat, classes, m, &a) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+                    sg::g_text_edit_find(a, out, room_got, d->num_cus, d->stream) == hipSuccess &&
+                    hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+                    hipStreamSynchronize(d->stream) == hipSuccess;
+    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
+    int r = SMARTGPU_OK;
+    if (!ok) {
+        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        r = SMARTGPU_ERR_HIP;
+    } else if (total > n) {  // refused like a poisoned count, never reported
+        set_error("text_edit_find: cursor %llu exceeds the %llu end positions", total, (unsigned long long)n);
+        r = SMARTGPU_ERR_HIP;
+    } else if (total && total <= room_got) {
+        if (!copy_positions(d, ends, out, total)) {
+            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+            r = SMARTGPU_ERR_HIP;
+        } else if (!sg::order_spans(ends, total, off, off + n - 1, sg::kMisShift)) {
+            set_error("text_edit_find: the entries are not ascending spans of %llu end positions", (unsigned long long)sg::kFindSpan);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (own) (void)hipFree(out);
+    if (r != SMARTGPU_OK) return r;
+    *count = total;
+    if (total <= cap && total > room_got) {
+        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu entries", call, total, (unsigned long long)cap, (unsigned long long)room);
+        return SMARTGPU_ERR_NOMEM;
+    }
+    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    unpack_mis(ends, distances, total);
+    return SMARTGPU_OK;
+}
+
 // ---- edit distance, long patterns (peditl.hpp): the contract of the calls above with m <= 256 and k <= 31, their own
 // kernels, and a switch that travels with the call ----
 
@@ -3414,6 +3540,31 @@ int smartgpu_pfind_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, cons
                                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     return pedit_find("pfind_sets_edit64", sets, true, m, k, text, off, n, ends, distances, cap, count);
+}
+
+/* ---- edit distance on byte texts: the same question of a smartgpu_text (tedit.hpp, k_tedit.hip) ------------------------- */
+int smartgpu_search_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                           uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return tedit_count("search_edit64", P, false, m, k, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_find_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                         uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return tedit_find("find_edit64", P, false, m, k, text, off, n, ends, distances, cap, count);
+}
+
+int smartgpu_search_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                                   uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return tedit_count("search_edit_classes64", classes, true, m, k, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_find_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                                 uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return tedit_find("find_edit_classes64", classes, true, m, k, text, off, n, ends, distances, cap, count);
 }
 
 /* ---- edit distance, long patterns: m <= 256, k <= 31 (peditl.hpp, k_peditl.hip) ---------------------------------------- */

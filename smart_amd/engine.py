@@ -179,6 +179,10 @@ def _load(path):
         "smartgpu_pfind_sets_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_search_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_find_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_search_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_find_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -849,6 +853,80 @@ def find(P, text, off=0, n=None, cap=1 << 20):
     if rc != 0:
         raise _err("find64 rc=%d" % rc)
     return out[:c.value].copy(), int(c.value)
+
+
+def _classes(classes):
+    """An (m, 32) uint8 array of 256-bit rows (byte_classes) as the calls take it, and m."""
+    classes = np.ascontiguousarray(classes, dtype=np.uint8)
+    if classes.ndim != 2 or classes.shape[1] != 32:
+        raise ValueError("classes: an (m, 32) uint8 array, one 256-bit row per pattern position, not shape %r" % (classes.shape,))
+    return classes, classes.shape[0]
+
+
+def byte_classes(P, ignore_case=False):
+    """The (len(P), 32) uint8 array search_edit_classes / find_edit_classes take, from a byte pattern: row j bit v (byte v // 8,
+    bit v % 8) set means position j accepts byte value v.  Every row holds the one bit of P[j]; with ignore_case a letter's
+    row holds both of its cases (ASCII folding only: A-Z and a-z, nothing beyond 127)."""
+    P = _u8(P)
+    rows = np.zeros((len(P), 32), dtype=np.uint8)
+    for j, v in enumerate(P.tolist()):
+        rows[j, v >> 3] |= 1 << (v & 7)
+        if ignore_case and (65 <= v <= 90 or 97 <= v <= 122):
+            w = v ^ 0x20
+            rows[j, w >> 3] |= 1 << (w & 7)
+    return rows
+
+
+def _tedit_count(name, pat, m, text, k, off, n):
+    if n is None:
+        n = len(text) - off
+    c = C.c_uint64(0)
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, text._h, off, n, C.byref(c), None, None)
+    if rc != 0:
+        raise _err("%s rc=%d" % (name, rc))
+    return int(c.value)
+
+
+def _tedit_find(name, pat, m, text, k, off, n, cap):
+    if n is None:
+        n = len(text) - off
+    ends = np.empty(max(cap, 1), dtype=np.uint64)
+    dist = np.empty(max(cap, 1), dtype=np.uint8)
+    c = C.c_uint64(0)
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, text._h, off, n, ends.ctypes.data if cap else None,
+                                            dist.ctypes.data if cap else None, cap, C.byref(c))
+    if rc != 0:  # (more than cap occurrences: SMARTGPU_ERR_NOMEM, the message holds the count a retry needs)
+        raise _err("%s rc=%d" % (name, rc))
+    return ends[:c.value].copy(), dist[:c.value].copy()
+
+
+def search_edit(P, text, k, off=0, n=None):
+    """The number of END positions e in bytes [off, off+n) of a Text where P occurs within edit distance k — substitutions,
+    insertions and deletions, 0 <= k <= 7, 1 <= len(P) <= 64 (smartgpu_search_edit64): some substring [s, e] of the range,
+    off <= s, is at most k edits from P.  The text may hold any byte values."""
+    P = _u8(P)
+    return _tedit_count("search_edit64", P, len(P), text, k, off, n)
+
+
+def find_edit(P, text, k, off=0, n=None, cap=1 << 20):
+    """(ends, distances) of P within edit distance k (search_edit) in bytes [off, off+n) of a Text: the ascending end
+    positions (uint64, the match's last byte, relative to text byte 0) and the edit distance of each (uint8).  More than
+    `cap` occurrences raise SmartGpuError; its text names their number (smartgpu_find_edit64)."""
+    P = _u8(P)
+    return _tedit_find("find_edit64", P, len(P), text, k, off, n, cap)
+
+
+def search_edit_classes(classes, text, k, off=0, n=None):
+    """search_edit for a pattern of byte CLASSES: an (m, 32) uint8 array whose row j says which byte values position j
+    accepts (byte_classes; smartgpu_search_edit_classes64).  An empty row accepts nothing, a full row everything."""
+    classes, m = _classes(classes)
+    return _tedit_count("search_edit_classes64", classes, m, text, k, off, n)
+
+
+def find_edit_classes(classes, text, k, off=0, n=None, cap=1 << 20):
+    """(ends, distances) of a pattern of byte classes (search_edit_classes), as find_edit returns them."""
+    classes, m = _classes(classes)
+    return _tedit_find("find_edit_classes64", classes, m, text, k, off, n, cap)
 
 
 def search_host(algo, P, T):
