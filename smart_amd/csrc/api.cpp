@@ -2438,17 +2438,23 @@ bool copy_positions(DeviceCtx* d, uint64_t* dst, const unsigned long long* src, 
     return true;
 }
 
-// ---- one host path for the count and the find calls on packed texts (set patterns, mismatches, both: planes.hpp) ----
-
-// The pattern's planes (`bytes` at `words`) through the staging buffer into the device's arena, for m > 32 only: the first
-// 32 positions travel as kernel arguments.
-bool stage_pattern(DeviceCtx* d, const uint32_t* words, size_t bytes, uint32_t m)
-{
-    if (m <= 32) return true;
-    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
-    std::memcpy(d->pinned, words, bytes);
-    return hipMemcpyAsync(d->arena, d->pinned, bytes, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
+// ---- ONE host path for every single-pattern count and find on a packed text and for the edit-distance calls on a byte
+// text: count_run and find_run.  The skeleton fixes the order of the steps — the device's context with nothing queued, the
+// arena (batch_reserve), for a find the entries' device buffer (find_reserve; none: the call still counts), the family's
+// staging, the slot's memset, the kernel, the read-back, the synchronisation —, the refusal of a count or cursor beyond
+// the bound, what *count receives, the find's outcomes (planes_host.hpp: find_outcome) with their return codes and texts,
+// and the times (pre: arena and staging; run: memset to synchronisation; counts only).  A family supplies its names
+// (RunNames), its bound — n - m + 1 start positions, or n end positions whatever m is —, the bytes it stages into the
+// arena, and two lambdas: `stage` (may do nothing; false is a HIP error) and `launch` (fills what its arguments need of the
+// device — the result slot is d->batch_counts — and launches).  A find adds a third, `order`: the entries in ascending
+// order, or set_error and false for what its kernel cannot have written.  So a family is: checks, masks, args, two
+// lambdas; what needs no launch it answers before it comes here. ----
+struct RunNames {
+    const char* call;     // the entry point: "<call>: ..." for what the caller can mend
+    const char* kernel;   // the kernel, for refusals of what the device wrote
+    const char* bound;    // what the bound counts: "start positions", "end positions"
+    const char* entries;  // what a find lists: "positions", "entries"
+};
 
 // What a count call answers: the times for smartgpu_last_times, the count and the times for the caller.
 int pcount_done(uint64_t c, double pre, double run, uint64_t* count, double* pre_ms, double* run_ms)
@@ -2461,87 +2467,137 @@ int pcount_done(uint64_t c, double pre, double run, uint64_t* count, double* pre
     return SMARTGPU_OK;
 }
 
-// One count on a packed text, n >= m: `a` holds the kind's own fields, `words` the pattern's planes.  pre: the device's
-// buffers and the staging; run: the slot's memset, the kernel, the read-back.
-template <typename Args>
-int pcount_run(const char* call, const char* kernel, hipError_t (*launch)(const Args&, int, int, hipStream_t), Args a, const smartgpu_ptext* text,
-               const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
+template <typename Stage, typename Launch>
+int count_run(const RunNames& w, int device, size_t arena_bytes, uint64_t bound, Stage stage, Launch launch, uint64_t* count, double* pre_ms,
+              double* run_ms)
 {
-    DeviceCtx* d = device_ctx_flushed(text->device);
+    DeviceCtx* d = device_ctx_flushed(device);
     if (!d) return SMARTGPU_ERR_HIP;
     const double t_pre = now_ms();
-    if (!batch_reserve(d, bytes, 1)) return SMARTGPU_ERR_NOMEM;
-    if (!stage_pattern(d, words, bytes, m)) { set_error("%s: %s", call, hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
+    if (!batch_reserve(d, arena_bytes, 1)) return SMARTGPU_ERR_NOMEM;
+    if (!stage(d)) { set_error("%s: %s", w.call, hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
     const double pre = now_ms() - t_pre;
     const double t0 = now_ms();
-    plane_head(a, d, text, m, off, n);
-    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(launch(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipMemsetAsync(d->batch_counts, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
+    HIP_TRY(launch(d), return SMARTGPU_ERR_HIP);
+    HIP_TRY(hipMemcpyAsync(d->pinned_counts, d->batch_counts, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
     HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
     const double run = now_ms() - t0;
-    // more occurrences than start positions: refused like a poisoned count, never reported
-    if (d->pinned_counts[0] > n - m + 1) { set_error("%s: count %llu exceeds the %llu start positions", kernel, (unsigned long long)d->pinned_counts[0], (unsigned long long)(n - m + 1)); return SMARTGPU_ERR_HIP; }
+    // more occurrences than positions: refused like a poisoned count, never reported
+    if (d->pinned_counts[0] > bound) { set_error("%s: count %llu exceeds the %llu %s", w.kernel, (unsigned long long)d->pinned_counts[0], (unsigned long long)bound, w.bound); return SMARTGPU_ERR_HIP; }
     return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
 }
 
-// One find on a packed text, n >= m, on a device whose arena has room for the pattern (batch_reserve): the positions'
-// device buffer, the pattern's staging, the cursor's memset and the kernel — `a` holds the kind's own fields —, the
-// cursor's read-back, the positions to the host in ascending order.
-// *count always receives the number of occurrences when the device answered; the return codes are smartgpu_pfind64's.
-// shift: order_spans' (the entries reach `positions` as the kernel wrote them).
-template <typename Args>
-int pfind_run(DeviceCtx* d, const char* call, const char* kernel,
-              hipError_t (*launch)(const Args&, unsigned long long*, unsigned long long, int, int, hipStream_t), Args a, const smartgpu_ptext* text,
-              const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* positions, uint64_t cap, uint64_t* count,
-              uint32_t shift = 0)
+// *count receives the number of occurrences whenever the device answered with a cursor within the bound, on
+// SMARTGPU_ERR_NOMEM too; `entries` receives the list, in order, on SMARTGPU_OK only, and nothing behind entries[cap] is
+// touched.  The entries reach `order` as the kernel wrote them; unpacking distances is the caller's.
+template <typename Stage, typename Launch, typename Order>
+int find_run(const RunNames& w, int device, size_t arena_bytes, uint64_t bound, Stage stage, Launch launch, Order order, uint64_t* entries,
+             uint64_t cap, uint64_t* count)
 {
-    plane_head(a, d, text, m, off, n);
-    const uint64_t starts = n - m + 1;
-    const uint64_t room = cap < starts ? cap : starts;  // no more positions than start positions
+    DeviceCtx* d = device_ctx_flushed(device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, arena_bytes, 1)) return SMARTGPU_ERR_NOMEM;
+    const uint64_t room = cap < bound ? cap : bound;  // no more entries than positions
     bool own = false;
     unsigned long long* out = nullptr;
     uint64_t room_got = room;
     if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
-    bool ok = stage_pattern(d, words, bytes, m) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-              launch(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
-              hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
-              hipStreamSynchronize(d->stream) == hipSuccess;
+    const bool ok = stage(d) && hipMemsetAsync(d->batch_counts, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+                    launch(d, out, room_got) == hipSuccess &&
+                    hipMemcpyAsync(d->pinned_counts, d->batch_counts, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
+                    hipStreamSynchronize(d->stream) == hipSuccess;
     const unsigned long long total = ok ? d->pinned_counts[0] : 0;
     int r = SMARTGPU_OK;
     if (!ok) {
-        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        set_error("%s: %s", w.call, hipGetErrorString(hipGetLastError()));
         r = SMARTGPU_ERR_HIP;
-    } else if (total > starts) {  // refused like a poisoned count, never reported
-        set_error("%s: cursor %llu exceeds the %llu start positions", kernel, total, (unsigned long long)starts);
+    } else switch (sg::find_outcome(total, bound, room_got, cap)) {
+    case sg::FindOutcome::kBeyondBound:
+        set_error("%s: cursor %llu exceeds the %llu %s", w.kernel, total, (unsigned long long)bound, w.bound);
         r = SMARTGPU_ERR_HIP;
-    } else if (total && total <= room_got) {
-        if (!copy_positions(d, positions, out, total)) {
-            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        break;
+    case sg::FindOutcome::kComplete:
+        if (total && !copy_positions(d, entries, out, total)) {
+            set_error("%s: %s", w.call, hipGetErrorString(hipGetLastError()));
             r = SMARTGPU_ERR_HIP;
-        } else if (!sg::order_spans(positions, total, off, off + n - m, shift)) {
-            set_error("%s: the positions are not ascending spans of %llu start positions", kernel, (unsigned long long)sg::kFindSpan);
+        } else if (total && !order(entries, total)) {
             r = SMARTGPU_ERR_HIP;
         }
+        break;
+    case sg::FindOutcome::kOverCap:
+        set_error("%s: %llu occurrences, room for %llu", w.call, total, (unsigned long long)cap);
+        r = SMARTGPU_ERR_NOMEM;
+        break;
+    case sg::FindOutcome::kNoRoom:
+        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu %s", w.call, total, (unsigned long long)cap, (unsigned long long)room, w.entries);
+        r = SMARTGPU_ERR_NOMEM;
+        break;
     }
     if (own) (void)hipFree(out);
-    if (r != SMARTGPU_OK) return r;
+    if (r != SMARTGPU_ERR_HIP) *count = total;
+    return r;
+}
+
+// find_run's `order` for the kernels that write spans (planes.hpp): order_spans over the positions [lo, hi]
+bool spans_in_order(const RunNames& w, uint64_t* entries, uint64_t total, uint64_t lo, uint64_t hi, uint32_t shift)
+{
+    if (sg::order_spans(entries, total, lo, hi, shift)) return true;
+    set_error("%s: the %s are not ascending spans of %llu %s", w.kernel, w.entries, (unsigned long long)sg::kFindSpan, w.bound);
+    return false;
+}
+
+// A find whose every start position is an occurrence (full sets): no launch
+int find_every_start(const char* call, uint64_t off, uint64_t total, uint64_t* positions, uint64_t cap, uint64_t* count)
+{
     *count = total;
-    if (total <= cap && total > room_got) {
-        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu positions", call, total, (unsigned long long)cap, (unsigned long long)room);
-        return SMARTGPU_ERR_NOMEM;
-    }
-    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+    for (uint64_t i = 0; i < total; ++i) positions[i] = off + i;
     return SMARTGPU_OK;
 }
 
-// The entries of a find with mismatches, position << kMisShift | distance in ascending order, unpacked in place.
-void unpack_mis(uint64_t* positions, uint8_t* mismatches, uint64_t count)
+// The pattern's planes (`bytes` at `words`) through the staging buffer into the device's arena, for m > 32 only: the first
+// 32 positions travel as kernel arguments.
+bool stage_pattern(DeviceCtx* d, const uint32_t* words, size_t bytes, uint32_t m)
+{
+    if (m <= 32) return true;
+    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
+    std::memcpy(d->pinned, words, bytes);
+    return hipMemcpyAsync(d->arena, d->pinned, bytes, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+}
+
+// count_run / find_run for the kernels of planes.hpp and planes3.hpp, n >= m: start positions, the pattern's planes at
+// `words` staged when m > 32, `a` holds the kind's own fields.  shift: order_spans'.
+template <typename Args>
+int pcount_run(const char* call, const char* kernel, hipError_t (*launch)(const Args&, int, int, hipStream_t), Args a, const smartgpu_ptext* text,
+               const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return count_run({call, kernel, "start positions", "positions"}, text->device, bytes, n - m + 1,
+                     [&](DeviceCtx* d) { return stage_pattern(d, words, bytes, m); },
+                     [&](DeviceCtx* d) { plane_head(a, d, text, m, off, n); return launch(a, text->planes, d->num_cus, d->stream); },
+                     count, pre_ms, run_ms);
+}
+
+template <typename Args>
+int pfind_run(const char* call, const char* kernel, hipError_t (*launch)(const Args&, unsigned long long*, unsigned long long, int, int, hipStream_t),
+              Args a, const smartgpu_ptext* text, const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* positions,
+              uint64_t cap, uint64_t* count, uint32_t shift = 0)
+{
+    const RunNames w = {call, kernel, "start positions", "positions"};
+    return find_run(w, text->device, bytes, n - m + 1,
+                    [&](DeviceCtx* d) { return stage_pattern(d, words, bytes, m); },
+                    [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { plane_head(a, d, text, m, off, n); return launch(a, out, room, text->planes, d->num_cus, d->stream); },
+                    [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - m, shift); },
+                    positions, cap, count);
+}
+
+// The entries of a find with distances, position << shift | distance in ascending order, unpacked in place.
+void unpack_mis(uint64_t* positions, uint8_t* mismatches, uint64_t count, uint32_t shift = sg::kMisShift)
 {
     for (uint64_t i = 0; i < count; ++i) {
         const uint64_t e = positions[i];
-        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << sg::kMisShift) - 1u));
-        positions[i] = e >> sg::kMisShift;
+        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << shift) - 1u));
+        positions[i] = e >> shift;
     }
 }
 
@@ -2641,19 +2697,10 @@ int p3_find(const char* call, const uint8_t* pat, bool sets, bool mis, uint32_t 
         *count = 0;
         return SMARTGPU_OK;
     }
-    if (full && !mis) {  // every start position of the range: no launch
-        const uint64_t total = n - m + 1;
-        *count = total;
-        if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-        for (uint64_t i = 0; i < total; ++i) positions[i] = off + i;
-        return SMARTGPU_OK;
-    }
+    if (full && !mis) return find_every_start(call, off, n - m + 1, positions, cap, count);
     if (!planes3_linked(call)) return SMARTGPU_ERR_HIP;
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, sizeof Y, 1)) return SMARTGPU_ERR_NOMEM;
     a.shift = mis ? sg::kMisShift : 0u;
-    const int r = pfind_run(d, call, "planes3_find", sg::g_planes3_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count, a.shift);
+    const int r = pfind_run(call, "planes3_find", sg::g_planes3_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count, a.shift);
     if (mis && r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
     return r;
 }
@@ -2666,16 +2713,19 @@ int refuse_planes3(const char* call, const smartgpu_ptext* text)
     return SMARTGPU_ERR_ARG;
 }
 
-// ---- edit distance (pedit.hpp): END positions, n of them whatever m is, and m > n is legal — its own run path, so that
-// no bound of pcount_run / pfind_run (n - m + 1 start positions) changes ----
+// The edit-distance families below count and list END positions, n of them whatever m is, and m > n is legal; their
+// entries are end << shift | distance.  None of them stages planes: `stage` does nothing, or (byte texts) sends the masks.
+constexpr auto no_stage = [](DeviceCtx*) { return true; };
 
-// The checks of the four edit calls that need no device; `what` names the pattern argument.
-int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off,
-                     uint64_t n, const uint64_t* count)
+// The checks of the edit, editl and align calls that need no device; `what` names the pattern argument, max_m and max_k are
+// the family's, flags is 0 for a call that takes none.
+int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t max_m, uint32_t k, uint32_t max_k, uint32_t flags,
+                     const smartgpu_ptext* text, uint64_t off, uint64_t n, const uint64_t* count)
 {
     if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > SMARTGPU_PEDIT_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_PEDIT_MAXM); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
+    if (m < 1 || m > max_m) { set_error("%s: pattern length %u outside [1,%u]", call, m, max_m); return SMARTGPU_ERR_ARG; }
+    if (k > max_k) { set_error("%s: k = %u edits, at most %u", call, k, max_k); return SMARTGPU_ERR_ARG; }
+    if (flags & ~SMARTGPU_PEDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_PEDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_PEDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
     if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
     if (refuse_planes3(call, text) != SMARTGPU_OK) return SMARTGPU_ERR_ARG;
     if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
@@ -2683,8 +2733,20 @@ int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint3
     return SMARTGPU_OK;
 }
 
-// The pattern's masks for a checked call: from bytes (sets == false) or from sets.  SMARTGPU_ERR_ARG: a set names a code the
-// text does not hold.
+// The fields that PlaneEditArgs, PlaneEditlArgs and PlaneAlignArgs share
+template <typename Args>
+void edit_head(Args& a, const smartgpu_ptext* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
+{
+    a.p0 = text->plane(0);
+    a.p1 = text->plane(text->planes - 1);
+    a.e_begin = off;
+    a.e_end = off + n;
+    a.m = m;
+    a.k = k;
+}
+
+// Edit distance, m <= 64 and k <= 7 (pedit.hpp).  The pattern's masks for a checked call, kernel arguments: from bytes
+// (sets == false) or from sets.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
 int edit_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, sg::PlaneEditArgs* a)
 {
     if (!sets) {
@@ -2697,50 +2759,26 @@ int edit_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool set
     return SMARTGPU_ERR_ARG;
 }
 
-void edit_head(sg::PlaneEditArgs& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
-{
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
-    a.count = d->batch_counts;
-}
-
-// One count of end positions, n + k >= m: the times are pcount_run's (no pattern is staged: the masks are kernel arguments).
 int pedit_count(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                 uint64_t* count, double* pre_ms, double* run_ms)
 {
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, k, text, off, n, count);
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     sg::PlaneEditArgs a;
     if ((rc = edit_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
     if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
     if (!sg::g_planes_edit_scan) { set_error("%s: this program holds no planes_edit_scan kernel (k_pedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    const double t_pre = now_ms();
-    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
-    const double pre = now_ms() - t_pre;
-    const double t0 = now_ms();
-    edit_head(a, d, text, m, k, off, n);
-    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(sg::g_planes_edit_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-    const double run = now_ms() - t0;
-    // more occurrences than end positions: refused like a poisoned count, never reported
-    if (d->pinned_counts[0] > n) { set_error("planes_edit_scan: count %llu exceeds the %llu end positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)n); return SMARTGPU_ERR_HIP; }
-    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
+    edit_head(a, text, m, k, off, n);
+    return count_run({call, "planes_edit_scan", "end positions", "entries"}, text->device, 0, n, no_stage,
+                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_planes_edit_scan(a, text->planes, d->num_cus, d->stream); },
+                     count, pre_ms, run_ms);
 }
 
-// One find of end positions: pfind_run's steps and return codes with n end positions in place of n - m + 1 start positions.
 int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, k, text, off, n, count);
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     sg::PlaneEditArgs a;
     if ((rc = edit_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
@@ -2749,53 +2787,18 @@ int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
         return SMARTGPU_OK;
     }
     if (!sg::g_planes_edit_find) { set_error("%s: this program holds no planes_edit_find kernel (k_pedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
-    edit_head(a, d, text, m, k, off, n);
-    const uint64_t room = cap < n ? cap : n;  // no more entries than end positions
-    bool own = false;
-    unsigned long long* out = nullptr;
-    uint64_t room_got = room;
-    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
-    const bool ok = hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-                    sg::g_planes_edit_find(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
-                    hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
-                    hipStreamSynchronize(d->stream) == hipSuccess;
-    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
-    int r = SMARTGPU_OK;
-    if (!ok) {
-        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-        r = SMARTGPU_ERR_HIP;
-    } else if (total > n) {  // refused like a poisoned count, never reported
-        set_error("planes_edit_find: cursor %llu exceeds the %llu end positions", total, (unsigned long long)n);
-        r = SMARTGPU_ERR_HIP;
-    } else if (total && total <= room_got) {
-        if (!copy_positions(d, ends, out, total)) {
-            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-            r = SMARTGPU_ERR_HIP;
-        } else if (!sg::order_spans(ends, total, off, off + n - 1, sg::kMisShift)) {
-            set_error("planes_edit_find: the entries are not ascending spans of %llu end positions", (unsigned long long)sg::kFindSpan);
-            r = SMARTGPU_ERR_HIP;
-        }
-    }
-    if (own) (void)hipFree(out);
-    if (r != SMARTGPU_OK) return r;
-    *count = total;
-    if (total <= cap && total > room_got) {
-        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu entries", call, total, (unsigned long long)cap, (unsigned long long)room);
-        return SMARTGPU_ERR_NOMEM;
-    }
-    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-    unpack_mis(ends, distances, total);
-    return SMARTGPU_OK;
+    edit_head(a, text, m, k, off, n);
+    const RunNames w = {call, "planes_edit_find", "end positions", "entries"};
+    rc = find_run(w, text->device, 0, n, no_stage,
+                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_planes_edit_find(a, out, room, text->planes, d->num_cus, d->stream); },
+                  [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
+                  ends, cap, count);
+    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count);
+    return rc;
 }
 
-// ---- edit distance on BYTE texts (tedit.hpp): the contract of the calls above with a smartgpu_text in place of the planes;
-// the pattern is 256 masks (tedit_host.hpp), too many for kernel arguments: they travel through the staging buffer to the
-// arena, as psearch_impl's patterns do ----
-
-// The checks of the four calls that need no device; `what` names the pattern argument.
+// Edit distance on BYTE texts (tedit.hpp): the contract of the calls above with a smartgpu_text in place of the planes.
+// The checks of its four calls that need no device; `what` names the pattern argument.
 int check_tedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off,
                      uint64_t n, const uint64_t* count)
 {
@@ -2808,8 +2811,10 @@ int check_tedit_args(const char* call, const char* what, const uint8_t* P, uint3
     return SMARTGPU_OK;
 }
 
-// The pattern's masks (bytes, or classes) as the kernel's table in the staging buffer, on their way to the arena
-// (batch_reserve has made room).  The staging buffer is free: every call that fills it ends with a synchronisation.
+// The pattern is 256 masks (tedit_host.hpp), too many for kernel arguments: bytes or classes as the kernel's table in the
+// staging buffer, on their way to the arena (kTEditArena bytes of it), as psearch_impl's patterns travel.  The staging
+// buffer is free: every call that fills it ends with a synchronisation.
+constexpr size_t kTEditArena = sizeof(uint32_t) * 256 * sg::kTEditWords;
 bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, sg::TextEditArgs* a)
 {
     uint32_t peq[256][sg::kTEditWords];
@@ -2820,18 +2825,15 @@ bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, sg:
     return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
 }
 
-void tedit_head(sg::TextEditArgs& a, const DeviceCtx* d, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
+void tedit_head(sg::TextEditArgs& a, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
 {
     a.text = text->data();
     a.e_begin = off;
     a.e_end = off + n;
     a.m = m;
     a.k = k;
-    a.count = d->batch_counts;
 }
 
-// One count of end positions, n + k >= m.  pre: the device's buffers, the masks and their staging; run: the slot's memset,
-// the kernel, the read-back.
 int tedit_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
                 uint64_t* count, double* pre_ms, double* run_ms)
 {
@@ -2839,99 +2841,39 @@ int tedit_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, 
     if (rc != SMARTGPU_OK) return rc;
     if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
     if (!sg::g_text_edit_scan) { set_error("%s: this program holds no text_edit_scan kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    const double t_pre = now_ms();
     sg::TextEditArgs a;
-    if (!batch_reserve(d, sizeof(uint32_t) * 256 * sg::kTEditWords, 1)) return SMARTGPU_ERR_NOMEM;
-    if (!tedit_stage(d, pat, classes, m, &a)) { set_error("%s: %s", call, hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
-    const double pre = now_ms() - t_pre;
-    const double t0 = now_ms();
-    tedit_head(a, d, text, m, k, off, n);
-    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(sg::g_text_edit_scan(a, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-    const double run = now_ms() - t0;
-    // more occurrences than end positions: refused like a poisoned count, never reported
-    if (d->pinned_counts[0] > n) { set_error("text_edit_scan: count %llu exceeds the %llu end positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)n); return SMARTGPU_ERR_HIP; }
-    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
+    tedit_head(a, text, m, k, off, n);
+    return count_run({call, "text_edit_scan", "end positions", "entries"}, text->device, kTEditArena, n,
+                     [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a); },
+                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_edit_scan(a, d->num_cus, d->stream); },
+                     count, pre_ms, run_ms);
 }
 
-// One find of end positions: pedit_find's steps and return codes.
 int tedit_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    const int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     if (n + k < m) {
         *count = 0;
         return SMARTGPU_OK;
     }
     if (!sg::g_text_edit_find) { set_error("%s: this program holds no text_edit_find kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, sizeof(uint32_t) * 256 * sg::kTEditWords, 1)) return SMARTGPU_ERR_NOMEM;
     sg::TextEditArgs a;
-    tedit_head(a, d, text, m, k, off, n);
-    const uint64_t room = cap < n ? cap : n;  // no more entries than end positions
-    bool own = false;
-    unsigned long long* out = nullptr;
-    uint64_t room_got = room;
-    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
-    const bool ok = tedit_stage(d, pat, classes, m, &a) && hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-                    sg::g_text_edit_find(a, out, room_got, d->num_cus, d->stream) == hipSuccess &&
-                    hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
-                    hipStreamSynchronize(d->stream) == hipSuccess;
-    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
-    int r = SMARTGPU_OK;
-    if (!ok) {
-        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-        r = SMARTGPU_ERR_HIP;
-    } else if (total > n) {  // refused like a poisoned count, never reported
-        set_error("text_edit_find: cursor %llu exceeds the %llu end positions", total, (unsigned long long)n);
-        r = SMARTGPU_ERR_HIP;
-    } else if (total && total <= room_got) {
-        if (!copy_positions(d, ends, out, total)) {
-            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-            r = SMARTGPU_ERR_HIP;
-        } else if (!sg::order_spans(ends, total, off, off + n - 1, sg::kMisShift)) {
-            set_error("text_edit_find: the entries are not ascending spans of %llu end positions", (unsigned long long)sg::kFindSpan);
-            r = SMARTGPU_ERR_HIP;
-        }
-    }
-    if (own) (void)hipFree(out);
-    if (r != SMARTGPU_OK) return r;
-    *count = total;
-    if (total <= cap && total > room_got) {
-        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu entries", call, total, (unsigned long long)cap, (unsigned long long)room);
-        return SMARTGPU_ERR_NOMEM;
-    }
-    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-    unpack_mis(ends, distances, total);
-    return SMARTGPU_OK;
+    tedit_head(a, text, m, k, off, n);
+    const RunNames w = {call, "text_edit_find", "end positions", "entries"};
+    rc = find_run(w, text->device, kTEditArena, n,
+                  [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a); },
+                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_edit_find(a, out, room, d->num_cus, d->stream); },
+                  [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
+                  ends, cap, count);
+    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count);
+    return rc;
 }
 
-// ---- edit distance, long patterns (peditl.hpp): the contract of the calls above with m <= 256 and k <= 31, their own
-// kernels, and a switch that travels with the call ----
-
-// The checks of the four editl calls that need no device; `what` names the pattern argument.
-int check_peditl_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text,
-                      uint64_t off, uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > SMARTGPU_PEDITL_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_PEDITL_MAXM); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_PEDITL_MAXK) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PEDITL_MAXK); return SMARTGPU_ERR_ARG; }
-    if (flags & ~SMARTGPU_PEDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_PEDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_PEDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
-    if (refuse_planes3(call, text) != SMARTGPU_OK) return SMARTGPU_ERR_ARG;
-    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// edit_masks, eight dwords wide
+// Edit distance, long patterns (peditl.hpp): m <= 256 and k <= 31, a switch that travels with the call, and entries that
+// the kernel writes in no order (order_editl sorts them).  edit_masks, eight dwords wide:
 int editl_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, sg::PlaneEditlArgs* a)
 {
     if (!sets) {
@@ -2944,63 +2886,27 @@ int editl_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool se
     return SMARTGPU_ERR_ARG;
 }
 
-void editl_head(sg::PlaneEditlArgs& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint32_t k, uint32_t flags, uint64_t off, uint64_t n)
-{
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
-    a.all_blocks = flags & SMARTGPU_PEDITL_ALL_BLOCKS;
-    a.count = d->batch_counts;
-}
-
-// pedit_count with the long kernels
 int peditl_count(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off,
                  uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
 {
-    int rc = check_peditl_args(call, sets ? "sets" : "P", pat, m, k, flags, text, off, n, count);
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDITL_MAXM, k, SMARTGPU_PEDITL_MAXK, flags, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     sg::PlaneEditlArgs a;
     if ((rc = editl_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
     if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
     if (!sg::g_planes_editl_scan) { set_error("%s: this program holds no planes_editl_scan kernel (k_peditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    const double t_pre = now_ms();
-    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
-    const double pre = now_ms() - t_pre;
-    const double t0 = now_ms();
-    editl_head(a, d, text, m, k, flags, off, n);
-    HIP_TRY(hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(sg::g_planes_editl_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-    const double run = now_ms() - t0;
-    if (d->pinned_counts[0] > n) { set_error("planes_editl_scan: count %llu exceeds the %llu end positions", (unsigned long long)d->pinned_counts[0], (unsigned long long)n); return SMARTGPU_ERR_HIP; }
-    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
+    edit_head(a, text, m, k, off, n);
+    a.all_blocks = flags & SMARTGPU_PEDITL_ALL_BLOCKS;
+    return count_run({call, "planes_editl_scan", "end positions", "entries"}, text->device, 0, n, no_stage,
+                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_planes_editl_scan(a, text->planes, d->num_cus, d->stream); },
+                     count, pre_ms, run_ms);
 }
 
-// The entries of planes_editl_find, (e << kEditlShift) | D(e) in the order the waves' pieces reached the cursor: sorted,
-// then refused unless they are distinct end positions of [lo, hi] with distances <= k.
-bool order_editl(uint64_t* entries, uint64_t count, uint64_t lo, uint64_t hi, uint32_t k)
-{
-    std::sort(entries, entries + count);
-    for (uint64_t i = 0; i < count; ++i) {
-        const uint64_t e = entries[i] >> sg::kEditlShift;
-        if (e < lo || e > hi || (entries[i] & ((1u << sg::kEditlShift) - 1u)) > k) return false;
-        if (i && e == entries[i - 1] >> sg::kEditlShift) return false;
-    }
-    return true;
-}
-
-// pedit_find with the long kernels; the entries are ordered by a sort (order_editl)
 int peditl_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off,
                 uint64_t n, uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_peditl_args(call, sets ? "sets" : "P", pat, m, k, flags, text, off, n, count);
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDITL_MAXM, k, SMARTGPU_PEDITL_MAXK, flags, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     sg::PlaneEditlArgs a;
     if ((rc = editl_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
@@ -3009,50 +2915,18 @@ int peditl_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uin
         return SMARTGPU_OK;
     }
     if (!sg::g_planes_editl_find) { set_error("%s: this program holds no planes_editl_find kernel (k_peditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
-    editl_head(a, d, text, m, k, flags, off, n);
-    const uint64_t room = cap < n ? cap : n;  // no more entries than end positions
-    bool own = false;
-    unsigned long long* out = nullptr;
-    uint64_t room_got = room;
-    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
-    const bool ok = hipMemsetAsync(a.count, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-                    sg::g_planes_editl_find(a, out, room_got, text->planes, d->num_cus, d->stream) == hipSuccess &&
-                    hipMemcpyAsync(d->pinned_counts, a.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
-                    hipStreamSynchronize(d->stream) == hipSuccess;
-    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
-    int r = SMARTGPU_OK;
-    if (!ok) {
-        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-        r = SMARTGPU_ERR_HIP;
-    } else if (total > n) {  // refused like a poisoned count, never reported
-        set_error("planes_editl_find: cursor %llu exceeds the %llu end positions", total, (unsigned long long)n);
-        r = SMARTGPU_ERR_HIP;
-    } else if (total && total <= room_got) {
-        if (!copy_positions(d, ends, out, total)) {
-            set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-            r = SMARTGPU_ERR_HIP;
-        } else if (!order_editl(ends, total, off, off + n - 1, k)) {
-            set_error("planes_editl_find: the entries are not distinct end positions of the range with distances <= %u", k);
-            r = SMARTGPU_ERR_HIP;
-        }
-    }
-    if (own) (void)hipFree(out);
-    if (r != SMARTGPU_OK) return r;
-    *count = total;
-    if (total <= cap && total > room_got) {
-        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu entries", call, total, (unsigned long long)cap, (unsigned long long)room);
-        return SMARTGPU_ERR_NOMEM;
-    }
-    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-    for (uint64_t i = 0; i < total; ++i) {
-        const uint64_t e = ends[i];
-        if (distances) distances[i] = static_cast<uint8_t>(e & ((1u << sg::kEditlShift) - 1u));
-        ends[i] = e >> sg::kEditlShift;
-    }
-    return SMARTGPU_OK;
+    edit_head(a, text, m, k, off, n);
+    a.all_blocks = flags & SMARTGPU_PEDITL_ALL_BLOCKS;
+    rc = find_run({call, "planes_editl_find", "end positions", "entries"}, text->device, 0, n, no_stage,
+                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_planes_editl_find(a, out, room, text->planes, d->num_cus, d->stream); },
+                  [&](uint64_t* e, uint64_t total) {
+                      if (sg::order_editl(e, total, off, off + n - 1, k, sg::kEditlShift)) return true;
+                      set_error("planes_editl_find: the entries are not distinct end positions of the range with distances <= %u", k);
+                      return false;
+                  },
+                  ends, cap, count);
+    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count, sg::kEditlShift);
+    return rc;
 }
 
 // ---- starts and alignments of edit-distance occurrences (palign.hpp): a list of END positions in, one lane each ----
@@ -3079,7 +2953,7 @@ int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
 {
     if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
     if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, k, text, off, n, &count);
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, &count);
     if (rc != SMARTGPU_OK) return rc;
     sg::PlaneEditArgs masks;
     if ((rc = edit_masks(text, pat, m, sets, &masks)) != SMARTGPU_OK) return rc;  // (the pattern as given: the message names ITS position)
@@ -3096,12 +2970,7 @@ int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
     DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     sg::PlaneAlignArgs a;
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
+    edit_head(a, text, m, k, off, n);
     std::memcpy(a.peq, masks.peq, sizeof a.peq);
     const uint64_t piece = ops ? kFindKeep / 4 : kFindKeep;
     for (uint64_t done = 0; done < count;) {
@@ -3317,10 +3186,7 @@ int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, u
     if (rc != SMARTGPU_OK) return rc;
     if (!count || (cap && !positions)) { set_error("pfind64: count must not be NULL, positions only with cap = 0"); return SMARTGPU_ERR_ARG; }
     if (text->planes == 3) return p3_find("pfind64", P, false, false, m, 0, text, off, n, positions, nullptr, cap, count);
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
     uint32_t X[2 * sg::kPatWords];
-    if (!batch_reserve(d, sizeof X, 1)) return SMARTGPU_ERR_NOMEM;
     if (sg::encode_pattern(text->values, text->nvalues, P, m, X, X + sg::kPatWords, nullptr) || m > n) {
         *count = 0;  // a byte the text does not hold, or no window fits: no launch
         return SMARTGPU_OK;
@@ -3328,7 +3194,7 @@ int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, u
     sg::PlaneArgs a;
     a.x0 = X[0];
     a.x1 = X[sg::kPatWords];
-    return pfind_run(d, "pfind64", "planes_find", sg::launch_planes_find, a, text, X, sizeof X, m, off, n, positions, cap, count);
+    return pfind_run("pfind64","planes_find", sg::launch_planes_find, a, text, X, sizeof X, m, off, n, positions, cap, count);
 }
 
 int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
@@ -3418,19 +3284,10 @@ int smartgpu_pfind_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext*
         *count = 0;
         return SMARTGPU_OK;
     }
-    if (full) {  // every start position of the range: no launch
-        const uint64_t total = n - m + 1;
-        *count = total;
-        if (total > cap) { set_error("pfind_sets64: %llu occurrences, room for %llu", (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-        for (uint64_t i = 0; i < total; ++i) positions[i] = off + i;
-        return SMARTGPU_OK;
-    }
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, sizeof Y, 1)) return SMARTGPU_ERR_NOMEM;
+    if (full) return find_every_start("pfind_sets64", off, n - m + 1, positions, cap, count);
     sg::PlaneSetArgs a;
     set_words(a, Y);
-    return pfind_run(d, "pfind_sets64", "planes_sets_find", sg::launch_planes_sets_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count);
+    return pfind_run("pfind_sets64", "planes_sets_find", sg::launch_planes_sets_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count);
 }
 
 /* ---- mismatches: occurrences within Hamming distance k ---------------------------------------------------------------- */
@@ -3464,10 +3321,7 @@ int smartgpu_pfind_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgp
         return SMARTGPU_OK;
     }
     a.budget = k - a.foreign;
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, sizeof X, 1)) return SMARTGPU_ERR_NOMEM;
-    const int r = pfind_run(d, "pfind_mis64", "planes_mis_find", sg::launch_planes_mis_find, a, text, X, sizeof X, m, off, n, positions, cap, count,
+    const int r = pfind_run("pfind_mis64", "planes_mis_find", sg::launch_planes_mis_find, a, text, X, sizeof X, m, off, n, positions, cap, count,
                             sg::kMisShift);
     if (r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
     return r;
@@ -3508,10 +3362,7 @@ int smartgpu_pfind_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const
     }
     a.budget = k - a.foreign;
     set_words(a, Y);
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, sizeof Y, 1)) return SMARTGPU_ERR_NOMEM;
-    const int r = pfind_run(d, "pfind_sets_mis64", "planes_sets_mis_find", sg::launch_planes_sets_mis_find, a, text, Y, sizeof Y, m, off, n, positions,
+    const int r = pfind_run("pfind_sets_mis64", "planes_sets_mis_find", sg::launch_planes_sets_mis_find, a, text, Y, sizeof Y, m, off, n, positions,
                             cap, count, sg::kMisShift);
     if (r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
     return r;

@@ -1,6 +1,6 @@
 // planes_host.hpp — what the packed-text calls of api.cpp decide on the host before (the pattern as planes) and after
-// (the find's spans in order) a launch.  Host only: no HIP call, no error text — tests/packed_host_check.cpp runs it all
-// without a device.  The planes' layout is planes.hpp's.
+// (what a find's cursor means, the find's entries in order) a launch.  Host only: no HIP call, no error text —
+// tests/packed_host_check.cpp runs it all without a device.  The planes' layout is planes.hpp's.
 #pragma once
 #include "planes.hpp"
 
@@ -114,6 +114,36 @@ inline bool order_spans(uint64_t* pos, uint64_t have, uint64_t s_begin, uint64_t
     }
     std::memcpy(pos, tmp.data(), have * sizeof(uint64_t));
     return true;
+}
+
+// The entries of a find whose kernel keeps no order at all (planes_editl_find), (e << shift) | D(e) as the waves' pieces
+// reached the cursor: sorted, then refused (false) unless they are distinct end positions of [lo, hi] with distances <= k.
+inline bool order_editl(uint64_t* entries, uint64_t count, uint64_t lo, uint64_t hi, uint32_t k, uint32_t shift)
+{
+    std::sort(entries, entries + count);
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint64_t e = entries[i] >> shift;
+        if (e < lo || e > hi || (entries[i] & ((1u << shift) - 1u)) > k) return false;
+        if (i && e == entries[i - 1] >> shift) return false;
+    }
+    return true;
+}
+
+// What the cursor of a find means once the device has answered.  total: the cursor, every occurrence counted whether it
+// was stored or not; bound: the positions an occurrence can have; cap: the caller's room; room_got: the device buffer the
+// kernel stored into, min(cap, bound) entries, or 0 when the device had no memory for them (the call still counts).
+enum class FindOutcome {
+    kBeyondBound,  // total > bound: a poisoned cursor, refused and never reported
+    kComplete,     // every occurrence is in the device buffer: copy the list and order it (nothing to copy at total = 0)
+    kOverCap,      // more occurrences than the caller has room for: the count alone
+    kNoRoom,       // the caller's room would do, the device had none: the count alone
+};
+inline FindOutcome find_outcome(uint64_t total, uint64_t bound, uint64_t room_got, uint64_t cap)
+{
+    if (total > bound) return FindOutcome::kBeyondBound;
+    if (total > cap) return FindOutcome::kOverCap;
+    if (total > room_got) return FindOutcome::kNoRoom;
+    return FindOutcome::kComplete;
 }
 
 }  // namespace sg

@@ -1,6 +1,6 @@
 // packed_host_check.cpp — what the packed-text calls decide on the host (smart_amd/csrc/planes_host.hpp), without a device:
 // every bit of the planes encode_pattern and encode_sets write against the definition in planes.hpp, their counts and
-// flags, and order_spans on both of its paths.  Built and run by tests/test_packed_host.py under AddressSanitizer and UBSan;
+// flags, order_spans on both of its paths, order_editl, and find_outcome over a small exhaustive grid.  Built and run by tests/test_packed_host.py under AddressSanitizer and UBSan;
 // every buffer is a heap block of exactly the documented size.
 #include <algorithm>
 #include <cstdint>
@@ -202,11 +202,89 @@ static void span_cases()
             }
 }
 
+// find_outcome: what a cursor means, over bound x cap x room_got x total.  The expected letters are written out by hand from
+// the four cases (B: cursor beyond the bound; C: list complete; O: more than cap; N: fits cap, the device had no room), one
+// letter per total = 0 .. bound + 1; the rows stand in the order the grid produces them, duplicates included.
+struct OutcomeRow { uint64_t bound, cap, room_got; const char* want; };
+static const OutcomeRow kOutcomes[] = {
+    // bound 1: cap 0, 1, bound - 1, bound, bound + 1; room_got 0, min(cap, bound)
+    {1, 0, 0, "COB"}, {1, 0, 0, "COB"},
+    {1, 1, 0, "CNB"}, {1, 1, 1, "CCB"},
+    {1, 0, 0, "COB"}, {1, 0, 0, "COB"},
+    {1, 1, 0, "CNB"}, {1, 1, 1, "CCB"},
+    {1, 2, 0, "CNB"}, {1, 2, 1, "CCB"},
+    // bound 5
+    {5, 0, 0, "COOOOOB"}, {5, 0, 0, "COOOOOB"},
+    {5, 1, 0, "CNOOOOB"}, {5, 1, 1, "CCOOOOB"},
+    {5, 4, 0, "CNNNNOB"}, {5, 4, 4, "CCCCCOB"},
+    {5, 5, 0, "CNNNNNB"}, {5, 5, 5, "CCCCCCB"},
+    {5, 6, 0, "CNNNNNB"}, {5, 6, 5, "CCCCCCB"},
+};
+
+static char outcome_letter(sg::FindOutcome o)
+{
+    switch (o) {
+    case sg::FindOutcome::kBeyondBound: return 'B';
+    case sg::FindOutcome::kComplete: return 'C';
+    case sg::FindOutcome::kOverCap: return 'O';
+    case sg::FindOutcome::kNoRoom: return 'N';
+    }
+    return '?';
+}
+
+static void outcome_cases()
+{
+    size_t row = 0;
+    for (uint64_t bound : {uint64_t(1), uint64_t(5)})
+        for (uint64_t cap : {uint64_t(0), uint64_t(1), bound - 1, bound, bound + 1})
+            for (uint64_t room_got : {uint64_t(0), std::min(cap, bound)}) {
+                const OutcomeRow& r = kOutcomes[row++];
+                const bool row_ok = r.bound == bound && r.cap == cap && r.room_got == room_got;  // the table follows the grid
+                for (uint64_t total = 0; total <= bound + 1; ++total)
+                    check(row_ok && outcome_letter(sg::find_outcome(total, bound, room_got, cap)) == r.want[total], "find_outcome", (int)bound, (int)cap,
+                          (int)room_got, (int)total);
+            }
+}
+
+// order_editl: entries (e << shift) | distance over the end positions [lo, hi] with distances <= k
+static void editl_cases()
+{
+    const uint32_t shift = 5, k = 9;
+    const uint64_t lo = 129, hi = 100000;
+    std::vector<uint64_t> want;
+    for (uint64_t e = lo; e < hi; e += 1 + rnd(700)) want.push_back(e << shift | rnd(k + 1));
+    want.push_back(hi << shift | k);  // both ends of the range, the largest distance
+    want[0] = lo << shift;
+
+    std::vector<uint64_t> v = want;
+    check(sg::order_editl(v.data(), v.size(), lo, hi, k, shift) && v == want, "order_editl: sorted", 0, 0, 0, 0);
+    for (size_t i = v.size() - 1; i > 0; --i) std::swap(v[i], v[rnd((uint32_t)i + 1)]);
+    std::swap(v[0], v[1]);
+    check(v != want && sg::order_editl(v.data(), v.size(), lo, hi, k, shift) && v == want, "order_editl: shuffled", 0, 0, 0, 0);
+    const std::vector<uint64_t> untouched = {want[3], want[1], want[2]};
+    v = untouched;
+    check(sg::order_editl(v.data(), 0, lo, hi, k, shift) && v == untouched, "order_editl: no entry", 0, 0, 0, 0);
+
+    const uint64_t bad[4] = {
+        (want[5] >> shift) << shift | ((want[5] & 31) ^ 1),  // an end position twice, with another distance
+        (lo - 1) << shift,                                    // an end below lo
+        (hi + 1) << shift,                                    // an end above hi
+        (lo + 1) << shift | (k + 1),                          // a distance of k + 1
+    };
+    for (int b = 0; b < 4; ++b) {
+        v = want;
+        if (b == 3) v[1] = bad[b]; else v.insert(v.begin() + 2, bad[b]);
+        check(!sg::order_editl(v.data(), v.size(), lo, hi, k, shift), "order_editl: refused", b, 0, 0, 0);
+    }
+}
+
 int main()
 {
     pattern_cases();
     set_cases();
     span_cases();
+    outcome_cases();
+    editl_cases();
     printf("%d cases, %d failures\n", g_cases, g_failures);
     return g_failures ? 1 : 0;
 }
