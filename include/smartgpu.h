@@ -591,7 +591,8 @@ int smartgpu_pfind_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, cons
  * form over the reversed pattern, walking e, e-1, ...; with ops every column goes to LDS and the traceback reads cell values
  * back from the columns' bit vectors.
  * NOT offered: the longest start, all starts, all optimal alignments; m > 64, k > 7 (smartgpu_pfind_editl64 finds the ends of
- * longer patterns; their alignments are not offered), affine costs, byte texts, a kernel that finds and aligns in one pass.
+ * longer patterns; their alignments are not offered), affine costs, a kernel that finds and aligns in one pass.  (Byte texts:
+ * smartgpu_align_edit64 below.)
  * MEASURED on an MI355X, 1 Gi symbols of rand4 with planted copies of the pattern, about 1 Mi occurrences (7 Mi for m = 20,
  * k = 7, which rand4 holds by itself), every end of the find aligned, ms per call by the host clock, the list's copy to the
  * device and the results' copy back included (profiles/packed/RESULTS.md, "Edit distance: starts and alignments";
@@ -671,8 +672,8 @@ int smartgpu_pfind_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, uin
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / classes == NULL, m outside [1, SMARTGPU_EDIT_MAXM] (the
  * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
  * cap > 0.  The calls are synchronous: launches pending in the coalescing queue are sent first, and they never enter it.
- * NOT offered: m > 64 and k > 7, start positions and alignments, Hamming-only search on byte texts, a batch call, MultiText
- * shards and the `smart` harness.
+ * NOT offered: m > 64 and k > 7, Hamming-only search on byte texts, a batch call, MultiText shards and the `smart` harness.
+ * (Start positions and alignments: smartgpu_align_edit64 below.)
  * MEASURED on an MI355X, 1 GiB texts, m = 8, 20, 32, 33, 64, k = 0, 3, 7 (profiles/tedit/RESULTS.md; tools/tedit_probe.py; kernel
  * times from a kernel trace, call times by the host clock, medians of 5 / 7, run-to-run spread at most 3 % of the median but for the
  * first cell measured — rand4, m = 8, k = 0: 5-8 % per call): on rand4, rand128 and the English corpus alike text_edit_scan takes 0.71-0.82 ms for m <= 32 (one dword per column:
@@ -697,6 +698,46 @@ int smartgpu_search_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t 
                                    uint64_t *count, double *pre_ms, double *run_ms);
 int smartgpu_find_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
                                  uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+/* START POSITIONS and ALIGNMENTS on a byte text: smartgpu_palign_edit64 / smartgpu_palign_sets_edit64 asked of a
+ * smartgpu_text — which bytes an end position e reported by smartgpu_find_edit64 / smartgpu_find_edit_classes64 stands for,
+ * and which of them were substituted, added or skipped.  The contract is that of smartgpu_palign_edit64, word for word,
+ * with "byte" for "symbol" and D(e) as smartgpu_search_edit64 defines it: START, ALIGNMENT (the four operations and the
+ * fixed choice among optimal alignments) and PACKING are stated there and hold here unchanged.
+ * INPUT.  ends[0..count): end positions relative to text byte 0, as the find returns them for the same pattern, m, k, off,
+ * n — but any e in [off, off+n) is legal, in any order, duplicates included.
+ * OUTPUT.  starts[i] = s(ends[i]), distances[i] = D(ends[i]) (computed, not taken on trust), ops[3i .. 3i+3) the alignment;
+ * distances and ops may be NULL, ops == NULL skips the traceback.  An end with D(e) > k is decided exactly by
+ * min(m + k, e - off + 1) columns: starts[i] = UINT64_MAX, distances[i] = 255, three zero words, and the call still returns
+ * SMARTGPU_OK.
+ * CLASSES: the 32 * m bytes of smartgpu_search_edit_classes64; an empty row accepts nothing, a full row everything.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: the refusals of smartgpu_find_edit64 (P / classes == NULL,
+ * m outside [1, SMARTGPU_EDIT_MAXM], k > SMARTGPU_PMIS_MAX, a NULL text — with count == 0 too —, a range outside the text),
+ * ends == NULL or starts == NULL with count > 0, and an ends[i] outside [off, off+n) (the message names i and the value).
+ * count == 0 with a valid text is SMARTGPU_OK with no launch.  Lists longer than the device's find buffer go through in
+ * pieces, as for the packed calls.  The calls are synchronous: launches pending in the coalescing queue are sent first,
+ * and they never enter it.
+ * One lane per occurrence (text_edit_align; smart_amd/csrc/k_talign.hip): the recurrence in its DISTANCE form over the
+ * reversed pattern's 256 masks, which the workgroup copies to LDS (one barrier); a lane parks the 11 or 19 aligned dwords
+ * that hold its at most m + k <= 71 bytes in LDS and walks e, e-1, ...; with ops every column goes to LDS as well and the
+ * traceback reads cell values back from the columns' bit vectors.
+ * NOT offered: the longest start, all starts or all optimal alignments of a byte text; m > 64, k > 7; a kernel that finds
+ * and aligns in one pass; a batch call; MultiText shards; the `smart` harness; three-plane texts.
+ * MEASURED on an MI355X, 1 GiB of rand128, English and rand4 with planted copies of the pattern, about 1 Mi occurrences (9.5 Mi
+ * for rand4 at m = 20, k = 7, which it holds by itself), every end of the find aligned, ms per call by the host clock, the
+ * list's copy to the device and the results' copy back included, medians of 7 (profiles/tedit/RESULTS.md, "Starts and
+ * alignments"; tools/talign_probe.py): m = 20 / 64, k = 2 / 7, on all three texts alike: without ops 1.6-2.1 ms per call
+ * (1.5-1.9 ns per occurrence), which ADDS 25-32 % TO THE FIND that produced the ends (5.3-6.6 ms; 56 ms for the 9.5 Mi); with ops
+ * 3.0-4.5 ms (2.9-4.3 ns per occurrence), 48-77 % of the find, 1.8-2.7 x the call without ops, outside the run-to-run spread
+ * in every cell.  AGAINST smartgpu_palign_edit64 on the same rand4 bytes packed, same P, k and ends (identical answers):
+ * 0.97-1.00 x without ops, 1.00-1.10 x with ops, INSIDE the run-to-run spread in every cell.
+ * NOT measured: the kernel's own time (no kernel trace: how a call divides between kernel and copies is not known), the LDS
+ * copy of the table against reads from the arena, 64 / 32 occurrences per workgroup against other sizes, the uncoalesced
+ * window loads, the classes calls (the same kernels, another table), texts beyond 1 GiB (the at-size test checks answers
+ * beyond 2^32, not times). */
+int smartgpu_align_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                          const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+int smartgpu_align_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                                  const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 /* No device: the reverse complement of an IUPAC nucleotide pattern — a primer is searched on both strands.  P[0..m): the
  * letters smartgpu_iupac_sets accepts; out[j] = the complement of P[m-1-j]: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and
  * N stay; U reads as T (its complement is A; no U is ever written).  Case is preserved.  out has m bytes (no terminator is

@@ -29,6 +29,7 @@
 #include "peditl.hpp"
 #include "tedit.hpp"
 #include "palign.hpp"
+#include "talign.hpp"
 #include "planes.hpp"
 #include "planes_host.hpp"
 #include "planes3.hpp"
@@ -1038,6 +1039,8 @@ hipError_t (*g_text_edit_scan)(const TextEditArgs&, int, hipStream_t) = nullptr;
 hipError_t (*g_text_edit_find)(const TextEditArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
 // palign.hpp: set by k_palign.hip where that unit is linked
 hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
+// talign.hpp: set by k_talign.hip where that unit is linked
+hipError_t (*g_text_edit_align)(const TextAlignArgs&, hipStream_t) = nullptr;
 // planes3.hpp: set by k_planes3.hip where that unit is linked
 hipError_t (*g_planes3_pack)(const uint8_t*, uint64_t, uint32_t*, uint32_t*, uint32_t*, const uint8_t[7], hipStream_t) = nullptr;
 hipError_t (*g_planes3_scan)(const Plane3Args&, int, int, hipStream_t) = nullptr;
@@ -2945,47 +2948,37 @@ bool upload_positions(DeviceCtx* d, unsigned long long* dst, const uint64_t* src
     return true;
 }
 
-// Both align calls.  The device works in the find's own buffer (find_reserve, at most kFindKeep entries, so never an
-// allocation per call beyond the first): a piece of `part` occurrences is [io: part entries | ops: 3 * part words], so a piece
-// is kFindKeep occurrences without ops and kFindKeep / 4 with them; longer lists go through piece after piece.
-int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+// The refusal of a listed end outside the range [off, off+n), shared by the align calls: the message names i and the value
+bool ends_in_range(const char* call, const uint64_t* ends, uint64_t count, uint64_t off, uint64_t n)
 {
-    if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, &count);
-    if (rc != SMARTGPU_OK) return rc;
-    sg::PlaneEditArgs masks;
-    if ((rc = edit_masks(text, pat, m, sets, &masks)) != SMARTGPU_OK) return rc;  // (the pattern as given: the message names ITS position)
     for (uint64_t i = 0; i < count; ++i)
         if (ends[i] < off || ends[i] - off >= n) {
             set_error("%s: ends[%llu] = %llu outside the range [%llu,+%llu)", call, (unsigned long long)i, (unsigned long long)ends[i], (unsigned long long)off, (unsigned long long)n);
-            return SMARTGPU_ERR_ARG;
+            return false;
         }
-    if (count == 0) return SMARTGPU_OK;
-    if (!sg::g_planes_edit_align) { set_error("%s: this program holds no planes_edit_align kernel (k_palign.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    uint8_t rev[SMARTGPU_PEDIT_MAXM];
-    for (uint32_t j = 0; j < m; ++j) rev[j] = pat[m - 1 - j];
-    (void)edit_masks(text, rev, m, sets, &masks);  // the kernel walks backward: the masks of the REVERSED pattern
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    sg::PlaneAlignArgs a;
-    edit_head(a, text, m, k, off, n);
-    std::memcpy(a.peq, masks.peq, sizeof a.peq);
+    return true;
+}
+
+// Every align call.  The device works in the find's own buffer (find_reserve, at most kFindKeep entries, so never an
+// allocation per call beyond the first): a piece of `part` occurrences is [io: part entries | ops: 3 * part words], so a piece
+// is kFindKeep occurrences without ops and kFindKeep / 4 with them; longer lists go through piece after piece.
+// `launch(io, ops, part)` starts the family's kernel on d->stream over one piece.
+template <typename Launch>
+int align_pieces(const char* call, DeviceCtx* d, Launch launch, const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances,
+                 uint64_t* ops)
+{
     const uint64_t piece = ops ? kFindKeep / 4 : kFindKeep;
     for (uint64_t done = 0; done < count;) {
         const uint64_t part = std::min<uint64_t>(count - done, piece);
         bool own = false;
         unsigned long long* buf = find_reserve(d, part * (ops ? 4 : 1), &own);
         if (!buf) return SMARTGPU_ERR_NOMEM;
-        a.io = buf;
-        a.ops = ops ? buf + part : nullptr;
-        a.count = part;
-        const bool ok = upload_positions(d, a.io, ends + done, part) &&
-                        sg::g_planes_edit_align(a, text->planes, d->stream) == hipSuccess &&
+        unsigned long long* const dev_ops = ops ? buf + part : nullptr;
+        const bool ok = upload_positions(d, buf, ends + done, part) &&
+                        launch(buf, dev_ops, part) == hipSuccess &&
                         hipStreamSynchronize(d->stream) == hipSuccess &&
-                        copy_positions(d, starts + done, a.io, part) &&
-                        (!ops || copy_positions(d, ops + 3 * done, a.ops, 3 * part));
+                        copy_positions(d, starts + done, buf, part) &&
+                        (!ops || copy_positions(d, ops + 3 * done, dev_ops, 3 * part));
         if (!ok) set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
         if (own) (void)hipFree(buf);
         if (!ok) return SMARTGPU_ERR_HIP;
@@ -2998,6 +2991,76 @@ int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
         done += part;
     }
     return SMARTGPU_OK;
+}
+
+int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
+               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
+    if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
+    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, &count);
+    if (rc != SMARTGPU_OK) return rc;
+    sg::PlaneEditArgs masks;
+    if ((rc = edit_masks(text, pat, m, sets, &masks)) != SMARTGPU_OK) return rc;  // (the pattern as given: the message names ITS position)
+    if (!ends_in_range(call, ends, count, off, n)) return SMARTGPU_ERR_ARG;
+    if (count == 0) return SMARTGPU_OK;
+    if (!sg::g_planes_edit_align) { set_error("%s: this program holds no planes_edit_align kernel (k_palign.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    uint8_t rev[SMARTGPU_PEDIT_MAXM];
+    for (uint32_t j = 0; j < m; ++j) rev[j] = pat[m - 1 - j];
+    (void)edit_masks(text, rev, m, sets, &masks);  // the kernel walks backward: the masks of the REVERSED pattern
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    sg::PlaneAlignArgs a;
+    edit_head(a, text, m, k, off, n);
+    std::memcpy(a.peq, masks.peq, sizeof a.peq);
+    return align_pieces(call, d,
+                        [&](unsigned long long* io, unsigned long long* dev_ops, uint64_t part) {
+                            a.io = io;
+                            a.ops = dev_ops;
+                            a.count = part;
+                            return sg::g_planes_edit_align(a, text->planes, d->stream);
+                        },
+                        ends, count, starts, distances, ops);
+}
+
+// The same on a BYTE text (talign.hpp).  The 256 masks of the REVERSED pattern travel to the arena as tedit_stage sends them;
+// the staging buffer they leave from is the one upload_positions fills next, so the stream is synchronised in between.
+int talign_run(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
+    if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
+    const int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, &count);
+    if (rc != SMARTGPU_OK) return rc;
+    if (!ends_in_range(call, ends, count, off, n)) return SMARTGPU_ERR_ARG;
+    if (count == 0) return SMARTGPU_OK;
+    if (!sg::g_text_edit_align) { set_error("%s: this program holds no text_edit_align kernel (k_talign.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    uint8_t rev[32 * SMARTGPU_EDIT_MAXM];
+    if (classes) sg::talign_reverse_classes(pat, m, rev); else sg::talign_reverse_bytes(pat, m, rev);
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    if (!batch_reserve(d, kTEditArena, 1)) return SMARTGPU_ERR_NOMEM;
+    sg::TextEditArgs staged;
+    if (!tedit_stage(d, rev, classes, m, &staged) || hipStreamSynchronize(d->stream) != hipSuccess) {
+        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
+        return SMARTGPU_ERR_HIP;
+    }
+    static_assert(sg::kTextAlignNone == sg::kAlignNone, "align_pieces unpacks both kernels' entries");
+    sg::TextAlignArgs a;
+    a.text = text->data();
+    a.peq = staged.peq;
+    a.e_begin = off;
+    a.e_end = off + n;
+    a.m = m;
+    a.k = k;
+    return align_pieces(call, d,
+                        [&](unsigned long long* io, unsigned long long* dev_ops, uint64_t part) {
+                            a.io = io;
+                            a.ops = dev_ops;
+                            a.count = part;
+                            return sg::g_text_edit_align(a, d->stream);
+                        },
+                        ends, count, starts, distances, ops);
 }
 
 }  // namespace
@@ -3454,6 +3517,19 @@ int smartgpu_palign_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, con
                                 const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
 {
     return palign_run("palign_sets_edit64", sets, true, m, k, text, off, n, ends, count, starts, distances, ops);
+}
+
+/* ---- the same on byte texts (talign.hpp, k_talign.hip) ------------------------------------------------------------------ */
+int smartgpu_align_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                          const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    return talign_run("align_edit64", P, false, m, k, text, off, n, ends, count, starts, distances, ops);
+}
+
+int smartgpu_align_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                                  const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    return talign_run("align_edit_classes64", classes, true, m, k, text, off, n, ends, count, starts, distances, ops);
 }
 
 // smartgpu_iupac_sets (most = 4) and smartgpu_iupac_sets8 (most = 8): one set of rules

@@ -191,6 +191,8 @@ def _load(path):
         "smartgpu_pfind_sets_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_palign_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_palign_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "smartgpu_align_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "smartgpu_align_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
         # packed texts of five to eight values (three bit planes)
         "smartgpu_ptext_layout8": (i32, [u64, i32, C.POINTER(i32), C.POINTER(u64)]),
@@ -927,6 +929,58 @@ def find_edit_classes(classes, text, k, off=0, n=None, cap=1 << 20):
     """(ends, distances) of a pattern of byte classes (search_edit_classes), as find_edit returns them."""
     classes, m = _classes(classes)
     return _tedit_find("find_edit_classes64", classes, m, text, k, off, n, cap)
+
+
+def _talign(name, pat, m, text, k, ends, off, n, ops):
+    if n is None:
+        n = len(text) - off
+    ends = np.ascontiguousarray(ends, dtype=np.uint64)
+    count = len(ends)
+    starts = np.empty(count, dtype=np.uint64)
+    dist = np.empty(count, dtype=np.uint8)
+    words = np.empty((count, 3), dtype=np.uint64) if ops else None
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, text._h, off, n, ends.ctypes.data if count else None, count,
+                                            starts.ctypes.data if count else None, dist.ctypes.data if count else None,
+                                            words.ctypes.data if ops and count else None)
+    if rc != 0:
+        raise _err("%s rc=%d" % (name, rc))
+    return starts, dist, words
+
+
+def align_edit(P, text, k, ends, off=0, n=None, ops=True):
+    """(starts, distances, ops) of the END positions `ends` on a Text (as find_edit returns them for the same P, k, off, n; any
+    order, duplicates allowed, any e of the range) — smartgpu_align_edit64, palign_edit's contract on bytes: starts[i] is the
+    LARGEST s with ed(P, T[s..ends[i]]) = D(ends[i]) (uint64), distances[i] = D(ends[i]) (uint8, computed), ops the alignment
+    as uint64 of shape (count, 3) (edit_cigar reads a row), or None with ops=False (no traceback).  An end with D(e) > k:
+    start 2**64 - 1, distance 255, ops 0."""
+    P = _u8(P)
+    return _talign("align_edit64", P, len(P), text, k, ends, off, n, ops)
+
+
+def align_edit_classes(classes, text, k, ends, off=0, n=None, ops=True):
+    """align_edit for a pattern of byte CLASSES (search_edit_classes; smartgpu_align_edit_classes64)."""
+    classes, m = _classes(classes)
+    return _talign("align_edit_classes64", classes, m, text, k, ends, off, n, ops)
+
+
+def _find_then_align(name, find, align, pat, text, k, off, n, cap):
+    ends, dist = find(pat, text, k, off=off, n=n, cap=cap)
+    starts, adist, ops = align(pat, text, k, ends, off=off, n=n)
+    if not np.array_equal(adist, dist):
+        raise SmartGpuError("%s: the align call's distances differ from the find's" % name)
+    return starts, ends, dist, ops
+
+
+def find_edit_align(P, text, k, off=0, n=None, cap=1 << 20):
+    """(starts, ends, distances, ops): find_edit, then align_edit on its ends — every occurrence of P within edit distance k as
+    the interval [start, end] of the text, its distance and its alignment.  More than `cap` occurrences raise SmartGpuError,
+    as find_edit does."""
+    return _find_then_align("find_edit_align", find_edit, align_edit, P, text, k, off, n, cap)
+
+
+def find_edit_classes_align(classes, text, k, off=0, n=None, cap=1 << 20):
+    """find_edit_align for a pattern of byte classes (find_edit_classes, then align_edit_classes)."""
+    return _find_then_align("find_edit_classes_align", find_edit_classes, align_edit_classes, classes, text, k, off, n, cap)
 
 
 def search_host(algo, P, T):

@@ -27,6 +27,7 @@ UNITS = {
     "k_peditl": ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_palign": ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_tedit": ("k_tedit.hip", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_talign": ("k_talign.hip", "talign.hpp", "talign_host.hpp", "tedit.hpp", "tedit_host.hpp", "edit_align.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {
     "hor_scan": "k_hor", "hor_multi_scan": "k_horm", "hor_sample_scan": "k_hors", "text_sample_build": "k_hors","hor_scan_bp": "k_hor", "hor_scan_gram": "k_horg", "bm_scan_gram": "k_bmg", "bm_scan": "k_bm", "bndm_scan": "k_bndm", "sbndm_scan": "k_bndmx",
@@ -41,6 +42,7 @@ KERNEL_UNIT = {
     "planes_editl_scan": "k_peditl", "planes_editl_find": "k_peditl",
     "planes_edit_align": "k_palign",
     "text_edit_scan": "k_tedit", "text_edit_find": "k_tedit",
+    "text_edit_align": "k_talign",
 }
 
 
