@@ -467,7 +467,7 @@ int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char *P, uin
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P == NULL, m = 0 or m > SMARTGPU_XSIZE,
  * k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0.
  * No launch: m > n (count 0), more foreign bytes than k (count 0).
- * NOT offered: a batch call, k > 7, byte texts.  (Set patterns with mismatches: smartgpu_psearch_sets_mis64 below; insertions
+ * NOT offered: a batch call, k > 7, byte texts.  (Byte texts: smartgpu_search_mis64 below.  Set patterns with mismatches: smartgpu_psearch_sets_mis64 below; insertions
  * and deletions: smartgpu_psearch_edit64 below.)
  * MEASURED on an MI355X, 1 Gi symbols (profiles/packed/RESULTS.md, "Mismatches"): on rand4, m = 8 .. 256, planes_mis_scan takes
  * 1.22-1.26 / 1.25-1.94 / 1.34-2.11 / 1.55-3.56 x planes_scan's kernel time for k = 0 / 1 / 3 / 7 (per call 1.07-1.17 /
@@ -503,7 +503,7 @@ int smartgpu_pfind_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgp
  * m > SMARTGPU_XSIZE, a NULL text, a range outside the text, count == NULL, positions == NULL with cap > 0, and a set with a
  * bit at or above the text's number of values (bits 4..7 always are on one and two planes; the message names the position).
  * No launch: m > n (count 0), more empty sets than k (count 0).
- * NOT offered: a batch call, k > 7, byte texts.  (Insertions and deletions: smartgpu_psearch_sets_edit64 below.)
+ * NOT offered: a batch call, k > 7, byte texts.  (Byte texts: smartgpu_search_mis_classes64 below.  Insertions and deletions: smartgpu_psearch_sets_edit64 below.)
  * NOT measured: everything — no timing of these calls has been taken (tools/sets_mis_probe.py takes the three comparisons:
  * singleton sets against smartgpu_psearch_mis64, k = 0 against smartgpu_psearch_sets64, one find against the finds over
  * the pattern's exact expansions); the occupancy choices are smartgpu_psearch_mis64's, taken over unmeasured. */
@@ -672,8 +672,8 @@ int smartgpu_pfind_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, uin
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / classes == NULL, m outside [1, SMARTGPU_EDIT_MAXM] (the
  * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
  * cap > 0.  The calls are synchronous: launches pending in the coalescing queue are sent first, and they never enter it.
- * NOT offered: m > 64 and k > 7, Hamming-only search on byte texts, a batch call, MultiText shards and the `smart` harness.
- * (Start positions and alignments: smartgpu_align_edit64 below.)
+ * NOT offered: m > 64 and k > 7, a batch call, MultiText shards and the `smart` harness.
+ * (Start positions and alignments: smartgpu_align_edit64 below.  Substitutions only, no shifts: smartgpu_search_mis64 below.)
  * MEASURED on an MI355X, 1 GiB texts, m = 8, 20, 32, 33, 64, k = 0, 3, 7 (profiles/tedit/RESULTS.md; tools/tedit_probe.py; kernel
  * times from a kernel trace, call times by the host clock, medians of 5 / 7, run-to-run spread at most 3 % of the median but for the
  * first cell measured — rand4, m = 8, k = 0: 5-8 % per call): on rand4, rand128 and the English corpus alike text_edit_scan takes 0.71-0.82 ms for m <= 32 (one dword per column:
@@ -738,6 +738,55 @@ int smartgpu_align_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartg
                           const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 int smartgpu_align_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
                                   const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+/* MISMATCHES ON A BYTE TEXT: smartgpu_psearch_mis64 / smartgpu_pfind_mis64 asked of a smartgpu_text, whatever number of byte
+ * values it holds ("which fixed-width record fields, barcodes, motifs lie within k substitutions of this one, no shifts?").
+ * The contract is that of those calls with "byte" for "symbol": a START position s, off <= s <= off + n - m, is an occurrence
+ * when its DISTANCE — the number of j < m with T[s+j] != P[j] — is at most k.  Positions are ascending and relative to text
+ * byte 0; mismatches may be NULL, otherwise mismatches[i] receives the distance of positions[i].
+ * 1 <= m <= SMARTGPU_MIS_MAXM, 0 <= k <= SMARTGPU_PMIS_MAX.  With k = 0 the positions are smartgpu_find64's.  k >= m is legal:
+ * every start position of the range is an occurrence, its distance is still reported.  m > n: count 0, no launch.  A pattern
+ * byte the text does not hold needs no bookkeeping (the packed calls count such bytes on the host): it is a mismatch in every
+ * window, through the masks.  cap / count / SMARTGPU_ERR_NOMEM, cap == 0 with NULL buffers as a count and the meaning of
+ * pre_ms / run_ms are those of smartgpu_find_edit64 (pre_ms holds the masks' construction and staging).
+ * CLASSES: the 32 * m bytes of smartgpu_search_edit_classes64 — classes[32 * j + v / 8] bit v % 8 set: position j accepts
+ * byte v —; the distance is the number of j whose row does not accept T[s+j].  An empty row is a mismatch in every window, a
+ * full row never is.  With one bit per row the answers are those of the byte-pattern calls.
+ * These calls and smartgpu_search_edit64 answer different questions: that call reports END positions of matches of any length
+ * from m - k to m + k and accepts insertions and deletions; at equal k every occurrence here has its end s + m - 1 among that
+ * call's ends, not the other way round.
+ * One pass over the text (text_mis_scan, text_mis_find; smart_amd/csrc/k_tmis.hip), in text_edit_scan's geometry: a workgroup
+ * brings 32 KiB of text into LDS with coalesced loads, a lane walks the 128 windows that END in its run and the m - 1 bytes
+ * before them.  The pattern is 256 masks "position j does not accept this byte" (1 or 2 KiB, built on the host, read from LDS);
+ * per byte a lane shifts 1 / 2 / 3 bit-sliced counter dwords (k <= 1 / 3 / 7; twice as many for m > 32) and a sticky "over
+ * budget" dword by one window, adds the byte's mask, and tests one bit: smartgpu_psearch_mis64's counter, turned so that
+ * it moves with the text (smart_amd/csrc/tmis_host.hpp).
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / classes == NULL, m outside [1, SMARTGPU_MIS_MAXM] (the
+ * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, positions == NULL with
+ * cap > 0.  The calls are synchronous: launches pending in the coalescing queue are sent first, and they never enter it.
+ * NOT offered: m > 64, k > 7, a batch call, MultiText shards, the `smart` harness, alignments (a Hamming alignment is the
+ * window itself: T[s+j] against P[j]).
+ * MEASURED on an MI355X, 1 GiB of rand4, rand128 and the English corpus, m = 8, 20, 32, 33, 64, k = 0, 1, 3, 7
+ * (profiles/tedit/RESULTS.md, "Mismatches"; tools/tmis_probe.py; kernel times from a kernel trace, medians of 5, run-to-run
+ * spread at most 5 % of the median; call times by the host clock, medians of 7): text_mis_scan takes 0.39-0.44 / 0.47-0.54 /
+ * 0.56-0.64 ms for m <= 32 at k <= 1 / k = 3 / k = 7 (one, two, three counter dwords) and 0.59-0.70 / 0.78-0.93 / 0.98-1.17 ms for
+ * m = 33, 64, the same on all three texts.  AGAINST text_edit_scan at the same text, P and k: 0.55-0.57 / 0.66-0.68 / 0.77-0.80 x
+ * its kernel time for m <= 32 and 0.49-0.51 / 0.64-0.67 / 0.79-0.82 x for m = 33, 64, outside the spread in all 60 cells.
+ * AGAINST smartgpu_psearch_mis64 on the same rand4 bytes packed: the planes win, text_mis_scan takes 3.5-10.7 x planes_mis_scan's
+ * kernel time (3.3-8.2 x per call), outside the spread in every cell: a text of at most four values is worth packing.
+ * smartgpu_find_mis64 at 2^20 occurrences (one per KiB): 4.9 ms per call against 0.60 ms (m = 20, k = 2) and 1.32 ms (m = 64,
+ * k = 7) for the count, the list's copy, ordering and unpacking included.
+ * NOT measured: the four workgroups per CU, the run of 128 positions per lane, the rolled walk against an unrolled one, the
+ * compressed code object's load time, text_mis_find's kernel time, the classes calls (the same kernels, another table),
+ * texts beyond 1 GiB, hardware counters. */
+#define SMARTGPU_MIS_MAXM 64
+int smartgpu_search_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                          uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_find_mis64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                        uint64_t *positions, uint8_t *mismatches, uint64_t cap, uint64_t *count);
+int smartgpu_search_mis_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                                  uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_find_mis_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                                uint64_t *positions, uint8_t *mismatches, uint64_t cap, uint64_t *count);
 /* No device: the reverse complement of an IUPAC nucleotide pattern — a primer is searched on both strands.  P[0..m): the
  * letters smartgpu_iupac_sets accepts; out[j] = the complement of P[m-1-j]: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W and
  * N stay; U reads as T (its complement is A; no U is ever written).  Case is preserved.  out has m bytes (no terminator is

@@ -10,4 +10,5 @@ from .engine import (ALGOS, MIN_M, MultiText, PackedText, Plan, SmartGpuError, T
                      pfind_sets_mis, psearch, psearch_batch, psearch_edit, psearch_mis, psearch_sets, psearch_sets_edit, psearch_sets_mis,
                      ptext_layout, ptext_layout8, search,
                      align_edit, align_edit_classes, find_edit_align, find_edit_classes_align,
-                     byte_classes, find_edit, find_edit_classes, search_edit, search_edit_classes, search_batch, search_host, version)
+                     byte_classes, find_edit, find_edit_classes, search_edit, search_edit_classes,
+                     find_mis, find_mis_classes, search_mis, search_mis_classes, search_batch, search_host, version)

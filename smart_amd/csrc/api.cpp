@@ -28,6 +28,7 @@
 #include "pedit.hpp"
 #include "peditl.hpp"
 #include "tedit.hpp"
+#include "tmis.hpp"
 #include "palign.hpp"
 #include "talign.hpp"
 #include "planes.hpp"
@@ -1037,6 +1038,9 @@ hipError_t (*g_planes_editl_find)(const PlaneEditlArgs&, unsigned long long*, un
 // tedit.hpp: set by k_tedit.hip where that unit is linked
 hipError_t (*g_text_edit_scan)(const TextEditArgs&, int, hipStream_t) = nullptr;
 hipError_t (*g_text_edit_find)(const TextEditArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
+// tmis.hpp: set by k_tmis.hip where that unit is linked
+hipError_t (*g_text_mis_scan)(const TextMisArgs&, int, hipStream_t) = nullptr;
+hipError_t (*g_text_mis_find)(const TextMisArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
 // palign.hpp: set by k_palign.hip where that unit is linked
 hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
 // talign.hpp: set by k_talign.hip where that unit is linked
@@ -2875,6 +2879,82 @@ int tedit_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, u
     return rc;
 }
 
+// Mismatches on BYTE texts (tmis.hpp): the contract of smartgpu_psearch_mis64 / smartgpu_pfind_mis64 with a smartgpu_text in
+// place of the planes.  The checks of its four calls that need no device; `what` names the pattern argument.
+int check_tmis_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off,
+                    uint64_t n, const uint64_t* count)
+{
+    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
+    if (m < 1 || m > SMARTGPU_MIS_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_MIS_MAXM); return SMARTGPU_ERR_ARG; }
+    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u mismatches, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
+    if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
+    if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
+    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
+    return SMARTGPU_OK;
+}
+
+// The 256 masks "position j does NOT accept this byte" (tmis_host.hpp) travel as tedit_stage's: the same table, the same arena.
+bool tmis_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, sg::TextMisArgs* a)
+{
+    uint32_t neq[256][sg::kTEditWords];
+    if (classes) sg::mis_neq_classes(pat, m, neq); else sg::mis_neq_bytes(pat, m, neq);
+    const uint32_t words = static_cast<uint32_t>(sg::mis_words(m));
+    sg::edit_peq_table(neq, words, reinterpret_cast<uint32_t*>(d->pinned));
+    a->neq = reinterpret_cast<const uint32_t*>(d->arena);
+    return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+}
+
+void tmis_head(sg::TextMisArgs& a, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
+{
+    a.text = text->data();
+    a.e_begin = off;
+    a.e_end = off + n;
+    a.m = m;
+    a.k = k;
+}
+
+int tmis_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+               uint64_t* count, double* pre_ms, double* run_ms)
+{
+    const int rc = check_tmis_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    if (m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // no window fits: no launch
+    if (!sg::g_text_mis_scan) { set_error("%s: this program holds no text_mis_scan kernel (k_tmis.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    sg::TextMisArgs a;
+    tmis_head(a, text, m, k, off, n);
+    return count_run({call, "text_mis_scan", "start positions", "positions"}, text->device, kTEditArena, n - m + 1,
+                     [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a); },
+                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_mis_scan(a, d->num_cus, d->stream); },
+                     count, pre_ms, run_ms);
+}
+
+int tmis_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+              uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
+{
+    if (cap && !positions) { set_error("%s: positions NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
+    int rc = check_tmis_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    if (m > n) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    if (!sg::g_text_mis_find) { set_error("%s: this program holds no text_mis_find kernel (k_tmis.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    sg::TextMisArgs a;
+    tmis_head(a, text, m, k, off, n);
+    const RunNames w = {call, "text_mis_find", "start positions", "positions"};
+    // the kernel's entries hold END positions, the spans order_spans knows (tmis.hpp); a window's start is m - 1 below its end
+    rc = find_run(w, text->device, kTEditArena, n - m + 1,
+                  [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a); },
+                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_mis_find(a, out, room, d->num_cus, d->stream); },
+                  [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
+                  positions, cap, count);
+    if (rc == SMARTGPU_OK) {
+        unpack_mis(positions, mismatches, *count);
+        for (uint64_t i = 0; i < *count; ++i) positions[i] -= m - 1;
+    }
+    return rc;
+}
+
 // Edit distance, long patterns (peditl.hpp): m <= 256 and k <= 31, a switch that travels with the call, and entries that
 // the kernel writes in no order (order_editl sorts them).  edit_masks, eight dwords wide:
 int editl_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, sg::PlaneEditlArgs* a)
@@ -3479,6 +3559,31 @@ int smartgpu_find_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k,
                                  uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     return tedit_find("find_edit_classes64", classes, true, m, k, text, off, n, ends, distances, cap, count);
+}
+
+/* ---- mismatches on byte texts: smartgpu_psearch_mis64's question of a smartgpu_text (tmis.hpp, k_tmis.hip) --------------- */
+int smartgpu_search_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                          uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return tmis_count("search_mis64", P, false, m, k, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_find_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                        uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
+{
+    return tmis_find("find_mis64", P, false, m, k, text, off, n, positions, mismatches, cap, count);
+}
+
+int smartgpu_search_mis_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                                  uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return tmis_count("search_mis_classes64", classes, true, m, k, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_find_mis_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
+                                uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
+{
+    return tmis_find("find_mis_classes64", classes, true, m, k, text, off, n, positions, mismatches, cap, count);
 }
 
 /* ---- edit distance, long patterns: m <= 256, k <= 31 (peditl.hpp, k_peditl.hip) ---------------------------------------- */

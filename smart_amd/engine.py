@@ -183,6 +183,10 @@ def _load(path):
         "smartgpu_find_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_search_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_find_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_search_mis64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_find_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_search_mis_classes64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_find_mis_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_pfind_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_psearch_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -929,6 +933,35 @@ def find_edit_classes(classes, text, k, off=0, n=None, cap=1 << 20):
     """(ends, distances) of a pattern of byte classes (search_edit_classes), as find_edit returns them."""
     classes, m = _classes(classes)
     return _tedit_find("find_edit_classes64", classes, m, text, k, off, n, cap)
+
+
+def search_mis(P, text, k, off=0, n=None):
+    """The number of START positions s, off <= s <= off + n - len(P), in bytes [off, off+n) of a Text whose window of len(P)
+    bytes differs from P in at most k positions — substitutions only, no shifts; 0 <= k <= 7, 1 <= len(P) <= 64
+    (smartgpu_search_mis64).  The text may hold any byte values; a byte of P it does not hold is a mismatch in every window."""
+    P = _u8(P)
+    return _tedit_count("search_mis64", P, len(P), text, k, off, n)
+
+
+def find_mis(P, text, k, off=0, n=None, cap=1 << 20):
+    """(positions, mismatches) of P with at most k mismatches (search_mis) in bytes [off, off+n) of a Text: the ascending start
+    positions (uint64, relative to text byte 0) and the number of mismatches of each (uint8).  More than `cap` occurrences
+    raise SmartGpuError; its text names their number (smartgpu_find_mis64)."""
+    P = _u8(P)
+    return _tedit_find("find_mis64", P, len(P), text, k, off, n, cap)
+
+
+def search_mis_classes(classes, text, k, off=0, n=None):
+    """search_mis for a pattern of byte CLASSES: an (m, 32) uint8 array whose row j says which byte values position j accepts
+    (byte_classes; smartgpu_search_mis_classes64).  An empty row is a mismatch in every window, a full row never is."""
+    classes, m = _classes(classes)
+    return _tedit_count("search_mis_classes64", classes, m, text, k, off, n)
+
+
+def find_mis_classes(classes, text, k, off=0, n=None, cap=1 << 20):
+    """(positions, mismatches) of a pattern of byte classes (search_mis_classes), as find_mis returns them."""
+    classes, m = _classes(classes)
+    return _tedit_find("find_mis_classes64", classes, m, text, k, off, n, cap)
 
 
 def _talign(name, pat, m, text, k, ends, off, n, ops):

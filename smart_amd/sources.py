@@ -27,6 +27,7 @@ UNITS = {
     "k_peditl": ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_palign": ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_tedit": ("k_tedit.hip", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_tmis": ("k_tmis.hip", "tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_talign": ("k_talign.hip", "talign.hpp", "talign_host.hpp", "tedit.hpp", "tedit_host.hpp", "edit_align.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {
@@ -43,6 +44,7 @@ KERNEL_UNIT = {
     "planes_edit_align": "k_palign",
     "text_edit_scan": "k_tedit", "text_edit_find": "k_tedit",
     "text_edit_align": "k_talign",
+    "text_mis_scan": "k_tmis", "text_mis_find": "k_tmis",
 }
 
 
