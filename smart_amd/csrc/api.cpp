@@ -2804,14 +2804,15 @@ int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
     return rc;
 }
 
-// Edit distance on BYTE texts (tedit.hpp): the contract of the calls above with a smartgpu_text in place of the planes.
-// The checks of its four calls that need no device; `what` names the pattern argument.
-int check_tedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off,
-                     uint64_t n, const uint64_t* count)
+// BYTE texts: edit distance (tedit.hpp) and mismatches (tmis.hpp), the contracts of the packed calls above with a
+// smartgpu_text in place of the planes.  The checks of their calls that need no device; `what` names the pattern argument,
+// `noun` what k counts.
+int check_text_args(const char* call, const char* what, int max_m, const char* noun, const uint8_t* P, uint32_t m, uint32_t k,
+                    const smartgpu_text* text, uint64_t off, uint64_t n, const uint64_t* count)
 {
     if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > SMARTGPU_EDIT_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_EDIT_MAXM); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
+    if (m < 1 || m > (uint32_t)max_m) { set_error("%s: pattern length %u outside [1,%d]", call, m, max_m); return SMARTGPU_ERR_ARG; }
+    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u %s, at most %d", call, k, noun, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
     if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
     if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
     if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
@@ -2822,17 +2823,23 @@ int check_tedit_args(const char* call, const char* what, const uint8_t* P, uint3
 // staging buffer, on their way to the arena (kTEditArena bytes of it), as psearch_impl's patterns travel.  The staging
 // buffer is free: every call that fills it ends with a synchronisation.
 constexpr size_t kTEditArena = sizeof(uint32_t) * 256 * sg::kTEditWords;
-bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, sg::TextEditArgs* a)
+bool text_table_stage(DeviceCtx* d, const uint32_t (&table)[256][sg::kTEditWords], uint32_t words, const uint32_t** dev)
 {
-    uint32_t peq[256][sg::kTEditWords];
-    if (classes) sg::edit_peq_classes(pat, m, peq); else sg::edit_peq_bytes(pat, m, peq);
-    const uint32_t words = m <= 32 ? 1u : 2u;
-    sg::edit_peq_table(peq, words, reinterpret_cast<uint32_t*>(d->pinned));
-    a->peq = reinterpret_cast<const uint32_t*>(d->arena);
+    sg::edit_peq_table(table, words, reinterpret_cast<uint32_t*>(d->pinned));
+    *dev = reinterpret_cast<const uint32_t*>(d->arena);
     return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
 }
 
-void tedit_head(sg::TextEditArgs& a, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
+bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
+{
+    uint32_t peq[256][sg::kTEditWords];
+    if (classes) sg::edit_peq_classes(pat, m, peq); else sg::edit_peq_bytes(pat, m, peq);
+    return text_table_stage(d, peq, m <= 32 ? 1u : 2u, dev);
+}
+
+// what TextEditArgs, TextMisArgs and TextAlignArgs share: the text and the range, the pattern's length and k
+template <class Args>
+void text_head(Args& a, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
 {
     a.text = text->data();
     a.e_begin = off;
@@ -2844,14 +2851,14 @@ void tedit_head(sg::TextEditArgs& a, const smartgpu_text* text, uint32_t m, uint
 int tedit_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
                 uint64_t* count, double* pre_ms, double* run_ms)
 {
-    const int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    const int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_EDIT_MAXM, "edits", pat, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
     if (!sg::g_text_edit_scan) { set_error("%s: this program holds no text_edit_scan kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
     sg::TextEditArgs a;
-    tedit_head(a, text, m, k, off, n);
+    text_head(a, text, m, k, off, n);
     return count_run({call, "text_edit_scan", "end positions", "entries"}, text->device, kTEditArena, n,
-                     [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a); },
+                     [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a.peq); },
                      [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_edit_scan(a, d->num_cus, d->stream); },
                      count, pre_ms, run_ms);
 }
@@ -2860,7 +2867,7 @@ int tedit_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, u
                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_EDIT_MAXM, "edits", pat, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     if (n + k < m) {
         *count = 0;
@@ -2868,10 +2875,10 @@ int tedit_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, u
     }
     if (!sg::g_text_edit_find) { set_error("%s: this program holds no text_edit_find kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
     sg::TextEditArgs a;
-    tedit_head(a, text, m, k, off, n);
+    text_head(a, text, m, k, off, n);
     const RunNames w = {call, "text_edit_find", "end positions", "entries"};
     rc = find_run(w, text->device, kTEditArena, n,
-                  [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a); },
+                  [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a.peq); },
                   [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_edit_find(a, out, room, d->num_cus, d->stream); },
                   [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
                   ends, cap, count);
@@ -2879,51 +2886,26 @@ int tedit_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, u
     return rc;
 }
 
-// Mismatches on BYTE texts (tmis.hpp): the contract of smartgpu_psearch_mis64 / smartgpu_pfind_mis64 with a smartgpu_text in
-// place of the planes.  The checks of its four calls that need no device; `what` names the pattern argument.
-int check_tmis_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off,
-                    uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > SMARTGPU_MIS_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_MIS_MAXM); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u mismatches, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
-    if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// The 256 masks "position j does NOT accept this byte" (tmis_host.hpp) travel as tedit_stage's: the same table, the same arena.
-bool tmis_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, sg::TextMisArgs* a)
+// Mismatches on BYTE texts (tmis.hpp).  The 256 masks "position j does NOT accept this byte" (tmis_host.hpp) travel as
+// tedit_stage's: the same table, the same arena.
+bool tmis_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
 {
     uint32_t neq[256][sg::kTEditWords];
     if (classes) sg::mis_neq_classes(pat, m, neq); else sg::mis_neq_bytes(pat, m, neq);
-    const uint32_t words = static_cast<uint32_t>(sg::mis_words(m));
-    sg::edit_peq_table(neq, words, reinterpret_cast<uint32_t*>(d->pinned));
-    a->neq = reinterpret_cast<const uint32_t*>(d->arena);
-    return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
-
-void tmis_head(sg::TextMisArgs& a, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
-{
-    a.text = text->data();
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
+    return text_table_stage(d, neq, static_cast<uint32_t>(sg::mis_words(m)), dev);
 }
 
 int tmis_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
                uint64_t* count, double* pre_ms, double* run_ms)
 {
-    const int rc = check_tmis_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    const int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_MIS_MAXM, "mismatches", pat, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     if (m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // no window fits: no launch
     if (!sg::g_text_mis_scan) { set_error("%s: this program holds no text_mis_scan kernel (k_tmis.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
     sg::TextMisArgs a;
-    tmis_head(a, text, m, k, off, n);
+    text_head(a, text, m, k, off, n);
     return count_run({call, "text_mis_scan", "start positions", "positions"}, text->device, kTEditArena, n - m + 1,
-                     [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a); },
+                     [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a.neq); },
                      [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_mis_scan(a, d->num_cus, d->stream); },
                      count, pre_ms, run_ms);
 }
@@ -2932,7 +2914,7 @@ int tmis_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, ui
               uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
 {
     if (cap && !positions) { set_error("%s: positions NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_tmis_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, count);
+    int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_MIS_MAXM, "mismatches", pat, m, k, text, off, n, count);
     if (rc != SMARTGPU_OK) return rc;
     if (m > n) {
         *count = 0;
@@ -2940,11 +2922,11 @@ int tmis_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, ui
     }
     if (!sg::g_text_mis_find) { set_error("%s: this program holds no text_mis_find kernel (k_tmis.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
     sg::TextMisArgs a;
-    tmis_head(a, text, m, k, off, n);
+    text_head(a, text, m, k, off, n);
     const RunNames w = {call, "text_mis_find", "start positions", "positions"};
     // the kernel's entries hold END positions, the spans order_spans knows (tmis.hpp); a window's start is m - 1 below its end
     rc = find_run(w, text->device, kTEditArena, n - m + 1,
-                  [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a); },
+                  [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a.neq); },
                   [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_mis_find(a, out, room, d->num_cus, d->stream); },
                   [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
                   positions, cap, count);
@@ -3110,7 +3092,7 @@ int talign_run(const char* call, const uint8_t* pat, bool classes, uint32_t m, u
 {
     if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
     if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    const int rc = check_tedit_args(call, classes ? "classes" : "P", pat, m, k, text, off, n, &count);
+    const int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_EDIT_MAXM, "edits", pat, m, k, text, off, n, &count);
     if (rc != SMARTGPU_OK) return rc;
     if (!ends_in_range(call, ends, count, off, n)) return SMARTGPU_ERR_ARG;
     if (count == 0) return SMARTGPU_OK;
@@ -3120,19 +3102,13 @@ int talign_run(const char* call, const uint8_t* pat, bool classes, uint32_t m, u
     DeviceCtx* d = device_ctx_flushed(text->device);
     if (!d) return SMARTGPU_ERR_HIP;
     if (!batch_reserve(d, kTEditArena, 1)) return SMARTGPU_ERR_NOMEM;
-    sg::TextEditArgs staged;
-    if (!tedit_stage(d, rev, classes, m, &staged) || hipStreamSynchronize(d->stream) != hipSuccess) {
+    sg::TextAlignArgs a;
+    if (!tedit_stage(d, rev, classes, m, &a.peq) || hipStreamSynchronize(d->stream) != hipSuccess) {
         set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
         return SMARTGPU_ERR_HIP;
     }
     static_assert(sg::kTextAlignNone == sg::kAlignNone, "align_pieces unpacks both kernels' entries");
-    sg::TextAlignArgs a;
-    a.text = text->data();
-    a.peq = staged.peq;
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
+    text_head(a, text, m, k, off, n);
     return align_pieces(call, d,
                         [&](unsigned long long* io, unsigned long long* dev_ops, uint64_t part) {
                             a.io = io;

@@ -140,6 +140,27 @@ __device__ __forceinline__ void flush_hits(uint32_t lane_hits, unsigned long lon
     }
 }
 
+// The find kernels' counterpart: a wave reserves room for its lanes' entries behind `cursor` — a wave-wide exclusive prefix
+// sum of the lanes' counts `mine`, ONE atomicAdd by lane 0, the 64-bit base broadcast as two scalars — and each lane gets
+// its first slot back.  EVERY lane of the wave must reach the call (the shuffles and readfirstlane read whatever lanes are
+// active): a caller leaves per WAVE in front of it (`if (!__any(...)) continue;`), never per lane.  `lane` is the lane's
+// index in its wave.  The cursor counts what was found, not what was kept: the caller stores while slot < cap.
+static __device__ __forceinline__ unsigned long long wave_reserve(uint32_t mine, unsigned long long* cursor, uint32_t lane)
+{
+    uint32_t incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += up;
+    }
+    const uint32_t total = __shfl(incl, 63, 64);
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(cursor, (unsigned long long)total);
+    base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+           __builtin_amdgcn_readfirstlane((uint32_t)base);
+    return base + (incl - mine);
+}
+
 // 16 bytes at a (text, any alignment) vs 16 bytes at b (pattern slot), first `nb`
 // bytes only (1 <= nb <= 16).  Both reads stay in bounds by construction: the text
 // buffer has a back pad and the pattern slot of the blob is 4224 zero-padded bytes.

@@ -371,18 +371,7 @@ __global__ __launch_bounds__(THREADS) void packed_find(ScanArgs a, uint64_t row_
         if (!__any(cand != 0)) continue;
         // wave-wide exclusive prefix sum of the lanes' hit counts
         const uint32_t mine = __popc(cand);
-        uint32_t incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d, 64);
-            if (lane >= (uint32_t)d) incl += up;
-        }
-        const uint32_t total = __shfl(incl, 63, 64);
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-        base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-               __builtin_amdgcn_readfirstlane((uint32_t)base);
-        unsigned long long slot = base + (incl - mine);
+        unsigned long long slot = wave_reserve(mine, a.count, lane);
         while (cand) {
             const uint32_t k = __builtin_ctz(cand);
             cand &= cand - 1;

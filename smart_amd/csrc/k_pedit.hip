@@ -129,18 +129,7 @@ static __device__ __forceinline__ void planes_edit_body(const PlaneEditArgs& a, 
             uint32_t mine = 0;
 #pragma unroll
             for (uint32_t w = 0; w < kEditDw; ++w) mine += __builtin_popcount(M[w]);
-            uint32_t incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, 64);
-                if (lane >= (uint32_t)d) incl += up;
-            }
-            const uint32_t total = __shfl(incl, 63, 64);
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                   __builtin_amdgcn_readfirstlane((uint32_t)base);
-            unsigned long long slot = base + (incl - mine);
+            unsigned long long slot = wave_reserve(mine, a.count, lane);
             const uint64_t pos = c * kEditRun;
 #pragma unroll
             for (uint32_t w = 0; w < kEditDw; ++w) {

@@ -134,18 +134,7 @@ static __device__ __forceinline__ void planes_editl_body(const PlaneEditlArgs& a
                     if (!__any(M != 0u)) continue;
                     // planes_find's output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
                     const uint32_t mine = __builtin_popcount(M);
-                    uint32_t incl = mine;
-#pragma unroll
-                    for (int s = 1; s < 64; s <<= 1) {
-                        const uint32_t up = __shfl_up(incl, s, 64);
-                        if (lane >= (uint32_t)s) incl += up;
-                    }
-                    const uint32_t total = __shfl(incl, 63, 64);
-                    unsigned long long base = 0;
-                    if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-                    base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                           __builtin_amdgcn_readfirstlane((uint32_t)base);
-                    unsigned long long slot = base + (incl - mine);
+                    unsigned long long slot = wave_reserve(mine, a.count, lane);
                     const uint64_t pos = c * kEditlRun + (uint64_t)(xd - kEditlWarm);  // (hits lie in owned pieces: xd >= kEditlWarm)
                     uint32_t r = M;
                     while (r) {

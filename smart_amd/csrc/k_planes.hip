@@ -295,18 +295,7 @@ __global__ __launch_bounds__(kPlanesT, 8) void planes_find(PlaneArgs a, unsigned
             uint32_t mine = 0;
 #pragma unroll
             for (uint32_t w = 0; w < kChunk; ++w) mine += __builtin_popcount(M[u][w]);
-            uint32_t incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, 64);
-                if (lane >= (uint32_t)d) incl += up;
-            }
-            const uint32_t total = __shfl(incl, 63, 64);
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                   __builtin_amdgcn_readfirstlane((uint32_t)base);
-            unsigned long long slot = base + (incl - mine);
+            unsigned long long slot = wave_reserve(mine, a.count, lane);
             const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
 #pragma unroll
             for (uint32_t w = 0; w < kChunk; ++w) {
@@ -503,18 +492,7 @@ static __device__ __forceinline__ void planes_sets_body(const PlaneSetArgs& a, u
             } else {
                 if (!__any(live != 0)) continue;
                 // planes_find's output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
-                uint32_t incl = mine;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(incl, d, 64);
-                    if (lane >= (uint32_t)d) incl += up;
-                }
-                const uint32_t total = __shfl(incl, 63, 64);
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-                base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                       __builtin_amdgcn_readfirstlane((uint32_t)base);
-                unsigned long long slot = base + (incl - mine);
+                unsigned long long slot = wave_reserve(mine, a.count, lane);
                 const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
 #pragma unroll
                 for (uint32_t w = 0; w < kChunk; ++w) {
@@ -768,18 +746,7 @@ static __device__ __forceinline__ void planes_mis_body(const PlaneMisArgs& a, ui
             } else {
                 if (!__any(live != 0)) continue;
                 // planes_find's output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
-                uint32_t incl = mine;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(incl, d, 64);
-                    if (lane >= (uint32_t)d) incl += up;
-                }
-                const uint32_t total = __shfl(incl, 63, 64);
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-                base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                       __builtin_amdgcn_readfirstlane((uint32_t)base);
-                unsigned long long slot = base + (incl - mine);
+                unsigned long long slot = wave_reserve(mine, a.count, lane);
                 const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
                 const uint32_t bias = a.foreign - start;  // distance = counter - start + the positions the host counted
 #pragma unroll
@@ -1042,18 +1009,7 @@ static __device__ __forceinline__ void planes_sets_mis_body(const PlaneSetMisArg
             } else {
                 if (!__any(live != 0)) continue;
                 // planes_find's output stage: wave-wide exclusive prefix sum of the lanes' counts, one atomic, the lanes' stores
-                uint32_t incl = mine;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(incl, d, 64);
-                    if (lane >= (uint32_t)d) incl += up;
-                }
-                const uint32_t total = __shfl(incl, 63, 64);
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-                base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                       __builtin_amdgcn_readfirstlane((uint32_t)base);
-                unsigned long long slot = base + (incl - mine);
+                unsigned long long slot = wave_reserve(mine, a.count, lane);
                 const uint64_t pos = (cw + (uint64_t)u * kPlanesT + lane) * kPos;
                 const uint32_t bias = a.foreign - start;  // distance = counter - start + the positions the host counted
 #pragma unroll

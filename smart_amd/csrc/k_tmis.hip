@@ -1,9 +1,10 @@
 // k_tmis.hip — byte texts: text_mis_scan / text_mis_find, occurrences with at most k MISMATCHES (substitutions only: the
 // Hamming distance of a window of m bytes) by a bit-sliced counter that moves with the text (tmis_host.hpp)
-// (one translation unit per kernel family: dev_common.hpp; the interface: tmis.hpp; the masks and the recurrence: tmis_host.hpp)
+// (one translation unit per kernel family: dev_common.hpp; the interface: tmis.hpp; the masks and the recurrence: tmis_host.hpp; the tile: text_tile.hpp)
 #include "dev_common.hpp"
 #include "launch_common.hpp"
 #include "tmis.hpp"
+#include "text_tile.hpp"
 
 namespace sg {
 
@@ -12,22 +13,12 @@ namespace sg {
 // and hold at most k bytes their pattern position does not accept: planes_mis_scan's question (k_planes.hip) asked of a
 // text of BYTES.  WORDS = 1 / 2 for m <= 32 / 64, BITS = 1 / 2 / 3 counter planes for k <= 1 / 3 / 7.
 //
-// THE GEOMETRY is text_edit_scan's (k_tedit.hip), restated here and not shared: that unit's sources stay as they were
-// measured.  A lane owns kTEditRun = 128 consecutive END positions e = s + m - 1, lane l of a wave the l-th run of 64 (a
-// wave: kFindSpan ends), the four waves of a workgroup four consecutive spans: a TILE of 32 KiB.  The tile comes into LDS
-// with coalesced 16-byte loads (ld_stream16) together with the run before it — 257 runs —, and every lane then walks its run
-// out of LDS, one dword read per four steps.  The m - 1 <= 63 bytes before a lane's run, the part of its first windows
-// that lies in the neighbour's run, are the end of the neighbour's row; they are walked without counting.
-//   * LDS layout: [128 bytes: flush_hits][256 x WORDS dwords: neq][257 rows of kRowBytes = 132 bytes: the tile].
-//     Run r of the tile (r = 0: the one before it) is row r: 128 bytes of text and 4 never written.
-//   * Banks.  ds_read_b32 serves a wave in two groups of 32 lanes, bank = dword address mod 32.  With rows of 33 dwords lane
-//     l's t-th dword is dword 33 l + t, bank (l + t) mod 32: the 32 lanes of a group on 32 distinct banks, in the warm-up
-//     too.  The tile's stores: chunk q (16 bytes) goes to row q / 8, chunk c = q % 8 of it, as four dword stores; dword i
-//     of it is on bank (r + 4 c + i) mod 32, and a group's 32 lanes hold four consecutive rows and all eight chunks of
-//     each, so the stores are conflict-free as well.  The mask lookups are a broadcast or a conflict as the text decides.
-//   * Bounds: none are checked.  The tile begins at most 128 bytes below text byte 0 (kFrontPad lies there) and ends less
-//     than kTMisTile bytes behind e_end <= n (kBackPad lies there); what is read outside [e_begin, e_end) is parked, at
-//     most walked, and never part of an answer that is kept (THE WALK).  Both are asserted below.
+// THE GEOMETRY is text_edit_scan's, and both units take it from text_tile.hpp: a lane owns kTEditRun = 128 consecutive END
+// positions e = s + m - 1, a workgroup's 256 lanes a TILE of 32 KiB, parked in LDS together with the run before it in rows
+// of 132 bytes; that header holds the layout, the banks, the bounds and the BARRIERS rule of the tile loop.  The
+// m - 1 <= 63 bytes before a lane's run, the part of its first windows that lies in the neighbour's run, are the end of the
+// neighbour's row; they are walked without counting.  What is read outside [e_begin, e_end) is parked, at most walked, and
+// never part of an answer that is kept (THE WALK).
 //
 // THE WALK.  edit_run_walk(c, e_begin, e_end, m - 1) says which bytes decide a lane's owned ends: it may start fresh
 // (mis_fresh) m - 1 bytes before its first owned end, or at e_begin when that is nearer.  A Hamming window needs exactly its
@@ -40,34 +31,17 @@ namespace sg {
 // the contract: no window begins before e_begin.  A lane at the edge of the range walks bytes it keeps nothing of; a wave
 // with no owned end skips the walk.
 //
-// BARRIERS.  The tile loop holds two __syncthreads() per trip (before the tile is overwritten, after it is written).  Its
-// trip count is tiles blockIdx.x, blockIdx.x + gridDim.x, ... below ntiles, and ntiles is computed from e_begin and e_end
-// alone: a function of blockIdx, gridDim and the kernel arguments, the same for all 256 lanes of a workgroup.  Nothing
-// between the barriers leaves the loop or skips a trip: a lane whose run lies outside the range keeps no answer and still
-// stores its chunks and arrives; the two `continue`s — a wave with no owned end, the find's wave with no hit — are per
-// WAVE, stand behind the trip's second barrier and lead only to the next trip's first barrier, which every wave reaches.  flush_hits' own two barriers come after the loop, where all
-// lanes arrive.
+// BARRIERS (text_tile.hpp).  A lane whose run lies outside the range keeps no answer and still stores its chunks and
+// arrives; the two `continue`s — a wave with no owned end, the find's wave with no hit — are per WAVE, stand behind the
+// trip's second barrier and lead only to the next trip's first barrier, which every wave reaches.
 //
-// The find's output stage is text_edit_find's: per 32 owned positions a hit mask and the counter planes' top bits, a
-// wave-wide prefix sum, ONE atomicAdd on the cursor by lane 0, ordinary vector stores of (e << kMisShift) | distance while
+// The find's output stage is text_edit_find's: per 32 owned positions a hit mask and the counter planes' top bits, a wave's
+// slots from wave_reserve (ONE atomicAdd on the cursor), ordinary vector stores of (e << kMisShift) | distance while
 // slot < cap (tmis.hpp: the host turns e into s).  No scratch, no static LDS.
 // ---------------------------------------------------------------------------
-constexpr int kTMisT = 256;
-constexpr int kTMisWgs = 4;                                  // workgroups per CU: 160 KiB of LDS / 35.3 KiB
-constexpr uint32_t kTMisTile = kTMisT * kTEditRun;           // bytes of text a workgroup owns per trip
-constexpr uint32_t kRowBytes = kTEditRun + 4, kRowDw = kRowBytes / 4;
-constexpr int kPadDw = 1;                                    // dwords between a row's last byte and the next row's first
-constexpr uint32_t kTileRows = kTMisT + 1;                   // the run before the tile: the first lane's warm-up
-constexpr uint32_t kTileChunks = kTileRows * (kTEditRun / 16);  // 16-byte chunks parked per trip
-constexpr uint32_t kNeqOff = 128;                            // behind flush_hits' 128 bytes
-static_assert(kRowDw % 32 == 1, "lanes a row apart sit on neighbouring banks");
-static_assert(kFrontPad >= kTEditRun && kFrontPad % 16 == 0, "the run before the first tile lies in the front pad");
-static_assert(kBackPad >= kTMisTile, "the last tile ends in the back pad");
-static_assert(kTileChunks > 8u * kTMisT && kTileChunks <= 9u * kTMisT, "a tile is parked in nine rounds, the ninth partial");
-
-__host__ __device__ constexpr uint32_t tmis_tile_off(int words) { return kNeqOff + 1024u * words; }
-__host__ __device__ constexpr uint32_t tmis_lds_bytes(int words) { return tmis_tile_off(words) + kTileRows * kRowBytes; }
-static_assert(kTMisWgs * tmis_lds_bytes(2) <= 160u * 1024u, "four workgroups' LDS on a CU");
+using Tile = TextTile<4>;  // (k_tedit.hip's variant build without the pad is not this unit's)
+constexpr int kPadDw = Tile::kPadDw;  // dwords between a row's last byte and the next row's first
+static_assert(Tile::kRowDw % 32 == 1, "lanes a row apart sit on neighbouring banks");
 
 template <int WORDS, int BITS, bool FIND>
 static __device__ __forceinline__ void text_mis_body(const TextMisArgs& a, uint8_t* smem, unsigned long long* __restrict__ out,
@@ -76,36 +50,20 @@ static __device__ __forceinline__ void text_mis_body(const TextMisArgs& a, uint8
     constexpr int GROUPS = kTEditRun / 32;  // answers are kept per 32 positions: the find's four hit masks
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t top = a.m - 1, tb = top & 31u, bias = (1u << BITS) - 1u - a.k;
-    uint32_t* const neq = reinterpret_cast<uint32_t*>(smem + kNeqOff);
-    uint8_t* const tile = smem + tmis_tile_off(WORDS);
+    uint32_t* const neq = reinterpret_cast<uint32_t*>(smem + kMasksOff);
+    uint8_t* const tile = smem + text_tile_off(WORDS);
     // this lane's row, and the dwords it walks: dword j >= 0 of its run at row[j], dword j < 0 (the warm-up) at row[j - kPadDw]: the row before
-    const uint32_t* const row = reinterpret_cast<const uint32_t*>(tile) + kRowDw * (tid + 1u);
-#pragma unroll
-    for (int w = 0; w < WORDS; ++w) neq[tid + kTMisT * w] = a.neq[tid + kTMisT * w];  // (read after the loop's barriers)
+    const uint32_t* const row = reinterpret_cast<const uint32_t*>(tile) + Tile::kRowDw * (tid + 1u);
+    text_table_park<WORDS>(neq, a.neq, tid);
 
     const uint64_t c0 = a.e_begin / kTEditRun;
-    const uint64_t ntiles = (a.e_end - c0 * kTEditRun + kTMisTile - 1) / kTMisTile;  // the same for every lane of the grid
+    const uint64_t ntiles = text_tile_count(a.e_begin, a.e_end);  // the grid's own count (text_tile.hpp, BARRIERS)
     uint32_t hits = 0;
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         __syncthreads();  // every lane is done with the tile before
-        {
-            const uint8_t* src = a.text + c0 * kTEditRun + t * kTMisTile - kTEditRun;
-            uint4 v[9];
-            v[8] = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-            for (uint32_t i = 0; i < 8; ++i) v[i] = ld_stream16(src + 16u * (tid + kTMisT * i));
-            if (tid < kTileChunks - 8u * kTMisT) v[8] = ld_stream16(src + 16u * (tid + kTMisT * 8u));
-#pragma unroll
-            for (uint32_t i = 0; i < 9; ++i) {
-                const uint32_t q = tid + kTMisT * i;
-                if (i < 8 || q < kTileChunks) {
-                    uint32_t* d = reinterpret_cast<uint32_t*>(tile + (q >> 3) * kRowBytes + (q & 7u) * 16u);
-                    d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
-                }
-            }
-        }
+        Tile::park(a.text + c0 * kTEditRun + t * kTextTile - kTEditRun, tile, tid);
         __syncthreads();
-        const uint64_t c = c0 + t * kTMisT + tid;
+        const uint64_t c = c0 + t * kTextT + tid;
         const EditWalk wk = edit_run_walk(c, a.e_begin, a.e_end, top);
         if (!__any(wk.last > wk.own)) continue;  // a wave outside the range (to the next trip's barrier: see BARRIERS)
         const int lo = mis_keep_from(wk, a.m), hi = wk.last;
@@ -174,18 +132,7 @@ static __device__ __forceinline__ void text_mis_body(const TextMisArgs& a, uint8
             uint32_t mine = 0;
 #pragma unroll
             for (int g = 0; g < GROUPS; ++g) mine += __builtin_popcount(M[g]);
-            uint32_t incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, 64);
-                if (lane >= (uint32_t)d) incl += up;
-            }
-            const uint32_t total = __shfl(incl, 63, 64);
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(a.count, (unsigned long long)total);
-            base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-                   __builtin_amdgcn_readfirstlane((uint32_t)base);
-            unsigned long long slot = base + (incl - mine);
+            unsigned long long slot = wave_reserve(mine, a.count, lane);
             uint64_t pos = c * kTEditRun;
 #pragma unroll 1
             for (int g = 0; g < GROUPS; ++g, pos += 32) {  // one copy of the stores' code: the groups move down to M[0]
@@ -212,44 +159,38 @@ static __device__ __forceinline__ void text_mis_body(const TextMisArgs& a, uint8
 }
 
 template <int WORDS, int BITS>
-__global__ __launch_bounds__(kTMisT, kTMisWgs) void text_mis_scan(TextMisArgs a)
+__global__ __launch_bounds__(kTextT, kTextWgs) void text_mis_scan(TextMisArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // tmis_lds_bytes(WORDS)
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // Tile::lds_bytes(WORDS)
     text_mis_body<WORDS, BITS, false>(a, smem, nullptr, 0);
 }
 
 template <int WORDS, int BITS>
-__global__ __launch_bounds__(kTMisT, kTMisWgs) void text_mis_find(TextMisArgs a, unsigned long long* __restrict__ out, unsigned long long cap)
+__global__ __launch_bounds__(kTextT, kTextWgs) void text_mis_find(TextMisArgs a, unsigned long long* __restrict__ out, unsigned long long cap)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // tmis_lds_bytes(WORDS)
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // Tile::lds_bytes(WORDS)
     text_mis_body<WORDS, BITS, true>(a, smem, out, cap);
 }
 
 static bool tmis_args_ok(const TextMisArgs& a) { return a.m >= 1 && a.m <= kTMisMaxM && a.k <= SMARTGPU_PMIS_MAX && a.text && a.neq; }
 
-static uint32_t text_mis_grid(const TextMisArgs& a, int num_cus)
-{
-    const uint64_t tiles = (a.e_end - a.e_begin / kTEditRun * kTEditRun + kTMisTile - 1) / kTMisTile;
-    return (uint32_t)std::min<uint64_t>(tiles, (uint64_t)num_cus * kTMisWgs);
-}
-
 template <int WORDS, int BITS>
 static void launch_scan_as(const TextMisArgs& a, uint32_t grid, hipStream_t stream)
 {
-    hipLaunchKernelGGL((text_mis_scan<WORDS, BITS>), dim3(grid), dim3(kTMisT), tmis_lds_bytes(WORDS), stream, a);
+    hipLaunchKernelGGL((text_mis_scan<WORDS, BITS>), dim3(grid), dim3(kTextT), Tile::lds_bytes(WORDS), stream, a);
 }
 
 template <int WORDS, int BITS>
 static void launch_find_as(const TextMisArgs& a, unsigned long long* out, unsigned long long cap, uint32_t grid, hipStream_t stream)
 {
-    hipLaunchKernelGGL((text_mis_find<WORDS, BITS>), dim3(grid), dim3(kTMisT), tmis_lds_bytes(WORDS), stream, a, out, cap);
+    hipLaunchKernelGGL((text_mis_find<WORDS, BITS>), dim3(grid), dim3(kTextT), Tile::lds_bytes(WORDS), stream, a, out, cap);
 }
 
 static hipError_t launch_text_mis_scan(const TextMisArgs& a, int num_cus, hipStream_t stream)
 {
     if (!tmis_args_ok(a)) return hipErrorInvalidValue;
     if (a.e_end <= a.e_begin) return hipSuccess;
-    const uint32_t grid = text_mis_grid(a, num_cus);
+    const uint32_t grid = text_tile_grid(a.e_begin, a.e_end, num_cus);
     switch (mis_words(a.m) * 10 + mis_bits(a.k)) {
     case 11: launch_scan_as<1, 1>(a, grid, stream); break;
     case 12: launch_scan_as<1, 2>(a, grid, stream); break;
@@ -265,7 +206,7 @@ static hipError_t launch_text_mis_find(const TextMisArgs& a, unsigned long long*
 {
     if (!tmis_args_ok(a)) return hipErrorInvalidValue;
     if (a.e_end <= a.e_begin) return hipSuccess;
-    const uint32_t grid = text_mis_grid(a, num_cus);
+    const uint32_t grid = text_tile_grid(a.e_begin, a.e_end, num_cus);
     switch (mis_words(a.m) * 10 + mis_bits(a.k)) {
     case 11: launch_find_as<1, 1>(a, out, cap, grid, stream); break;
     case 12: launch_find_as<1, 2>(a, out, cap, grid, stream); break;

@@ -26,8 +26,8 @@ UNITS = {
     "k_pedit": ("k_pedit.hip", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_peditl": ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_palign": ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
-    "k_tedit": ("k_tedit.hip", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
-    "k_tmis": ("k_tmis.hip", "tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_tedit": ("k_tedit.hip", "text_tile.hpp", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_tmis": ("k_tmis.hip", "text_tile.hpp", "tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_talign": ("k_talign.hip", "talign.hpp", "talign_host.hpp", "tedit.hpp", "tedit_host.hpp", "edit_align.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {

@@ -2,6 +2,7 @@
 libraries, the source registry, the documentation, the refusals that are decided before the first HIP call, and the compiled
 kernels planes_find<1> / planes_find<2>."""
 import ctypes
+import glob
 import os
 import re
 import subprocess
@@ -51,6 +52,14 @@ def test_python_functions_exist():
 def test_sources_registry_names_the_kernel():
     assert sources.KERNEL_UNIT["planes_find"] == "k_planes"
     assert sources.kernel_sha256("planes_find") == sources.kernel_sha256("planes_scan")
+
+
+def test_the_wave_reservation_stands_once():
+    """The find kernels' slots come from dev_common.hpp's wave_reserve: no unit keeps a prefix sum of its own
+    (kernels_ab.inc holds the superseded kernels as they were)."""
+    own = [os.path.basename(p) for p in glob.glob(os.path.join(sources.CSRC, "*.hip")) + glob.glob(os.path.join(sources.CSRC, "*.hpp"))
+           if "__shfl_up(" in open(p).read()]
+    assert own == ["dev_common.hpp"]
 
 
 def test_integration_md_names_both_symbols():

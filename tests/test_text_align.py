@@ -81,7 +81,7 @@ def test_sources_registry_has_the_unit_and_leaves_the_other_units_alone():
     assert sources.KERNEL_UNIT["text_edit_align"] == "k_talign"
     sha = sources.unit_sha256("k_talign")
     assert sources.kernel_sha256("text_edit_align") == sha and sha not in (sources.unit_sha256("k_tedit"), sources.unit_sha256("k_palign"))
-    assert sources.UNITS["k_tedit"] == ("k_tedit.hip", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp")
+    assert sources.UNITS["k_tedit"] == ("k_tedit.hip", "text_tile.hpp", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp")
     assert sources.UNITS["k_palign"] == ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp")
     makefile = open(os.path.join(sources.CSRC, "Makefile")).read()
     assert re.search(r"^KERNELS\s*:=.*\bk_talign\b", makefile, flags=re.M)

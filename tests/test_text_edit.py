@@ -55,7 +55,7 @@ def test_python_functions_exist():
 
 def test_sources_registry_has_the_unit_and_leaves_the_packed_unit_alone():
     assert [f for f in sources.UNITS["k_tedit"] if f.startswith("k_")] == ["k_tedit.hip"]
-    for f in ("tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"):
+    for f in ("text_tile.hpp", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"):
         assert f in sources.UNITS["k_tedit"], f
         assert os.path.exists(os.path.join(sources.CSRC, f)), f
     for k in ("text_edit_scan", "text_edit_find"):
@@ -64,7 +64,7 @@ def test_sources_registry_has_the_unit_and_leaves_the_packed_unit_alone():
     assert sources.UNITS["k_pedit"] == ("k_pedit.hip", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp")
     makefile = open(os.path.join(sources.CSRC, "Makefile")).read()
     assert re.search(r"^KERNELS\s*:=.*\bk_tedit\b", makefile, flags=re.M)
-    for header in ("tedit.hpp", "tedit_host.hpp"):
+    for header in ("tedit.hpp", "tedit_host.hpp", "text_tile.hpp"):
         assert re.search(r"^HEADERS\s*:=.*\b%s\b" % re.escape(header), makefile, flags=re.M), header
 
 

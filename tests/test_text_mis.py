@@ -55,25 +55,30 @@ def test_python_functions_exist():
 
 def test_sources_registry_has_the_unit_and_leaves_the_edit_unit_alone():
     assert [f for f in sources.UNITS["k_tmis"] if f.startswith("k_")] == ["k_tmis.hip"]
-    for f in ("tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"):
-        assert f in sources.UNITS["k_tmis"], f
+    assert sources.UNITS["k_tmis"] == ("k_tmis.hip", "text_tile.hpp", "tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp")
+    for f in sources.UNITS["k_tmis"]:
         assert os.path.exists(os.path.join(sources.CSRC, f)), f
     for k in ("text_mis_scan", "text_mis_find"):
         assert sources.KERNEL_UNIT[k] == "k_tmis"
         assert sources.kernel_sha256(k) == sources.unit_sha256("k_tmis") != sources.unit_sha256("k_tedit")
-    assert sources.UNITS["k_tedit"] == ("k_tedit.hip", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp")
+    assert sources.UNITS["k_tedit"] == ("k_tedit.hip", "text_tile.hpp", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp")
     assert sources.KERNEL_UNIT["text_edit_scan"] == sources.KERNEL_UNIT["text_edit_find"] == "k_tedit"
     makefile = open(os.path.join(sources.CSRC, "Makefile")).read()
     assert re.search(r"^KERNELS\s*:=.*\bk_tmis\b", makefile, flags=re.M)
-    for header in ("tmis.hpp", "tmis_host.hpp"):
+    for header in ("tmis.hpp", "tmis_host.hpp", "text_tile.hpp"):
         assert re.search(r"^HEADERS\s*:=.*\b%s\b" % re.escape(header), makefile, flags=re.M), header
 
 
 def test_the_new_unit_includes_no_other_kernel_unit_and_shares_the_run_length():
-    """k_tmis.hip restates the tile staging: it reads tedit_host.hpp's geometry (the run, edit_run_walk), never k_tedit.hip."""
+    """k_tmis.hip reads tedit_host.hpp's geometry (the run, edit_run_walk), never k_tedit.hip; the tile and its staging are
+    text_tile.hpp's for both units, and neither keeps a copy of the loads."""
     unit = open(os.path.join(sources.CSRC, "k_tmis.hip")).read()
     assert not re.search(r'#include\s+"k_', unit)
     assert "edit_run_walk(c, a.e_begin, a.e_end, top)" in unit  # a warm-up of m - 1 bytes
+    for name in ("k_tmis.hip", "k_tedit.hip"):
+        text = open(os.path.join(sources.CSRC, name)).read()
+        assert re.search(r'#include\s+"text_tile.hpp"', text) and "ld_stream16(" not in text, name
+    assert "ld_stream16(" in open(os.path.join(sources.CSRC, "text_tile.hpp")).read()
     assert re.search(r"constexpr uint32_t kTEditRun = 128;", open(os.path.join(sources.CSRC, "tedit_host.hpp")).read())
 
 
@@ -150,13 +155,13 @@ def test_count_null_is_refused_by_name():
     """count == NULL needs a text handle to be reached: the order of the checks is read from the source, the message from a
     call in tests/test_text_mis_gpu.py."""
     api = open(os.path.join(sources.CSRC, "api.cpp")).read()
-    body = api[api.index("int check_tmis_args("):api.index("bool tmis_stage(")]
-    order = [body.index(s) for s in ("%s is NULL", "outside [1,%d]", "mismatches, at most", "text handle is NULL", "outside the text", "count must not be NULL")]
+    body = api[api.index("int check_text_args("):api.index("bool text_table_stage(")]
+    order = [body.index(s) for s in ("%s is NULL", "outside [1,%d]", "k = %u %s, at most", "text handle is NULL", "outside the text", "count must not be NULL")]
     assert order == sorted(order)
     # and every refusal of the two paths comes before the first thing that touches a device
     for fn, until in (("int tmis_count(", "int tmis_find("), ("int tmis_find(", "// Edit distance, long patterns")):
         path = api[api.index(fn):api.index(until)]
-        assert path.index("check_tmis_args(") < path.index("_run(")
+        assert path.index('check_text_args(call, classes ? "classes" : "P", SMARTGPU_MIS_MAXM, "mismatches",') < path.index("_run(")
 
 
 def test_the_python_classes_calls_refuse_another_shape():

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Per-kernel facts from hipcc's gfx950 assembly (-save-temps=obj: *-hip-amdgcn-amd-amdhsa-gfx950.s):
-instructions, VGPRs, SGPRs, scratch bytes, and a hash of the instruction stream (labels and comments stripped),
+"""Per-kernel facts from hipcc's gfx950 assembly (make -C smart_amd/csrc asm: *-hip-amdgcn-amd-amdhsa-gfx950.s):
+instructions, code bytes, VGPRs, SGPRs, scratch bytes, static LDS, occupancy, and a hash of the instruction stream (labels
+and comments stripped),
 so that two builds can be compared kernel by kernel — "did moving this kernel to its own translation unit change
 its code?" — without a GPU.
 
@@ -34,6 +35,10 @@ def parse(path):
             if m and meta:
                 meta[list(meta)[-1]][m.group(1)] = int(m.group(2))
                 continue
+            m = re.match(r"^; (codeLenInByte|TotalNumSgprs|LDSByteSize|Occupancy)\s*[=:]\s*(\d+)", s)
+            if m and meta:  # the compiler's summary behind a kernel; the first one after its .amdhsa_kernel block is its own
+                meta[list(meta)[-1]].setdefault(m.group(1), int(m.group(2)))
+                continue
             m = re.match(r"^(_Z\w+):\s*(;.*)?$", s)
             if m and cur is None:
                 cur = m.group(1)
@@ -56,7 +61,8 @@ def parse(path):
         name = re.sub(r"^void sg::", "", names[k])
         name = re.sub(r"\(sg::ScanArgs.*$", "", name)
         out[name] = {"insts": len(v["body"]), "vgpr": meta[k].get("next_free_vgpr"), "sgpr": meta[k].get("next_free_sgpr"),
-                     "scratch": meta[k].get("private_segment_fixed_size"), "hash": hashlib.sha1(code.encode()).hexdigest()[:10]}
+                     "scratch": meta[k].get("private_segment_fixed_size"), "bytes": meta[k].get("codeLenInByte"),
+                     "sgprs": meta[k].get("TotalNumSgprs"), "lds": meta[k].get("LDSByteSize"), "occ": meta[k].get("Occupancy"), "hash": hashlib.sha1(code.encode()).hexdigest()[:10]}
     return out
 
 
@@ -67,14 +73,17 @@ def main():
         new = {}
         for p in args[2:]:
             new.update(parse(p))
-        print("%-58s %7s %7s %5s %5s %4s %4s  %s" % ("kernel", "insts", "new", "vgpr", "new", "scr", "new", "code"))
+        print("%-58s %7s %7s %6s %6s %5s %5s %5s %5s %4s %4s %4s %4s %4s %4s  %s"
+              % ("kernel", "insts", "new", "bytes", "new", "vgpr", "new", "sgpr", "new", "scr", "new", "lds", "new", "occ", "new", "code"))
         for k in sorted(set(old) | set(new)):
             o, n = old.get(k), new.get(k)
             if o is None or n is None:
                 print("%-58s %s" % (k[:58], "only in the NEW build" if o is None else "only in the OLD build"))
                 continue
             same = "same" if o["hash"] == n["hash"] else "differs"
-            print("%-58s %7d %7d %5s %5s %4s %4s  %s" % (k[:58], o["insts"], n["insts"], o["vgpr"], n["vgpr"], o["scratch"], n["scratch"], same))
+            print("%-58s %7d %7d %6s %6s %5s %5s %5s %5s %4s %4s %4s %4s %4s %4s  %s"
+                  % (k[:58], o["insts"], n["insts"], o["bytes"], n["bytes"], o["vgpr"], n["vgpr"], o["sgprs"], n["sgprs"], o["scratch"], n["scratch"],
+                     o["lds"], n["lds"], o["occ"], n["occ"], same))
         return
     for p in args:
         print("==", p)
