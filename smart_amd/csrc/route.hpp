@@ -1,11 +1,11 @@
 // route.hpp — which launcher a plan leads to: ONE decision (route, launch.hip) behind launch_scan, scan_kernel_name and the
-// groups of a pattern set in one grid (group_key).  Host-only; included by launch.hip and api.cpp, by no kernel unit.
+// groups of a pattern set in one grid (group_key).  Host-only; included by launch.hip, plan.hpp and api.cpp, by no kernel unit.
 #pragma once
 #include "kernels.hpp"
 
 namespace sg {
 
-// The four words a plan carries besides its tables, as api.cpp build_blob encodes them (ScanArgs holds the same four):
+// The four words a plan carries besides its tables, as plan.cpp build_blob encodes them (ScanArgs holds the same four):
 //  halo           bits 0-7: the skip kernels' back halo H = min(m-1, kHaloMax) (KR: min(m-1, 32); KMP: m-1, forward) — for
 //                 BNDM / BNDML (m <= 32) bndm_scan's q instead, with kBndmGramWindow (bit 8) beside it;
 //                 bits 8-15, HOR only: the q of Horspool's q-gram table (0: the byte table)

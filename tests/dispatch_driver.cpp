@@ -1,16 +1,24 @@
-// dispatch_driver.cpp — tests/test_dispatch.py builds this with launch.hip and tables.cpp, for the product and for the A/B
-// build: the launchers of launch_common.hpp as STUBS that record what they were called with, and a main that drives
-// launch_scan over a grid of (algorithm, pattern length, pattern, text codes, smartgpu_tune setting).  No GPU, no HIP call.
+// dispatch_driver.cpp — tests/test_dispatch.py builds this with plan.cpp, launch.hip and tables.cpp, for the product and
+// for the A/B build, under AddressSanitizer and UBSan: the launchers of launch_common.hpp as STUBS that record what they were
+// called with, and a main that drives launch_scan over a grid of (algorithm, pattern length, pattern, text codes,
+// smartgpu_tune setting).  No GPU, no HIP call.
 //
-//   dispatch_driver <english text file> [--dump]
+//   dispatch_driver <english text file> [--dump | --blobs]
 //
-// Checks, per grid point: launch_scan made exactly one launch, and scan_kernel_name names the kernel it launched (the gram
+// Checks, per plan: the layout facts of its blob that the kernels rely on without checking (check_blob).  Per grid point:
+// launch_scan made exactly one launch, and scan_kernel_name names the kernel it launched (the gram
 // launchers count as their base kernel).  Per pair of plans of one algorithm and length: an equal group_key means an equal
 // launcher, argument and launcher-read words (what a pattern set in one grid relies on).  --dump prints every grid point.
-#include "../smart_amd/csrc/api.cpp"  // build_blob, check_pattern: the plan builder itself, not a copy
+// --blobs prints one line per plan — its words, the blob's size and a 64-bit FNV-1a hash of its bytes — and skips the grid:
+// two trees build the same plans if their outputs are equal.
+#include "../smart_amd/csrc/plan.hpp"  // build_blob, min_pattern: the plan builder itself, not a copy
 #include "../smart_amd/csrc/launch_common.hpp"
+#include "../smart_amd/csrc/tables.hpp"
 
 #include <array>
+#include <cstdio>
+#include <cstring>
+#include <string>
 
 namespace sg {
 
@@ -56,28 +64,76 @@ hipError_t launch_ab_kmp(const ScanArgs& a, int, hipStream_t, bool* handled)
     return k ? record("launch_ab_kmp", k, 0, a) : hipSuccess;
 }
 #endif
-// what else api.cpp links against; never called here
-hipError_t launch_find(const ScanArgs&, unsigned long long*, unsigned long long, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_generate(uint8_t*, uint64_t, int, uint64_t, uint64_t, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_tile_fill(uint8_t*, const uint8_t*, uint64_t, uint64_t, uint64_t, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_text_alphabet(const uint8_t*, uint64_t, uint32_t*, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_probe_read(const uint8_t*, uint64_t, unsigned long long*, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_pack(const uint8_t*, uint64_t, uint32_t*, uint32_t*, int, const uint8_t[3], hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_scan(const PlaneArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_find(const PlaneArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_sets_scan(const PlaneSetArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_sets_find(const PlaneSetArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_mis_scan(const PlaneMisArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_mis_find(const PlaneMisArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_sets_mis_scan(const PlaneSetMisArgs&, int, int, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_planes_sets_mis_find(const PlaneSetMisArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) { return hipErrorNotSupported; }
 
 }  // namespace sg
 
+// Bytes from kTableOff on that the algorithm's kernels find at places kernels.hpp states (sizes only: what the tables
+// hold is tables.cpp's and the parity tests' matter).
+static size_t own_table_bytes(int algo, uint32_t m, const sg::PlanWords& w)
+{
+    const size_t fp = 32;  // the fingerprint: u32 fp[4], u32 fpmask[4]
+    switch (algo) {
+        case SMARTGPU_BM: return ((2 * (768 + size_t(m) + 1) + 3) & ~size_t(3)) + fp;
+        case SMARTGPU_KMP: {
+            size_t end = sg::kmp_spread_off(m);  // next[m+1] and the compact table lie below it
+            bool spread = w.prefer_packed != 0;
+#ifdef SMARTGPU_AB
+            spread = true;
+#endif
+            if (spread) end += sg::kmp_runs_table_bytes(w.prefer_packed ? w.prefer_packed : sg::kmp_window(m)) + sg::kKmpQBytes;
+#ifdef SMARTGPU_AB
+            end += 256 * 256;  // kmp_runs1's table follows it
+#endif
+            return end - sg::kTableOff;
+        }
+        case SMARTGPU_SO: return 1024;
+        case SMARTGPU_SA: return 2048;
+        case SMARTGPU_SBNDM: return 1024 + fp + 4;
+        case SMARTGPU_BNDML:
+            if (m > 32) return 1024 * (std::min(m, sg::kBndmlWindow) <= 64 ? 2 : std::min(m, sg::kBndmlWindow) <= 128 ? 4 : 8) + 4 + fp;
+            return 1024 + fp;
+        case SMARTGPU_BNDM: return 1024 + fp;
+        case SMARTGPU_EPSM: return fp;
+        case SMARTGPU_KR: return 4 + fp;
+        default: return 512 + 256 + fp;  // HOR's layout: TUNEDBM, RAITA, HASH3/5/8, QS
+    }
+}
+
+// What the kernels rely on without checking; `blob` is the vector the driver reuses for every plan.  Returns the failures.
+static int check_blob(int algo, const uint8_t* P, uint32_t m, const char* corpus, const std::vector<uint8_t>& blob, const sg::PlanWords& w)
+{
+    int bad = 0;
+    auto fail = [&](const char* what) { printf("BLOB MISMATCH %s m=%u %s: %s (size %zu, so_off %u)\n", sg::kAlgoNames[algo], m, corpus, what, blob.size(), w.so_off); ++bad; };
+    if (blob.size() % 256 || blob.size() < sg::kPatternBytes) { fail("size is no multiple of 256 or below the pattern slot"); return bad; }
+    if (std::memcmp(blob.data(), P, m)) fail("bytes [0, m) are not the pattern");
+    for (uint32_t i = m; i < sg::kPatternBytes; ++i)
+        if (blob[i]) { fail("a byte of [m, kPatternBytes) is not zero"); break; }
+    size_t tables_end = blob.size();
+    if (w.so_off) {
+        if (w.so_off % 16 || w.so_off < sg::kPatternBytes || size_t(w.so_off) + 1024 > blob.size()) { fail("so_off is unaligned, inside the pattern slot or its masks end outside the blob"); return bad; }
+        const std::vector<uint32_t> S = sg::shift_or_masks(P, m);
+        if (std::memcmp(blob.data() + w.so_off, S.data(), 1024)) fail("the dwords at so_off are not the Shift-Or masks");
+        tables_end = w.so_off;
+    }
+    if (sg::kTableOff + own_table_bytes(algo, m, w) > tables_end) fail("the algorithm's own tables do not fit below so_off / the blob's end");
+    std::vector<uint8_t> fresh;
+    const sg::PlanWords f = sg::build_blob(fresh, algo, P, m);
+    if (fresh != blob || f.halo != w.halo || f.prefer_packed != w.prefer_packed || f.sparse != w.sparse || f.so_off != w.so_off) fail("a build into a fresh vector differs from the build into the reused one");
+    return bad;
+}
+
+static unsigned long long fnv1a(const std::vector<uint8_t>& v)
+{
+    unsigned long long h = 14695981039346656037ull;
+    for (uint8_t b : v) h = (h ^ b) * 1099511628211ull;
+    return h;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s <english text file> [--dump]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s <english text file> [--dump | --blobs]\n", argv[0]); return 2; }
     const bool dump = argc > 2 && std::string(argv[2]) == "--dump";
+    const bool blobs = argc > 2 && std::string(argv[2]) == "--blobs";
     std::vector<uint32_t> ms;
     for (uint32_t m = 1; m <= 40; ++m) ms.push_back(m);
     for (uint32_t m : {47u, 48u, 63u, 64u, 65u, 255u, 256u, 4096u}) ms.push_back(m);
@@ -112,10 +168,15 @@ int main(int argc, char** argv)
     unsigned long long points = 0, pairs = 0, bad = 0;
     for (int algo = 0; algo < SMARTGPU_NUM_ALGOS; ++algo)
         for (uint32_t m : ms) {
-            const uint8_t* P0 = corpus[0].data() + 1000 + 3 * m;
-            if (check_pattern(algo, P0, m) != SMARTGPU_OK) continue;  // the algorithm does not apply to this length
+            if (m < sg::min_pattern(algo)) continue;  // the algorithm does not apply to this length
             sg::PlanWords words[4];
-            for (int c = 0; c < 4; ++c) words[c] = build_blob(blob, algo, corpus[c].data() + 1000 + 3 * m, m);
+            for (int c = 0; c < 4; ++c) {
+                const uint8_t* P = corpus[c].data() + 1000 + 3 * m;
+                const sg::PlanWords w = words[c] = sg::build_blob(blob, algo, P, m);
+                bad += check_blob(algo, P, m, corpus_names[c], blob, w);
+                if (blobs) printf("%s m=%u %s words=%x,%u,%u,%u size=%zu fnv1a=%016llx\n", sg::kAlgoNames[algo], m, corpus_names[c], w.halo, w.prefer_packed, w.sparse, w.so_off, blob.size(), fnv1a(blob));
+            }
+            if (blobs) continue;
             for (const auto& t : tunes) {
                 sg::g_tune[0] = t[0]; sg::g_tune[2] = t[1]; sg::g_tune[3] = t[2]; sg::g_tune[6] = t[3];
                 for (int tc = 0; tc < 3; ++tc) {
@@ -137,7 +198,7 @@ int main(int argc, char** argv)
                         const bool ok = e == hipSuccess && k.n == 1 && std::strcmp(name, k.kernel) == 0;
                         if (dump || !ok)
                             printf("%s%s m=%u %s codes=%d tune=%d,%d,%d,%d words=%x,%u,%u,%u name=%s -> %s(%ld) %s x%d halo=%u fp_off=%u pp=%u sparse=%u so_off=%u codes=%u,%x,%x\n",
-                                   ok ? "" : "MISMATCH ", kAlgoNames[algo], m, corpus_names[c], tc, t[0], t[1], t[2], t[3], w.halo, w.prefer_packed, w.sparse, w.so_off,
+                                   ok ? "" : "MISMATCH ", sg::kAlgoNames[algo], m, corpus_names[c], tc, t[0], t[1], t[2], t[3], w.halo, w.prefer_packed, w.sparse, w.so_off,
                                    name, k.launcher, k.extra, k.kernel, k.n, k.a.halo, k.a.fp_off, k.a.prefer_packed, k.a.sparse, k.a.so_off, k.codes.shift, k.codes.symtab, k.codes.one);
                         bad += !ok;
                     }
@@ -147,13 +208,13 @@ int main(int argc, char** argv)
                             if (keys[x] != keys[y]) continue;
                             const sg::Call &p = calls[x], &q = calls[y];
                             if (p.launcher == q.launcher && p.kernel == q.kernel && p.extra == q.extra && p.a.halo == q.a.halo && p.a.prefer_packed == q.a.prefer_packed && p.a.sparse == q.a.sparse) continue;
-                            printf("GROUP MISMATCH %s m=%u %s / %s codes=%d tune=%d,%d,%d,%d: one key, %s(%ld) and %s(%ld)\n", kAlgoNames[algo], m, corpus_names[x], corpus_names[y],
+                            printf("GROUP MISMATCH %s m=%u %s / %s codes=%d tune=%d,%d,%d,%d: one key, %s(%ld) and %s(%ld)\n", sg::kAlgoNames[algo], m, corpus_names[x], corpus_names[y],
                                    tc, t[0], t[1], t[2], t[3], p.launcher, p.extra, q.launcher, q.extra);
                             ++bad;
                         }
                 }
             }
         }
-    fprintf(dump ? stderr : stdout, "%llu grid points, %llu pairs, %zu tune settings, %llu failures\n", points, pairs, tunes.size(), bad);
+    fprintf(dump || blobs ? stderr : stdout, "%llu grid points, %llu pairs, %zu tune settings, %llu failures\n", points, pairs, tunes.size(), bad);
     return bad ? 1 : 0;
 }

@@ -282,7 +282,7 @@ def test_launch_pool_of_the_multi_gpu_search():
 
 
 def test_kernel_choice_follows_the_pattern(oracle):
-    """The plan picks the kernel from the pattern's own symbols (api.cpp build_blob, DESIGN.md §4);
+    """The plan picks the kernel from the pattern's own symbols (plan.cpp build_blob, DESIGN.md §4);
     smartgpu_kernel_for answers without a device."""
     from smart_amd import engine
     kf = smart_amd.kernel_for

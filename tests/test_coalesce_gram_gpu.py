@@ -48,7 +48,7 @@ def groups_of_eight():
 
 def streaming(P, algo="hor"):
     """True for a pattern whose Horspool plan takes hor_scan's streaming form: its symbols do not repeat, by the rule of
-    api.cpp build_blob (ordered pairs of equal symbols against 1/48 of all pairs; below 32 bytes, four such pairs)."""
+    plan.cpp build_blob (ordered pairs of equal symbols against 1/48 of all pairs; below 32 bytes, four such pairs)."""
     m = len(P)
     c = np.bincount(P, minlength=256).astype(np.int64)
     pairs = int((c * (c - 1)).sum())

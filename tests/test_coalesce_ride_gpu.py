@@ -16,7 +16,7 @@ a rider (riders) or went alone.  Where riders rises by the number of repeating l
 where passes rises by the number of keys sent, each with two entries or more, every kernel was a hor_multi_scan.
 
 The pattern that occurs often.  A pattern (x y)^(m/2) has two symbols, so its plan carries Horspool's q-gram table
-(api.cpp build_blob: q = 8 from 16 bytes on) and its route is {hor, 8}, not the {hor, 0} a pass takes: by the rider's
+(plan.cpp build_blob: q = 8 from 16 bytes on) and its route is {hor, 8}, not the {hor, 0} a pass takes: by the rider's
 own rules it never rides.  It is launched here all the same, twice, between the launches of a pass, and counted: it
 goes alone.  The frequent RIDER is the nearest pattern that can ride: period nine over nine symbols (fewer than nine
 symbols in 32 bytes or more leave hor_scan's route), with a planted run of that period of 3000 bytes (400 in the small

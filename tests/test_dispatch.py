@@ -8,7 +8,12 @@ every smartgpu_tune setting the build accepts for the keys launch.hip reads:
 * launch_scan makes exactly one launch, and scan_kernel_name names the kernel that launch runs (the gram launchers
   count as their base kernel) — an invariant, not a recorded table: retuning a threshold does not touch this test;
 * plans of one algorithm and length with equal group_key lead to the same launcher with the same argument and the
-  same launcher-read words — what a pattern set that runs as one grid relies on."""
+  same launcher-read words — what a pattern set that runs as one grid relies on.
+
+The driver links the plan builder (plan.cpp) itself and asserts, for every blob of that grid, the layout facts the kernels
+rely on without checking: size and pattern slot, the place and contents of the Shift-Or masks of a rerouted plan, room
+for the algorithm's own tables where kernels.hpp states their place, and that a build into a reused vector equals a
+build into a fresh one.  All of it is compiled with AddressSanitizer and UBSan and runs as a program, without a preload."""
 import os
 import re
 import subprocess
@@ -19,13 +24,14 @@ from conftest import ROOT
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "smart_amd", "csrc")
-FLAGS = ["-O1", "-std=c++17", "-Wall", "-Wno-unused-result", "-Wno-unused-value", "-Wno-unused-function"]
+SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+FLAGS = ["-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-result", "-Wno-unused-value", "-Wno-unused-function"] + SANITIZE
 
 
 @pytest.mark.parametrize("build", ["product", "ab"])
 def test_kernel_name_is_the_launcher_launch_scan_calls(tmp_path, build):
     define = ["-DSMARTGPU_AB"] if build == "ab" else []
-    units = {"launch": os.path.join(CSRC, "launch.hip"), "tables": os.path.join(CSRC, "tables.cpp"),
+    units = {"plan": os.path.join(CSRC, "plan.cpp"), "launch": os.path.join(CSRC, "launch.hip"), "tables": os.path.join(CSRC, "tables.cpp"),
              "driver": os.path.join(ROOT, "tests", "dispatch_driver.cpp")}
     procs = [(u, subprocess.Popen([HIPCC] + FLAGS + define + ["--offload-arch=gfx950", "-c", "-o", str(tmp_path / (u + ".o")), src],
                                   stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)) for u, src in units.items()]
@@ -33,7 +39,7 @@ def test_kernel_name_is_the_launcher_launch_scan_calls(tmp_path, build):
         out, _ = p.communicate(timeout=900)
         assert p.returncode == 0, (u, out)
     exe = tmp_path / "dispatch_driver"
-    subprocess.check_call([HIPCC, "-o", str(exe)] + [str(tmp_path / (u + ".o")) for u in units] + ["-ldl"])
+    subprocess.check_call([HIPCC, "-o", str(exe)] + SANITIZE + [str(tmp_path / (u + ".o")) for u in units] + ["-ldl"])
     r = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "english_excerpt.txt")], capture_output=True, text=True, timeout=600)
     summary = re.search(r"(\d+) grid points, (\d+) pairs, (\d+) tune settings, (\d+) failures", r.stdout)
     assert summary, r.stdout[-2000:] + r.stderr[-2000:]

@@ -60,7 +60,7 @@ def test_fuzz_vectors(oracle):
 
 
 def test_fuzz_vectors_every_algorithm_on_its_own_kernel(oracle):
-    """The plans send short patterns and patterns whose symbols repeat to so_runs (api.cpp build_blob); with
+    """The plans send short patterns and patterns whose symbols repeat to so_runs (plan.cpp build_blob); with
     smartgpu_tune(0,1) every algorithm counts on its own kernel — hor_scan, bm_scan, bndm_scan, bndml_scan,
     hor_scan_bp — for every fuzz vector (small alphabets, periodic texts, m = 1 .. 300), and with (0,3) the skip
     algorithms count on the packed matcher."""
@@ -352,7 +352,7 @@ def test_small_alphabets_dense_matches(oracle):
 
 def test_two_symbol_patterns_count_on_shift_or_runs_and_on_their_own_kernels(oracle):
     """A pattern of 16+ bytes over two or three symbols is counted by so_runs whatever the algorithm
-    (api.cpp build_blob / launch.hip launch_scan); tune(0,1) keeps every algorithm on its own kernel.
+    (plan.cpp build_blob / launch.hip launch_scan); tune(0,1) keeps every algorithm on its own kernel.
     Both must give the oracle's count; patterns over larger alphabets are not rerouted."""
     from smart_amd import engine
     own = ("kmp", "kr")

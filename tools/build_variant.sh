@@ -13,6 +13,7 @@ for u in k_hor k_horm k_horg k_planes k_bm k_bmg k_bndm k_bndmx k_so k_kmp k_pac
 done
 /opt/rocm/bin/hipcc $FLAGS "$@" --offload-arch=gfx950 -c -o $T/api.o $D/api.cpp &
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC "$@" -c -o $T/tables.o $D/tables.cpp &
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC "$@" -c -o $T/plan.o $D/plan.cpp &
 wait
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $D/libsmartgpu_$NAME.so $T/*.o -ldl
 rm -rf $T

@@ -41,7 +41,7 @@ M = 32
 
 
 def streams(P):
-    """A pattern whose symbols do not repeat (api.cpp build_blob: ordered pairs of equal symbols against 1/48 of all
+    """A pattern whose symbols do not repeat (plan.cpp build_blob: ordered pairs of equal symbols against 1/48 of all
     pairs): its launch is one the queue counts, not a rider."""
     counts = {}
     for b in P.tolist():

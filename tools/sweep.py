@@ -61,7 +61,7 @@ def main():
             if m < smart_amd.MIN_M.get(algo, 1):  # the algorithm does not apply (raita.c:37, hash3.c:31, ...)
                 continue
             plans = [Plan(algo, p) for p in pats]
-            kernels = sorted({pl.kernel_name for pl in plans})  # the plan's choice (api.cpp build_blob), per pattern
+            kernels = sorted({pl.kernel_name for pl in plans})  # the plan's choice (plan.cpp build_blob), per pattern
             plans[0].launch(text, slot=1)  # warm-up
             plans[0].result(1)
             for pl in plans:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Render tools/sweep.py logs as the markdown tables of DESIGN.md §8: python tools/tables.py <log> [...]
-A cell whose plans did not run on the algorithm's own kernel (api.cpp build_blob rerouted the pattern) carries a
+A cell whose plans did not run on the algorithm's own kernel (plan.cpp build_blob rerouted the pattern) carries a
 mark: p = packed_scan, s = so_runs; mixed = some of the cell's patterns each."""
 import re
 import sys
