@@ -174,6 +174,31 @@ void smartgpu_last_times(double *pre_ms, double *run_ms);
  * list is complete), SMARTGPU_ERR_NOMEM when it is not (retry with cap >= *count). */
 int smartgpu_find64(const uint8_t *P, uint32_t m, const smartgpu_text *text, uint64_t off, uint64_t n,
                     uint64_t *positions, uint64_t cap, uint64_t *count);
+/* The positions of a whole PATTERN SET of one length, in shared passes over the text: smartgpu_pfind_batch64's contract
+ * (below), asked of a smartgpu_text.  The positions of pattern k are positions[starts[k] .. starts[k+1]), each slice
+ * ascending and relative to text byte 0: every s in [off, off+n-m] with T[s..s+m) == P[k], overlapping occurrences
+ * listed.  starts has K+1 entries, starts[0] = 0, starts[K] = the total.  starts[K] > cap: SMARTGPU_ERR_NOMEM with
+ * starts completely filled — every count and the room a retry needs.  cap == 0 with positions == NULL is a count.
+ * Nothing behind positions[cap] is ever written.  m > n leaves all counts 0 without a launch.  The same pattern twice
+ * in a set gets two equal slices.
+ * One kernel, hor_multi_find (smart_amd/csrc/k_hormf.hip): hor_multi_scan's skip table, walk and candidate chains
+ * with an output stage.  A pass decides 208 patterns up to m = 16, 124 up to m = 32, 89 up to m = 48, 69 up to
+ * m = 64 and 56 beyond in ONE read of the text, and it counts and lists in the same read, so starts is exact even
+ * when entries were dropped; the passes of a call run back to back, with one synchronisation and one copy to the host.
+ * m = 1 and m = 2 have no two-byte gram to skip on: they are answered by K runs of smartgpu_find64 into consecutive
+ * slices, under the same contract.
+ * SMARTGPU_ERR_ARG, each decided before any HIP call: the argument checks of smartgpu_search_batch64; starts == NULL;
+ * positions == NULL with cap > 0; a NULL pattern; K > 262144 (2^18: an entry keeps 18 bits for the pattern);
+ * K > SMARTGPU_FIND_BATCH_STAGING / (bytes staged per pattern) — the patterns travel through the device's pinned
+ * staging buffer, 16 * ceil(min(m, 65) / 16) bytes of a pattern's end and, from m = 18 on, 16 * ceil(m / 16) of the
+ * whole pattern: 87381 patterns at m = 300, 8035 at m = 4096, no bound below 2^18 up to m = 64; off + n >= 2^46 (an
+ * entry keeps 46 bits for the position).  What the device wrote is refused with SMARTGPU_ERR_HIP, never reported,
+ * where its cursor and its counts disagree or the entries are not the counted occurrences.
+ * NOT offered: patterns of several lengths in one call (smart_amd.find_batch groups them by length), MultiText shards.
+ * Measured with tools/find_batch_probe.py (profiles/coalesce/RESULTS.md, "Positions of a pattern set"). */
+#define SMARTGPU_FIND_BATCH_STAGING (32u << 20)
+int smartgpu_find_batch64(const uint8_t *const *P, uint32_t m, uint32_t K, const smartgpu_text *text,
+                          uint64_t off, uint64_t n, uint64_t *positions, uint64_t cap, uint64_t *starts);
 
 /* ---- plans: preprocess once, launch many (harness hot loop, smart.c:312-345) ---- */
 /* Builds the algorithm's tables on the host and places them in HBM of `device`. */

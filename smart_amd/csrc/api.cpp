@@ -25,6 +25,8 @@
 
 #include "kernels.hpp"
 #include "multi.hpp"
+#include "multi_find.hpp"
+#include "multi_find_host.hpp"
 #include "pedit.hpp"
 #include "peditl.hpp"
 #include "tedit.hpp"
@@ -110,7 +112,7 @@ DeviceCtx* device_ctx(int device)
         d.num_cus = prop.multiProcessorCount;
         d.device = device;
         HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking), return nullptr);
-        d.pinned_bytes = 32u << 20;
+        d.pinned_bytes = sg::kStagingBytes;  // (multi_find.hpp: find_batch_max counts on it)
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d.pinned), d.pinned_bytes, hipHostMallocDefault),
                 return nullptr);
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d.pinned_count), 64, hipHostMallocDefault),
@@ -668,6 +670,7 @@ hipError_t queue_launch(const DeviceCtx* d, int algo, const sg::PlanWords& words
 
 namespace sg {
 hipError_t (*g_hor_multi)(const MultiArgs&, int, hipStream_t) = nullptr;  // multi.hpp: set by k_horm.hip where that unit is linked
+hipError_t (*g_hor_multi_find)(const MultiFindArgs&, int, hipStream_t) = nullptr;  // multi_find.hpp: set by k_hormf.hip where that unit is linked
 // sample.hpp: set by k_hors.hip where that unit is linked
 hipError_t (*g_hor_sample)(const MultiArgs&, const uint32_t*, int, int, hipStream_t) = nullptr;
 hipError_t (*g_sample_build)(const uint8_t*, uint64_t, uint32_t*, int, hipStream_t) = nullptr;
@@ -3009,6 +3012,136 @@ int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, cons
             r = SMARTGPU_ERR_HIP;
         } else if (!sg::order_spans(positions + starts[k], counts[k], off, off + n - m)) {
             set_error("planes_find: pattern %u: the positions are not ascending spans of %llu start positions", k, (unsigned long long)sg::kFindSpan);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (own) (void)hipFree(out);
+    return r;
+}
+
+/* ---- occurrence positions of a pattern set on a BYTE text (k_hormf.hip: hor_multi_find) ----------------------------- */
+// smartgpu_pfind_batch64's contract, asked of a smartgpu_text.  The set goes through the staging buffer into the arena
+// once (rows, and whole patterns where a window is completed in memory); its passes, find_width(m) patterns each, run
+// back to back on the device's stream into ONE entry buffer behind ONE cursor, counting and listing in the same read of
+// the text; one synchronisation, one copy_positions, and multi_find_host.hpp's order_find_batch sorts the entries into
+// the patterns' slices.  What the device wrote is refused, never reported, where its two tallies disagree.
+static_assert(sg::kFindBatchIndexBits == sg::kFindBatchShift, "order_find_batch strips what hor_multi_find adds");
+static_assert(sg::kStagingBytes == SMARTGPU_FIND_BATCH_STAGING, "the bound the header documents");
+
+int smartgpu_find_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_text* text, uint64_t off, uint64_t n,
+                          uint64_t* positions, uint64_t cap, uint64_t* starts)
+{
+    if (!P || K < 1 || !starts) { set_error("find_batch: P/starts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
+    if (K > sg::kFindBatchMaxK) { set_error("find_batch: %u patterns in one set (at most %u: an entry keeps 18 bits for the pattern)", K, sg::kFindBatchMaxK); return SMARTGPU_ERR_ARG; }
+    const int rc = check_search_args(SMARTGPU_EPSM, P[0], m, text, off, n);
+    if (rc != SMARTGPU_OK) return rc;
+    if (cap && !positions) { set_error("find_batch: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
+    for (uint32_t k = 0; k < K; ++k)
+        if (!P[k]) { set_error("find_batch: pattern %u is NULL", k); return SMARTGPU_ERR_ARG; }
+    if (K > sg::find_batch_max(m)) {
+        set_error("find_batch: %u patterns of length %u, at most %u per call (%u bytes per pattern in the staging buffer of %zu)", K, m, sg::find_batch_max(m),
+                  sg::find_batch_bytes(m), sg::kStagingBytes);
+        return SMARTGPU_ERR_ARG;
+    }
+    if (off + n >= sg::kFindBatchMaxEnd) {
+        set_error("find_batch: the range ends at byte %llu, it must end below %llu (an entry keeps 46 bits for the position)", (unsigned long long)(off + n),
+                  (unsigned long long)sg::kFindBatchMaxEnd);
+        return SMARTGPU_ERR_ARG;
+    }
+    for (uint32_t k = 0; k <= K; ++k) starts[k] = 0;
+    if (m > n) return SMARTGPU_OK;  // no window fits: no launch
+    if (m < 3) {
+        // no gram, no previous byte: K runs of the single-pattern find into consecutive slices; past the room they only count
+        for (uint32_t k = 0; k < K; ++k) {
+            const uint64_t room = cap > starts[k] ? cap - starts[k] : 0;
+            uint64_t c = 0;
+            const int r = smartgpu_find64(P[k], m, text, off, n, room ? positions + starts[k] : nullptr, room, &c);
+            if (r != SMARTGPU_OK && r != SMARTGPU_ERR_NOMEM) return r;
+            if (r == SMARTGPU_ERR_NOMEM && c <= room) return r;  // the device's memory, not the caller's room
+            starts[k + 1] = starts[k] + c;
+        }
+        if (starts[K] > cap) { set_error("find_batch: %llu occurrences, room for %llu", (unsigned long long)starts[K], (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
+        return SMARTGPU_OK;
+    }
+    if (!sg::g_hor_multi_find) { set_error("find_batch: this program holds no hor_multi_find kernel (k_hormf.hip is not linked)"); return SMARTGPU_ERR_HIP; }
+    DeviceCtx* d = device_ctx_flushed(text->device);
+    if (!d) return SMARTGPU_ERR_HIP;
+    const uint32_t stride = sg::tail_stride(m), pitch = sg::find_pitch(m);
+    const bool in_memory = sg::find_in_memory(m);
+    const size_t rows_bytes = static_cast<size_t>(K) * stride, staged = static_cast<size_t>(K) * sg::find_batch_bytes(m);
+    if (staged > d->pinned_bytes) { set_error("find_batch: %u patterns exceed the staging buffer", K); return SMARTGPU_ERR_ARG; }
+    if (!batch_reserve(d, staged, static_cast<size_t>(K) + 1)) return SMARTGPU_ERR_NOMEM;
+    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
+    for (uint32_t k = 0; k < K; ++k) {
+        uint8_t row[sg::kTailRow];
+        sg::tail_fill(row, P[k], m);
+        std::memcpy(d->pinned + static_cast<size_t>(k) * stride, row, stride);
+        if (in_memory) {
+            uint8_t* whole = d->pinned + rows_bytes + static_cast<size_t>(k) * pitch;
+            std::memcpy(whole, P[k], m);
+            std::memset(whole + m, 0, pitch - m);
+        }
+    }
+    const uint64_t per = n - m + 1, bound = per * K;  // (K <= 2^18 and n < 2^46)
+    const uint64_t room = cap < bound ? cap : bound;
+    bool own = false;
+    unsigned long long* out = nullptr;
+    uint64_t room_got = room;
+    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
+    unsigned long long* const cursor = d->batch_counts + K;
+    bool ok = hipMemcpyAsync(d->arena, d->pinned, staged, hipMemcpyHostToDevice, d->stream) == hipSuccess &&
+              hipMemsetAsync(d->batch_counts, 0, (static_cast<size_t>(K) + 1) * 8, d->stream) == hipSuccess;
+    sg::MultiFindArgs a;
+    a.text = text->data();
+    a.s_begin = off;
+    a.s_end = off + per;
+    a.m = m;
+    a.halo = m - 1 < sg::kHaloMax ? m - 1 : sg::kHaloMax;
+    a.counts = d->batch_counts;
+    a.out = out;
+    a.cap = room_got;
+    a.cursor = cursor;
+    const uint32_t width = sg::find_width(m);
+    for (uint32_t base = 0; base < K && ok; base += width) {
+        a.base = base;
+        a.np = K - base < width ? K - base : width;
+        a.rows = d->arena + static_cast<size_t>(base) * stride;
+        a.pats = d->arena + rows_bytes + static_cast<size_t>(base) * pitch;
+        ok = sg::g_hor_multi_find(a, d->num_cus, d->stream) == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(d->pinned_counts, d->batch_counts, (static_cast<size_t>(K) + 1) * 8, hipMemcpyDeviceToHost, d->stream) == hipSuccess;
+    const bool synced = hipStreamSynchronize(d->stream) == hipSuccess;  // (also after a failure: nothing may still write to the buffers)
+    int r = SMARTGPU_OK;
+    uint64_t total = 0;
+    std::vector<uint64_t> counts(K);
+    if (!ok || !synced) {
+        set_error("find_batch: %s", hipGetErrorString(hipGetLastError()));
+        r = SMARTGPU_ERR_HIP;
+    } else {
+        // the two tallies of the kernel: every count within the start positions, and the cursor their sum
+        for (uint32_t k = 0; k < K && r == SMARTGPU_OK; ++k) {
+            counts[k] = d->pinned_counts[k];
+            if (counts[k] > per) { set_error("hor_multi_find: pattern %u: count %llu exceeds the %llu start positions", k, (unsigned long long)counts[k], (unsigned long long)per); r = SMARTGPU_ERR_HIP; }
+            total += counts[k];
+        }
+        if (r == SMARTGPU_OK && d->pinned_counts[K] != total) {
+            set_error("hor_multi_find: cursor %llu, the patterns' counts add up to %llu", d->pinned_counts[K], (unsigned long long)total);
+            r = SMARTGPU_ERR_HIP;
+        }
+    }
+    if (r == SMARTGPU_OK) {
+        for (uint32_t k = 0; k < K; ++k) starts[k + 1] = starts[k] + counts[k];
+        if (total > cap) {
+            set_error("find_batch: %llu occurrences, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+            r = SMARTGPU_ERR_NOMEM;
+        } else if (total > room_got) {
+            set_error("find_batch: %llu occurrences, room for %llu, but the device has no memory for %llu entries", (unsigned long long)total, (unsigned long long)cap, (unsigned long long)room);
+            r = SMARTGPU_ERR_NOMEM;
+        } else if (total && !copy_positions(d, positions, out, total)) {
+            set_error("find_batch: %s", hipGetErrorString(hipGetLastError()));
+            r = SMARTGPU_ERR_HIP;
+        } else if (total && !sg::order_find_batch(positions, total, K, counts.data(), off, off + n - m, starts)) {
+            set_error("hor_multi_find: the entries are not the counted occurrences of %u patterns at distinct starts in [%llu, %llu]", K, (unsigned long long)off, (unsigned long long)(off + n - m));
             r = SMARTGPU_ERR_HIP;
         }
     }

@@ -119,6 +119,7 @@ def _load(path):
         "smartgpu_search_batch64_each": (i32, [i32, vp, u32, u32, vp, u64, u64, vp, vp, vp, C.POINTER(C.c_double)]),
         "smartgpu_msearch_batch64": (i32, [i32, vp, u32, u32, vp, i32, vp, vp, C.POINTER(C.c_double)]),
         "smartgpu_find64": (i32, [vp, u32, vp, u64, u64, vp, u64, C.POINTER(u64)]),
+        "smartgpu_find_batch64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp]),
         "smartgpu_last_times": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_plan_create": (vp, [i32, vp, u32, i32]),
         "smartgpu_plan_free": (None, [vp]),
@@ -859,6 +860,72 @@ def find(P, text, off=0, n=None, cap=1 << 20):
     if rc != 0:
         raise _err("find64 rc=%d" % rc)
     return out[:c.value].copy(), int(c.value)
+
+
+FIND_BATCH_MAX_K = 1 << 18          # multi_find.hpp: kFindBatchMaxK
+FIND_BATCH_STAGING = 32 << 20       # include/smartgpu.h: SMARTGPU_FIND_BATCH_STAGING
+
+
+def find_width(m):
+    """Patterns of length m that one pass of hor_multi_find decides (multi_find.hpp: find_width): what the LDS of a
+    workgroup holds beside the table, the stage and the tile when four are resident on a CU."""
+    stride = (min(m, 65) + 15) // 16 * 16
+    return {16: 208, 32: 124, 48: 89, 64: 69, 80: 56}[stride]
+
+
+def find_batch_max(m):
+    """The most patterns of length m that one smartgpu_find_batch64 call takes (multi_find.hpp: find_batch_max)."""
+    stride = (min(m, 65) + 15) // 16 * 16
+    staged = stride + ((m + 15) // 16 * 16 if m - 1 > 16 else 0)
+    return min(FIND_BATCH_STAGING // staged, FIND_BATCH_MAX_K)
+
+
+def _find_batch_one(pats, text, off, n, cap):
+    """One smartgpu_find_batch64 call: (list of len(pats) ascending uint64 arrays or None, counts) for patterns of ONE
+    length; None when their occurrences are more than `cap`."""
+    pats, ptrs, m = _pattern_set(pats)
+    K = len(pats)
+    out = np.empty(max(cap, 1), dtype=np.uint64)
+    starts = np.zeros(K + 1, dtype=np.uint64)
+    rc = lib().smartgpu_find_batch64(C.cast(ptrs, C.c_void_p), m, K, text._h, off, n, out.ctypes.data if cap else None, cap,
+                                     starts.ctypes.data)
+    counts = np.diff(starts)
+    if rc == -5 and int(starts[K]) > cap:
+        return None, counts
+    if rc != 0:
+        raise _err("find_batch64 rc=%d" % rc)
+    return [out[int(starts[k]):int(starts[k + 1])].copy() for k in range(K)], counts
+
+
+def find_batch(patterns, text, off=0, n=None, cap=1 << 20):
+    """(list of K ascending uint64 arrays, counts): the start offsets (relative to text byte 0) of every pattern of a set
+    in text[off..off+n), found in shared passes over the text (smartgpu_find_batch64), and their numbers, in the caller's
+    order.  `cap` is the room for the positions of ALL patterns; when they are more, the list is None and the counts say
+    how much room a retry needs.  Patterns of several lengths are grouped by length, one call per length."""
+    pats = [_u8(p) for p in patterns]
+    if not pats:
+        raise SmartGpuError("find_batch: an empty pattern set")
+    if n is None:
+        n = len(text) - off
+    by_len = {}
+    for i, p in enumerate(pats):
+        by_len.setdefault(len(p), []).append(i)
+    lists = [None] * len(pats)
+    counts = np.zeros(len(pats), dtype=np.uint64)
+    left = cap  # None: the room is used up, the remaining lengths only count
+    for m in sorted(by_len):
+        idx = by_len[m]
+        got, c = _find_batch_one([pats[i] for i in idx], text, off, n, left if left is not None else 0)
+        counts[idx] = c
+        if left is not None and got is not None:
+            for i, g in zip(idx, got):
+                lists[i] = g
+            left -= int(c.sum())
+        else:
+            left = None
+    if left is None and int(counts.sum()) > cap:
+        return None, counts
+    return lists, counts
 
 
 def _classes(classes):

@@ -11,6 +11,7 @@ COMMON = ("dev_common.hpp", "kernels.hpp", "launch_common.hpp")
 UNITS = {
     "k_hor": ("k_hor.hip",),
     "k_horm": ("k_horm.hip", "multi.hpp"),
+    "k_hormf": ("k_hormf.hip", "multi_find.hpp", "multi.hpp"),
     "k_hors": ("k_hors.hip", "sample.hpp", "multi.hpp"),
     "k_horg": ("k_horg.hip", "gram_skip.hpp"),
     "k_bmg": ("k_bmg.hip", "gram_skip.hpp"),
@@ -31,7 +32,7 @@ UNITS = {
     "k_talign": ("k_talign.hip", "talign.hpp", "talign_host.hpp", "tedit.hpp", "tedit_host.hpp", "edit_align.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {
-    "hor_scan": "k_hor", "hor_multi_scan": "k_horm", "hor_sample_scan": "k_hors", "text_sample_build": "k_hors","hor_scan_bp": "k_hor", "hor_scan_gram": "k_horg", "bm_scan_gram": "k_bmg", "bm_scan": "k_bm", "bndm_scan": "k_bndm", "sbndm_scan": "k_bndmx",
+    "hor_scan": "k_hor", "hor_multi_scan": "k_horm", "hor_multi_find": "k_hormf", "hor_sample_scan": "k_hors", "text_sample_build": "k_hors","hor_scan_bp": "k_hor", "hor_scan_gram": "k_horg", "bm_scan_gram": "k_bmg", "bm_scan": "k_bm", "bndm_scan": "k_bndm", "sbndm_scan": "k_bndmx",
     "bndml_scan": "k_bndmx", "so_runs": "k_so", "kmp_runs": "k_kmp", "packed_scan": "k_packed", "packed_find": "k_packed",
     "generate_text": "k_util", "tile_fill": "k_util", "text_alphabet": "k_util", "text_histogram": "k_util", "probe_read": "k_util",
     "planes_pack": "k_planes", "planes_scan": "k_planes", "planes_find": "k_planes",

@@ -6,7 +6,8 @@ so that two builds can be compared kernel by kernel — "did moving this kernel 
 its code?" — without a GPU.
 
     python tools/asm_stats.py a.s [b.s ...]            one table per file
-    python tools/asm_stats.py --diff old.s new1.s new2.s ...   kernels of the new files against the old one
+    python tools/asm_stats.py --diff old.s new1.s new2.s ...   kernels of the new files against the old one (several units
+                                                               of the old build: concatenate their files), and a summary line
 """
 import hashlib
 import re
@@ -75,15 +76,20 @@ def main():
             new.update(parse(p))
         print("%-58s %7s %7s %6s %6s %5s %5s %5s %5s %4s %4s %4s %4s %4s %4s  %s"
               % ("kernel", "insts", "new", "bytes", "new", "vgpr", "new", "sgpr", "new", "scr", "new", "lds", "new", "occ", "new", "code"))
+        tally = {"same": 0, "differs": 0, "new": 0, "old": 0}
         for k in sorted(set(old) | set(new)):
             o, n = old.get(k), new.get(k)
             if o is None or n is None:
                 print("%-58s %s" % (k[:58], "only in the NEW build" if o is None else "only in the OLD build"))
+                tally["new" if o is None else "old"] += 1
                 continue
             same = "same" if o["hash"] == n["hash"] else "differs"
+            tally[same] += 1
             print("%-58s %7d %7d %6s %6s %5s %5s %5s %5s %4s %4s %4s %4s %4s %4s  %s"
                   % (k[:58], o["insts"], n["insts"], o["bytes"], n["bytes"], o["vgpr"], n["vgpr"], o["sgprs"], n["sgprs"], o["scratch"], n["scratch"],
                      o["lds"], n["lds"], o["occ"], n["occ"], same))
+        print("%d kernels of the old build: %d same, %d differ, %d only in the old build; %d only in the new build"
+              % (len(old), tally["same"], tally["differs"], tally["old"], tally["new"]))
         return
     for p in args:
         print("==", p)
