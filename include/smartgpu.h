@@ -697,7 +697,8 @@ int smartgpu_pfind_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, uin
  * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / classes == NULL, m outside [1, SMARTGPU_EDIT_MAXM] (the
  * message names the limit), k > SMARTGPU_PMIS_MAX, a NULL text, a range outside the text, count == NULL, ends == NULL with
  * cap > 0.  The calls are synchronous: launches pending in the coalescing queue are sent first, and they never enter it.
- * NOT offered: m > 64 and k > 7, a batch call, MultiText shards and the `smart` harness.
+ * NOT offered: m > 64 and k > 7 (smartgpu_search_editl64 / smartgpu_find_editl64 below: up to 256 bytes and 31 edits), a batch
+ * call, MultiText shards and the `smart` harness.
  * (Start positions and alignments: smartgpu_align_edit64 below.  Substitutions only, no shifts: smartgpu_search_mis64 below.)
  * MEASURED on an MI355X, 1 GiB texts, m = 8, 20, 32, 33, 64, k = 0, 3, 7 (profiles/tedit/RESULTS.md; tools/tedit_probe.py; kernel
  * times from a kernel trace, call times by the host clock, medians of 5 / 7, run-to-run spread at most 3 % of the median but for the
@@ -723,6 +724,61 @@ int smartgpu_search_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t 
                                    uint64_t *count, double *pre_ms, double *run_ms);
 int smartgpu_find_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
                                  uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+/* EDIT DISTANCE ON A BYTE TEXT, LONG PATTERNS: smartgpu_search_edit64 / smartgpu_find_edit64 and their classes forms for
+ * 1 <= m <= SMARTGPU_EDITL_MAXM = 256 bytes and 0 <= k <= SMARTGPU_EDITL_MAXK = 31 edits — a sentence or a log line with typos,
+ * a protein domain of 100-150 residues, a 120-byte record, an English phrase at an error rate of 5-10 %.  The contract is that
+ * of those calls, word for word, with only the bounds widened: the calls count and list END positions e in [off, off+n) with
+ * D(e) <= k, D the last row of Sellers' programme on the range alone; ends are ascending and relative to text byte 0,
+ * distances[i] = D(ends[i]); m > n is legal, only n + k < m is "count 0, no launch"; k >= m is legal; a byte the pattern does
+ * not hold or an empty row accepts nothing, a full row everything; cap / count / SMARTGPU_ERR_NOMEM and distances == NULL
+ * behave the same, cap == 0 with NULL buffers is a count.  classes: 32 bytes per position, smartgpu_search_edit_classes64's
+ * rows.  Lengths up to 64 and k up to 7 are legal here too: the answers are those of the calls above, from a second,
+ * independent kernel.
+ * flags: 0, or SMARTGPU_EDITL_ALL_BLOCKS (bit 0): compute every block of every column, without the cut-off.  The answers are the
+ * same; the bit exists for the cross-check and the measurement.  Any other bit is SMARTGPU_ERR_ARG.
+ * One pass over the text (text_editl_scan, text_editl_find; smart_amd/csrc/k_teditl.hip): the recurrence of
+ * smartgpu_psearch_editl64 — BLOCKS of 32 pattern rows with Ukkonen's cut-off, the number of active blocks shared by the 64
+ * lanes of a wave — fed as smartgpu_search_edit64's kernels are fed: the pattern is 256 masks of 2, 4 or 8 dwords in LDS, one
+ * dword read per active block, and the text comes into LDS by coalesced loads.  A lane owns 512 consecutive end positions and
+ * walks them, and up to m + k <= 287 bytes before them without counting, in pieces of 128 bytes.  The find's entries are sorted
+ * on the host.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written: P / classes == NULL, m outside [1, SMARTGPU_EDITL_MAXM], k >
+ * SMARTGPU_EDITL_MAXK (the messages name the limits), a flags bit other than SMARTGPU_EDITL_ALL_BLOCKS, a NULL text, a range
+ * outside the text, count == NULL, ends == NULL with cap > 0.  The calls are synchronous: launches pending in the coalescing
+ * queue are sent first, and they never enter it.
+ * NOT offered: start positions and ALIGNMENTS of long patterns on a byte text (smartgpu_align_edit64 stays at m <= 64, k <= 7),
+ * m > 256, k > 31, a batch call, MultiText shards, the `smart` harness.
+ * MEASURED on an MI355X, 1 GiB of rand128, English and rand4, m = 64, 65, 100, 150, 256, k = 0, 3, 7, 15, 31, the pattern cut
+ * from the text (profiles/tedit/RESULTS.md, "Long patterns"; tools/teditl_probe.py; kernel times from a kernel trace taken in a
+ * run of its own, medians of 5, run-to-run spread at most 2 % of the median; call times by the host clock, medians of 7, spread
+ * at most 4 %).  text_editl_scan at k <= 7, on the three texts alike: 1.59-1.68 ms at m = 64 (0.64-0.68 TB/s of text), 1.77-1.99 ms
+ * at m = 65, 100, 2.73-2.89 ms at m = 150, 3.15-3.42 ms at m = 256; at k = 15 1.66-3.51 ms on rand128 and English and 2.29-4.47 ms
+ * on rand4 (four values keep the second block active), at k = 31 2.35-5.19 ms; per call 1.63-5.20 ms.  THE CUT-OFF'S WORTH: with
+ * SMARTGPU_EDITL_ALL_BLOCKS the same cells take 1.94-7.96 ms; all blocks / cut-off is 2.26-2.45 at m = 256, k <= 7 (the packed
+ * kernel's 3.6 is not reached), 1.71-1.82 at m = 150, 1.65-1.75 at m = 100, 1.39-1.48 at m = 65, 1.17-1.24 at m = 64, 1.53-1.74 at
+ * m = 256, k = 31, outside the spread in all of these; where every block is active anyway the cut-off form is the SLOWER one: all
+ * blocks / cut-off is 0.85-0.87 (m = 64 at k = 31, and at k = 15 on rand4) and 0.89-0.99 (m = 65 at k = 31); inside the spread: m = 65 at k = 31 on rand128,
+ * m = 65 at k = 15 on rand4, per call also m = 65, k = 31 on English and m = 100, k = 31 on rand4.  AGAINST smartgpu_search_edit64
+ * (text_edit_scan, unchanged) at m = 64, k = 0, 3, 7, same pattern: 1.12-1.16 x its kernel time on all three texts, outside the
+ * spread: on the length both can do the two-dword kernel is the faster one.  AGAINST smartgpu_psearch_editl64 (planes_editl_scan)
+ * on the same rand4 bytes packed, same P and k: 1.08-1.12 x its kernel time for m <= 100 at k <= 7, 1.27-1.29 x for m = 150, 256
+ * at k <= 7, 1.06-1.21 x at k = 15 (m >= 65), 1.08 x at m >= 150, k = 31, 0.95-0.96 x at m = 65, 100, k = 31, 1.00 x (inside the
+ * spread) at m = 64, k = 15, 31: bytes cost 8-29 % here, where the warm-up pieces are parked whole for every lane.  The step from
+ * m = 100 to m = 150 (1.45 x, for 1.08 x the bytes walked) coincides with the 8-dword kernel, which runs 3 workgroups per CU
+ * instead of 4; the two were not separated.
+ * NOT measured: the occupancy choice (4 / 4 / 3 workgroups per CU is what the LDS holds), other run and piece lengths, a
+ * prefetch of the next piece, the find form's speed and the host ordering's share in it, the classes calls, texts beyond 1 GiB. */
+#define SMARTGPU_EDITL_MAXM 256
+#define SMARTGPU_EDITL_MAXK 31
+#define SMARTGPU_EDITL_ALL_BLOCKS 1u   /* flags bit 0 */
+int smartgpu_search_editl64(const uint8_t *P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text *text,
+                            uint64_t off, uint64_t n, uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_find_editl64(const uint8_t *P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text *text,
+                          uint64_t off, uint64_t n, uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
+int smartgpu_search_editl_classes64(const uint8_t *classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text *text,
+                                    uint64_t off, uint64_t n, uint64_t *count, double *pre_ms, double *run_ms);
+int smartgpu_find_editl_classes64(const uint8_t *classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text *text,
+                                  uint64_t off, uint64_t n, uint64_t *ends, uint8_t *distances, uint64_t cap, uint64_t *count);
 /* START POSITIONS and ALIGNMENTS on a byte text: smartgpu_palign_edit64 / smartgpu_palign_sets_edit64 asked of a
  * smartgpu_text — which bytes an end position e reported by smartgpu_find_edit64 / smartgpu_find_edit_classes64 stands for,
  * and which of them were substituted, added or skipped.  The contract is that of smartgpu_palign_edit64, word for word,

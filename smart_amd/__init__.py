@@ -11,4 +11,5 @@ from .engine import (ALGOS, MIN_M, MultiText, PackedText, Plan, SmartGpuError, T
                      ptext_layout, ptext_layout8, search,
                      align_edit, align_edit_classes, find_edit_align, find_edit_classes_align,
                      byte_classes, find_edit, find_edit_classes, search_edit, search_edit_classes,
+                     find_editl, find_editl_classes, search_editl, search_editl_classes,
                      find_mis, find_mis_classes, search_mis, search_mis_classes, search_batch, search_host, version)

@@ -30,6 +30,7 @@
 #include "pedit.hpp"
 #include "peditl.hpp"
 #include "tedit.hpp"
+#include "teditl.hpp"
 #include "tmis.hpp"
 #include "palign.hpp"
 #include "talign.hpp"
@@ -685,6 +686,9 @@ hipError_t (*g_planes_editl_find)(const PlaneEditlArgs&, unsigned long long*, un
 // tedit.hpp: set by k_tedit.hip where that unit is linked
 hipError_t (*g_text_edit_scan)(const TextEditArgs&, int, hipStream_t) = nullptr;
 hipError_t (*g_text_edit_find)(const TextEditArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
+// teditl.hpp: set by k_teditl.hip where that unit is linked
+hipError_t (*g_text_editl_scan)(const TextEditlArgs&, int, hipStream_t) = nullptr;
+hipError_t (*g_text_editl_find)(const TextEditlArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
 // tmis.hpp: set by k_tmis.hip where that unit is linked
 hipError_t (*g_text_mis_scan)(const TextMisArgs&, int, hipStream_t) = nullptr;
 hipError_t (*g_text_mis_find)(const TextMisArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
@@ -2641,6 +2645,77 @@ int peditl_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uin
     return rc;
 }
 
+// Edit distance on BYTE texts, long patterns (teditl.hpp): tedit_count / tedit_find with peditl's bounds, its switch and its
+// unordered entries.  check_text_args' checks, in its order and style, with the wider bounds and the flags check.
+int check_teditl_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text,
+                      uint64_t off, uint64_t n, const uint64_t* count)
+{
+    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
+    if (m < 1 || m > SMARTGPU_EDITL_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_EDITL_MAXM); return SMARTGPU_ERR_ARG; }
+    if (k > SMARTGPU_EDITL_MAXK) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_EDITL_MAXK); return SMARTGPU_ERR_ARG; }
+    if (flags & ~SMARTGPU_EDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_EDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_EDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
+    if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
+    if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
+    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
+    return SMARTGPU_OK;
+}
+
+// The 256 masks, word-major (teditl_host.hpp: 2, 4 or 8 KiB), through the staging buffer into the arena, as text_table_stage
+// sends the short patterns' table.
+constexpr size_t kTEditlArena = sizeof(uint32_t) * 256 * sg::kTEditlWords;
+bool teditl_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
+{
+    uint32_t peq[256][sg::kTEditlWords];
+    if (classes) sg::editl_peq_classes(pat, m, peq); else sg::editl_peq_bytes(pat, m, peq);
+    const uint32_t words = m <= 64 ? 2u : m <= 128 ? 4u : 8u;  // the kernels' WORDS (k_teditl.hip)
+    sg::editl_peq_table(peq, words, reinterpret_cast<uint32_t*>(d->pinned));
+    *dev = reinterpret_cast<const uint32_t*>(d->arena);
+    return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+}
+
+int teditl_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
+                 uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
+{
+    const int rc = check_teditl_args(call, classes ? "classes" : "P", pat, m, k, flags, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
+    if (!sg::g_text_editl_scan) { set_error("%s: this program holds no text_editl_scan kernel (k_teditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    sg::TextEditlArgs a;
+    text_head(a, text, m, k, off, n);
+    a.all_blocks = flags & SMARTGPU_EDITL_ALL_BLOCKS;
+    return count_run({call, "text_editl_scan", "end positions", "entries"}, text->device, kTEditlArena, n,
+                     [&](DeviceCtx* d) { return teditl_stage(d, pat, classes, m, &a.peq); },
+                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_editl_scan(a, d->num_cus, d->stream); },
+                     count, pre_ms, run_ms);
+}
+
+int teditl_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
+                uint64_t n, uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
+    int rc = check_teditl_args(call, classes ? "classes" : "P", pat, m, k, flags, text, off, n, count);
+    if (rc != SMARTGPU_OK) return rc;
+    if (n + k < m) {
+        *count = 0;
+        return SMARTGPU_OK;
+    }
+    if (!sg::g_text_editl_find) { set_error("%s: this program holds no text_editl_find kernel (k_teditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
+    sg::TextEditlArgs a;
+    text_head(a, text, m, k, off, n);
+    a.all_blocks = flags & SMARTGPU_EDITL_ALL_BLOCKS;
+    rc = find_run({call, "text_editl_find", "end positions", "entries"}, text->device, kTEditlArena, n,
+                  [&](DeviceCtx* d) { return teditl_stage(d, pat, classes, m, &a.peq); },
+                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_editl_find(a, out, room, d->num_cus, d->stream); },
+                  [&](uint64_t* e, uint64_t total) {
+                      if (sg::order_editl(e, total, off, off + n - 1, k, sg::kTEditlShift)) return true;
+                      set_error("text_editl_find: the entries are not distinct end positions of the range with distances <= %u", k);
+                      return false;
+                  },
+                  ends, cap, count);
+    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count, sg::kTEditlShift);
+    return rc;
+}
+
 // ---- starts and alignments of edit-distance occurrences (palign.hpp): a list of END positions in, one lane each ----
 
 // copy_positions the other way: the caller's (pageable) end positions to the device through the pinned staging buffer
@@ -3312,6 +3387,31 @@ int smartgpu_find_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k,
                                  uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     return tedit_find("find_edit_classes64", classes, true, m, k, text, off, n, ends, distances, cap, count);
+}
+
+/* ---- edit distance on byte texts, long patterns: m <= 256, k <= 31 (teditl.hpp, k_teditl.hip) --------------------------- */
+int smartgpu_search_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off, uint64_t n,
+                            uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return teditl_count("search_editl64", P, false, m, k, flags, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_find_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off, uint64_t n,
+                          uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return teditl_find("find_editl64", P, false, m, k, flags, text, off, n, ends, distances, cap, count);
+}
+
+int smartgpu_search_editl_classes64(const uint8_t* classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
+                                    uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
+{
+    return teditl_count("search_editl_classes64", classes, true, m, k, flags, text, off, n, count, pre_ms, run_ms);
+}
+
+int smartgpu_find_editl_classes64(const uint8_t* classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
+                                  uint64_t n, uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
+{
+    return teditl_find("find_editl_classes64", classes, true, m, k, flags, text, off, n, ends, distances, cap, count);
 }
 
 /* ---- mismatches on byte texts: smartgpu_psearch_mis64's question of a smartgpu_text (tmis.hpp, k_tmis.hip) --------------- */

@@ -184,6 +184,10 @@ def _load(path):
         "smartgpu_find_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_search_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_find_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_search_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_find_editl64": (i32, [vp, u32, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
+        "smartgpu_search_editl_classes64": (i32, [vp, u32, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "smartgpu_find_editl_classes64": (i32, [vp, u32, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_search_mis64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "smartgpu_find_mis64": (i32, [vp, u32, u32, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]),
         "smartgpu_search_mis_classes64": (i32, [vp, u32, u32, vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -950,23 +954,23 @@ def byte_classes(P, ignore_case=False):
     return rows
 
 
-def _tedit_count(name, pat, m, text, k, off, n):
+def _tedit_count(name, pat, m, text, k, off, n, *flags):
     if n is None:
         n = len(text) - off
     c = C.c_uint64(0)
-    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, text._h, off, n, C.byref(c), None, None)
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, *flags, text._h, off, n, C.byref(c), None, None)
     if rc != 0:
         raise _err("%s rc=%d" % (name, rc))
     return int(c.value)
 
 
-def _tedit_find(name, pat, m, text, k, off, n, cap):
+def _tedit_find(name, pat, m, text, k, off, n, cap, *flags):
     if n is None:
         n = len(text) - off
     ends = np.empty(max(cap, 1), dtype=np.uint64)
     dist = np.empty(max(cap, 1), dtype=np.uint8)
     c = C.c_uint64(0)
-    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, text._h, off, n, ends.ctypes.data if cap else None,
+    rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, *flags, text._h, off, n, ends.ctypes.data if cap else None,
                                             dist.ctypes.data if cap else None, cap, C.byref(c))
     if rc != 0:  # (more than cap occurrences: SMARTGPU_ERR_NOMEM, the message holds the count a retry needs)
         raise _err("%s rc=%d" % (name, rc))
@@ -1000,6 +1004,32 @@ def find_edit_classes(classes, text, k, off=0, n=None, cap=1 << 20):
     """(ends, distances) of a pattern of byte classes (search_edit_classes), as find_edit returns them."""
     classes, m = _classes(classes)
     return _tedit_find("find_edit_classes64", classes, m, text, k, off, n, cap)
+
+
+def search_editl(P, text, k, off=0, n=None, all_blocks=False):
+    """search_edit for LONG patterns: 1 <= len(P) <= 256, 0 <= k <= 31 (smartgpu_search_editl64; Myers' recurrence in blocks of
+    32 rows with Ukkonen's cut-off).  The same contract, and for len(P) <= 64, k <= 7 the same answers.  all_blocks=True
+    computes every block of every column (SMARTGPU_EDITL_ALL_BLOCKS): the same answers, for cross-checks and measurements."""
+    P = _u8(P)
+    return _tedit_count("search_editl64", P, len(P), text, k, off, n, int(bool(all_blocks)))
+
+
+def find_editl(P, text, k, off=0, n=None, cap=1 << 20, all_blocks=False):
+    """(ends, distances) as find_edit returns them, for LONG patterns (search_editl; smartgpu_find_editl64)."""
+    P = _u8(P)
+    return _tedit_find("find_editl64", P, len(P), text, k, off, n, cap, int(bool(all_blocks)))
+
+
+def search_editl_classes(classes, text, k, off=0, n=None, all_blocks=False):
+    """search_editl for a pattern of byte CLASSES (search_edit_classes' rows; smartgpu_search_editl_classes64)."""
+    classes, m = _classes(classes)
+    return _tedit_count("search_editl_classes64", classes, m, text, k, off, n, int(bool(all_blocks)))
+
+
+def find_editl_classes(classes, text, k, off=0, n=None, cap=1 << 20, all_blocks=False):
+    """(ends, distances) of a pattern of byte classes, for LONG patterns (smartgpu_find_editl_classes64)."""
+    classes, m = _classes(classes)
+    return _tedit_find("find_editl_classes64", classes, m, text, k, off, n, cap, int(bool(all_blocks)))
 
 
 def search_mis(P, text, k, off=0, n=None):

@@ -28,6 +28,7 @@ UNITS = {
     "k_peditl": ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_palign": ("k_palign.hip", "palign.hpp", "edit_align.hpp", "pedit.hpp", "pedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_tedit": ("k_tedit.hip", "text_tile.hpp", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_teditl": ("k_teditl.hip", "teditl.hpp", "teditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_tmis": ("k_tmis.hip", "text_tile.hpp", "tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_talign": ("k_talign.hip", "talign.hpp", "talign_host.hpp", "tedit.hpp", "tedit_host.hpp", "edit_align.hpp", "edit_step.hpp", "planes.hpp"),
 }
@@ -44,6 +45,7 @@ KERNEL_UNIT = {
     "planes_editl_scan": "k_peditl", "planes_editl_find": "k_peditl",
     "planes_edit_align": "k_palign",
     "text_edit_scan": "k_tedit", "text_edit_find": "k_tedit",
+    "text_editl_scan": "k_teditl", "text_editl_find": "k_teditl",
     "text_edit_align": "k_talign",
     "text_mis_scan": "k_tmis", "text_mis_find": "k_tmis",
 }
