@@ -1,5 +1,7 @@
 // api.cpp — C ABI of libsmartgpu (include/smartgpu.h): text residency in HBM,
 // host-side preprocessing, launches, timing.  Compiled with hipcc as host code.
+// The calls on packed texts, the approximate matchers and the align calls are
+// match_calls.cpp; what the two units share is host_ctx.hpp, defined here.
 //
 // There is deliberately no CPU search path in this file or anywhere in the
 // library: if HIP is not usable every compute entry point fails.
@@ -23,21 +25,11 @@
 #include <string>
 #include <vector>
 
+#include "host_ctx.hpp"
 #include "kernels.hpp"
 #include "multi.hpp"
 #include "multi_find.hpp"
 #include "multi_find_host.hpp"
-#include "pedit.hpp"
-#include "peditl.hpp"
-#include "tedit.hpp"
-#include "teditl.hpp"
-#include "tmis.hpp"
-#include "palign.hpp"
-#include "talign.hpp"
-#include "planes.hpp"
-#include "planes_host.hpp"
-#include "planes3.hpp"
-#include "planes3_host.hpp"
 #include "plan.hpp"
 #include "route.hpp"
 #include "sample.hpp"
@@ -49,6 +41,11 @@ namespace {
 thread_local std::string g_error;
 thread_local double g_last_pre_ms = 0.0, g_last_run_ms = 0.0;
 
+}  // namespace
+
+// ---- what host_ctx.hpp declares for match_calls.cpp is defined outside the anonymous namespaces: here, and further down
+// device_ctx_flushed, batch_reserve, find_reserve and copy_positions ----
+
 void set_error(const char* fmt, ...)
 {
     char buf[512];
@@ -59,39 +56,51 @@ void set_error(const char* fmt, ...)
     g_error = buf;
 }
 
-#define HIP_TRY(expr, fail)                                                          \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            fail;                                                                    \
-        }                                                                            \
-    } while (0)
+// (host_ctx.hpp) what a count call answers, and how match_calls.cpp sets the times smartgpu_last_times reports
+int pcount_done(uint64_t c, double pre, double run, uint64_t* count, double* pre_ms, double* run_ms)
+{
+    g_last_pre_ms = pre;
+    g_last_run_ms = run;
+    if (count) *count = c;
+    if (pre_ms) *pre_ms = pre;
+    if (run_ms) *run_ms = run;
+    return SMARTGPU_OK;
+}
+
+double now_ms()
+{
+    using clk = std::chrono::steady_clock;  // CLOCK_MONOTONIC, as src/timer.h:43-55
+    return std::chrono::duration<double, std::milli>(clk::now().time_since_epoch()).count();
+}
+
+// `reps` passes of probe_read over [first, first + bytes) after one warm-up pass, timed by two events of its own: both
+// are released on every path
+int probe_read_ms(const DeviceCtx* d, const uint8_t* first, uint64_t bytes, unsigned long long* sink, int reps, double* ms_per_pass)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const auto timed = [&]() -> int {
+        HIP_TRY(hipEventCreate(&e0), return SMARTGPU_ERR_HIP);
+        HIP_TRY(hipEventCreate(&e1), return SMARTGPU_ERR_HIP);
+        sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);  // warm-up
+        hipEventRecord(e0, d->stream);
+        for (int i = 0; i < reps; ++i) sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);
+        hipEventRecord(e1, d->stream);
+        HIP_TRY(hipEventSynchronize(e1), return SMARTGPU_ERR_HIP);
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, e0, e1);
+        *ms_per_pass = ms / reps;
+        return SMARTGPU_OK;
+    };
+    const int rc = timed();
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    return rc;
+}
+
+namespace {
 
 constexpr int kMaxDevices = 16;
 
-struct DeviceCtx {
-    bool ready = false;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int num_cus = 0;
-    uint8_t* pinned = nullptr;      // staging for uploads
-    size_t pinned_bytes = 0;
-    unsigned long long* pinned_count = nullptr;  // 8-byte readback slot
-    hipEvent_t mark[2] = {nullptr, nullptr};     // smartgpu_stream_mark()
-    bool hor_preloaded = false;                  // sg::g_hor_preload has run on this device (smartgpu_plan_create)
-    // smartgpu_search_batch64(): one arena for the K pattern blobs and the K counts, grown when a
-    // batch needs more, never per pattern; K+1 events for the per-pattern device times
-    uint8_t* arena = nullptr;
-    size_t arena_bytes = 0;
-    unsigned long long* batch_counts = nullptr;
-    size_t batch_slots = 0;
-    unsigned long long* pinned_counts = nullptr;  // host side of the one read-back
-    std::vector<hipEvent_t> batch_events;
-    // smartgpu_pfind64(): the positions' device buffer, kept between calls while it is small (find_reserve)
-    unsigned long long* find_out = nullptr;
-    size_t find_out_cap = 0;  // entries
-};
 DeviceCtx g_dev[kMaxDevices];
 
 DeviceCtx* device_ctx(int device)
@@ -144,56 +153,7 @@ bool count_poisoned(unsigned long long c)
     return true;
 }
 
-double now_ms()
-{
-    using clk = std::chrono::steady_clock;  // CLOCK_MONOTONIC, as src/timer.h:43-55
-    return std::chrono::duration<double, std::milli>(clk::now().time_since_epoch()).count();
-}
-
-// `reps` passes of probe_read over [first, first + bytes) after one warm-up pass, timed by two events of its own: both
-// are released on every path
-int probe_read_ms(const DeviceCtx* d, const uint8_t* first, uint64_t bytes, unsigned long long* sink, int reps, double* ms_per_pass)
-{
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const auto timed = [&]() -> int {
-        HIP_TRY(hipEventCreate(&e0), return SMARTGPU_ERR_HIP);
-        HIP_TRY(hipEventCreate(&e1), return SMARTGPU_ERR_HIP);
-        sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);  // warm-up
-        hipEventRecord(e0, d->stream);
-        for (int i = 0; i < reps; ++i) sg::launch_probe_read(first, bytes, sink, d->num_cus, d->stream);
-        hipEventRecord(e1, d->stream);
-        HIP_TRY(hipEventSynchronize(e1), return SMARTGPU_ERR_HIP);
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, e0, e1);
-        *ms_per_pass = ms / reps;
-        return SMARTGPU_OK;
-    };
-    const int rc = timed();
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return rc;
-}
-
 }  // namespace
-
-struct smartgpu_text {
-    int device = 0;
-    uint64_t n = 0;
-    uint8_t* base = nullptr;  // allocation start; text byte 0 at base + kFrontPad
-    const uint8_t* data() const { return base + sg::kFrontPad; }
-    // what the text consists of, taken once when it is created (text_alphabet below): the byte values that occur, and
-    // — for at most four of them — their two-bit codes (ScanArgs.four_shift, four_symtab; 7: none)
-    uint32_t alphabet[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t four_shift = 7, four_symtab = 0, one_bit = 0xFF;
-    sg::TextCodes codes() const { sg::TextCodes c; c.shift = four_shift; c.symtab = four_symtab; c.one = one_bit; return c; }
-    // how often two of its symbols are equal, from a byte histogram of a sample taken in the same pass (text_rate.hpp);
-    // -1: none (text_no_alphabet, a text of fewer than two bytes).  What queue_launch asks before a pattern whose own
-    // symbols repeat may ride in a shared pass.
-    double rate = -1.0;
-    // the 4 bytes at every 28th position (sample.hpp), written once behind the alphabet pass; null: the text has none
-    // (smartgpu_text_sampling, a one-search upload, or no memory for it) and its passes read the text itself
-    uint32_t* sample = nullptr;
-};
 
 struct smartgpu_plan {
     int device = 0;
@@ -582,6 +542,8 @@ void flush_all_queues()
     if (current >= 0) (void)hipSetDevice(current);
 }
 
+}  // namespace
+
 // device_ctx for an entry point that waits for the device's stream or puts work of its own on it
 DeviceCtx* device_ctx_flushed(int device)
 {
@@ -591,6 +553,8 @@ DeviceCtx* device_ctx_flushed(int device)
     if (e != hipSuccess) { set_error("a queued launch failed: %s", hipGetErrorString(e)); return nullptr; }
     return d;
 }
+
+namespace {
 
 // Queue the launch if it is one that can share a pass.  *queued = false: the caller launches it (after flush_queue).
 // A RIDER is a launch of the same route whose pattern's own symbols repeat (words.sparse == 0, m >= 8) over a text whose
@@ -677,29 +641,6 @@ hipError_t (*g_hor_sample)(const MultiArgs&, const uint32_t*, int, int, hipStrea
 hipError_t (*g_sample_build)(const uint8_t*, uint64_t, uint32_t*, int, hipStream_t) = nullptr;
 hipError_t (*g_hor_preload)() = nullptr;  // launch_common.hpp: set by k_hor.hip where that unit is linked
 int (*g_text_histogram)(const uint8_t*, uint64_t, unsigned long long*, int, void*) = nullptr;  // text_rate.hpp: set by k_util.hip where that unit is linked
-// pedit.hpp: set by k_pedit.hip where that unit is linked
-hipError_t (*g_planes_edit_scan)(const PlaneEditArgs&, int, int, hipStream_t) = nullptr;
-hipError_t (*g_planes_edit_find)(const PlaneEditArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
-// peditl.hpp: set by k_peditl.hip where that unit is linked
-hipError_t (*g_planes_editl_scan)(const PlaneEditlArgs&, int, int, hipStream_t) = nullptr;
-hipError_t (*g_planes_editl_find)(const PlaneEditlArgs&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
-// tedit.hpp: set by k_tedit.hip where that unit is linked
-hipError_t (*g_text_edit_scan)(const TextEditArgs&, int, hipStream_t) = nullptr;
-hipError_t (*g_text_edit_find)(const TextEditArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
-// teditl.hpp: set by k_teditl.hip where that unit is linked
-hipError_t (*g_text_editl_scan)(const TextEditlArgs&, int, hipStream_t) = nullptr;
-hipError_t (*g_text_editl_find)(const TextEditlArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
-// tmis.hpp: set by k_tmis.hip where that unit is linked
-hipError_t (*g_text_mis_scan)(const TextMisArgs&, int, hipStream_t) = nullptr;
-hipError_t (*g_text_mis_find)(const TextMisArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
-// palign.hpp: set by k_palign.hip where that unit is linked
-hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
-// talign.hpp: set by k_talign.hip where that unit is linked
-hipError_t (*g_text_edit_align)(const TextAlignArgs&, hipStream_t) = nullptr;
-// planes3.hpp: set by k_planes3.hip where that unit is linked
-hipError_t (*g_planes3_pack)(const uint8_t*, uint64_t, uint32_t*, uint32_t*, uint32_t*, const uint8_t[7], hipStream_t) = nullptr;
-hipError_t (*g_planes3_scan)(const Plane3Args&, int, int, hipStream_t) = nullptr;
-hipError_t (*g_planes3_find)(const Plane3Args&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
 }
 
 extern "C" {
@@ -1154,13 +1095,10 @@ int smartgpu_search64(int algo, const uint8_t* P, uint32_t m, const smartgpu_tex
     return SMARTGPU_OK;
 }
 
-
 /* ---- a whole pattern set per call (the harness loop, src/smart.c:312-345) ------------- */
 }  // extern "C"
 
-namespace {
-
-// make sure the device's batch arena holds `blob_bytes` of tables and `k` counts
+// (host_ctx.hpp) make sure the device's batch arena holds `blob_bytes` of tables and `k` counts
 bool batch_reserve(DeviceCtx* d, size_t blob_bytes, size_t k)
 {
     if (blob_bytes > d->arena_bytes) {
@@ -1187,6 +1125,43 @@ bool batch_reserve(DeviceCtx* d, size_t blob_bytes, size_t k)
     }
     return true;
 }
+
+// (host_ctx.hpp) the device buffer of `cap` positions for a find
+unsigned long long* find_reserve(DeviceCtx* d, uint64_t cap, bool* own)
+{
+    *own = false;
+    if (cap <= d->find_out_cap) return d->find_out;
+    unsigned long long* out = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&out), cap * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("pfind: cannot allocate %llu positions on the device", (unsigned long long)cap);
+        return nullptr;
+    }
+    if (cap > kFindKeep) {
+        *own = true;
+        return out;
+    }
+    if (d->find_out) (void)hipFree(d->find_out);  // (idle: every find ends with a synchronisation of the device's stream)
+    d->find_out = out;
+    d->find_out_cap = static_cast<size_t>(cap);
+    return out;
+}
+
+// (host_ctx.hpp) positions from the device to the caller's memory through the pinned staging buffer
+bool copy_positions(DeviceCtx* d, uint64_t* dst, const unsigned long long* src, uint64_t count)
+{
+    for (uint64_t done = 0; done < count;) {
+        const uint64_t part = std::min<uint64_t>(count - done, d->pinned_bytes / 8);
+        if (hipMemcpyAsync(d->pinned, src + done, part * 8, hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
+            hipStreamSynchronize(d->stream) != hipSuccess)
+            return false;
+        std::memcpy(dst + done, d->pinned, part * 8);
+        done += part;
+    }
+    return true;
+}
+
+namespace {
 
 struct BatchPlan { sg::PlanWords words; size_t off; };  // off: the blob inside the arena
 // the staging buffer of a set of K patterns: [table blobs ...][K argument records][K launch-order indices]
@@ -1875,1225 +1850,6 @@ int smartgpu_build_table(int which, const uint8_t* P, uint32_t m, int32_t* out, 
     return static_cast<int>(v.size());
 }
 
-}  // extern "C"
-
-/* ---- packed texts: at most four byte values as bit planes (planes.hpp, k_planes.hip), five to eight on three
- * (planes3.hpp, k_planes3.hip) ------------------------------------------------------------------------------------- */
-struct smartgpu_ptext {
-    int device = 0;
-    uint64_t n = 0;            // symbols
-    int planes = 1;            // 1: at most two values, 2: three or four, 3: five to eight
-    int nvalues = 0;
-    uint8_t values[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // values[code], ascending
-    uint8_t* base = nullptr;   // allocation start; plane b at base + kFrontPad + b * plane_stride(n)
-    uint32_t* plane(int b) const { return reinterpret_cast<uint32_t*>(base + sg::kFrontPad + static_cast<uint64_t>(b) * sg::plane_stride(n)); }
-    uint64_t alloc_bytes() const { return sg::kFrontPad + static_cast<uint64_t>(planes) * sg::plane_stride(n); }
-};
-
-namespace {
-
-int check_psearch_args(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n)
-{
-    if (!P || m < 1 || m > SMARTGPU_XSIZE) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
-    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// The head every packed kernel's arguments share (PlaneArgs, PlaneSetArgs, PlaneMisArgs, PlaneSetMisArgs), n >= m: the planes,
-// the start positions, the pattern's planes in the device's arena (read when m > 32 only) and result slot d->batch_counts[k].
-template <typename Args>
-void plane_head(Args& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint64_t off, uint64_t n, uint32_t k = 0)
-{
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.s_begin = off;
-    a.s_end = off + n - m + 1;
-    a.m = m;
-    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
-    a.count = d->batch_counts + k;
-}
-
-// plane_head for a three-plane text (Plane3Args: planes3.hpp)
-void plane_head(sg::Plane3Args& a, const DeviceCtx* d, const smartgpu_ptext* text, uint32_t m, uint64_t off, uint64_t n, uint32_t k = 0)
-{
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(1);
-    a.p2 = text->plane(2);
-    a.s_begin = off;
-    a.s_end = off + n - m + 1;
-    a.m = m;
-    a.pat = reinterpret_cast<const uint32_t*>(d->arena);
-    a.count = d->batch_counts + k;
-}
-
-// a.y of Plane3Args: the first dword of each of the eight membership planes at Y
-void set_words8(sg::Plane3Args& a, const uint32_t* Y)
-{
-    for (uint32_t c = 0; c < 8; ++c) a.y[c] = Y[c * sg::kPatWords];
-}
-
-// The calls on a three-plane text need k_planes3.hip in the program: a missing kernel is an error, never a fall-back.
-bool planes3_linked(const char* call)
-{
-    if (sg::g_planes3_scan && sg::g_planes3_find) return true;
-    set_error("%s: this program holds no planes3_scan / planes3_find kernel (k_planes3.hip is not linked)", call);
-    return false;
-}
-
-// What the kernels receive for pattern k of a set staged at host_pat (encode_pattern, 2 * kPatWords dwords per pattern)
-// and, for m > 32, at the same stride in the device's arena.
-sg::PlaneArgs plane_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* host_pat, uint32_t k, uint32_t m, uint64_t off, uint64_t n)
-{
-    sg::PlaneArgs a;
-    plane_head(a, d, text, m, off, n, k);
-    a.x0 = host_pat[2 * sg::kPatWords * k];
-    a.x1 = host_pat[2 * sg::kPatWords * k + sg::kPatWords];
-    a.pat += 2 * sg::kPatWords * k;
-    return a;
-}
-
-// What planes3_scan / planes3_find receive for pattern k of a set staged at host_pat (encode_pattern8, kSet8Words dwords per
-// pattern) and, for m > 32, at the same stride in the device's arena: an exact pattern, singleton sets, budget 0.
-sg::Plane3Args plane3_args(const DeviceCtx* d, const smartgpu_ptext* text, const uint32_t* host_pat, uint32_t k, uint32_t m, uint64_t off, uint64_t n)
-{
-    sg::Plane3Args a;
-    plane_head(a, d, text, m, off, n, k);
-    set_words8(a, host_pat + sg::kSet8Words * k);
-    a.budget = a.foreign = a.shift = 0;
-    a.pat += sg::kSet8Words * k;
-    return a;
-}
-
-// psearch_impl on a three-plane text (K <= kBatch3Max: checked by the callers before any HIP call): eight membership planes
-// per pattern in place of two code planes.
-int psearch3_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                  uint64_t* counts, double* pre_ms, double* run_ms)
-{
-    if (!planes3_linked("psearch64")) return SMARTGPU_ERR_HIP;
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    const double t_pre = now_ms();
-    constexpr size_t kPatBytes = 4 * sg::kSet8Words;
-    if (static_cast<size_t>(K) * kPatBytes > d->pinned_bytes) { set_error("psearch_batch: %u patterns exceed the staging buffer", K); return SMARTGPU_ERR_ARG; }
-    if (!batch_reserve(d, static_cast<size_t>(K) * kPatBytes, K)) return SMARTGPU_ERR_NOMEM;
-    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
-    uint32_t* host_pat = reinterpret_cast<uint32_t*>(d->pinned);
-    std::vector<uint8_t> present(K, 0);
-    for (uint32_t k = 0; k < K; ++k) {
-        if (!P[k]) { set_error("pattern %u is NULL", k); return SMARTGPU_ERR_ARG; }
-        present[k] = sg::encode_pattern8(text->values, text->nvalues, P[k], m, false, host_pat + sg::kSet8Words * k) == 0;
-    }
-    const bool fits = n >= m;  // m > n: no window fits, count 0
-    if (m > 32 && fits)
-        HIP_TRY(hipMemcpyAsync(d->arena, host_pat, static_cast<size_t>(K) * kPatBytes, hipMemcpyHostToDevice, d->stream), return SMARTGPU_ERR_HIP);
-    if (pre_ms) *pre_ms = now_ms() - t_pre;
-    const double t0 = now_ms();
-    HIP_TRY(hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream), return SMARTGPU_ERR_HIP);
-    for (uint32_t k = 0; k < K && fits; ++k) {
-        if (!present[k]) continue;
-        const sg::Plane3Args a = plane3_args(d, text, host_pat, k, m, off, n);
-        HIP_TRY(sg::g_planes3_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-    }
-    HIP_TRY(hipMemcpyAsync(d->pinned_counts, d->batch_counts, static_cast<size_t>(K) * 8, hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-    if (run_ms) *run_ms = now_ms() - t0;
-    for (uint32_t k = 0; k < K; ++k) {
-        // more occurrences than start positions: refused like a poisoned count, never reported
-        if (d->pinned_counts[k] > (fits ? n - m + 1 : 0)) { set_error("planes3_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[k], (unsigned long long)(fits ? n - m + 1 : 0)); return SMARTGPU_ERR_HIP; }
-        counts[k] = d->pinned_counts[k];
-    }
-    return SMARTGPU_OK;
-}
-
-// The batch calls' bound on a three-plane text (planes3.hpp: kBatch3Max), decided before any HIP call.
-int check_batch3(const char* call, const smartgpu_ptext* text, uint32_t K)
-{
-    if (text->planes != 3 || K <= sg::kBatch3Max) return SMARTGPU_OK;
-    set_error("%s: %u patterns on a three-plane text, at most %u per call (eight membership planes per pattern in the staging buffer)", call, K, sg::kBatch3Max);
-    return SMARTGPU_ERR_ARG;
-}
-
-// K patterns of m symbols: their planes to the device's arena (m > 32 only: shorter patterns travel as kernel arguments),
-// K launches back to back on the device's stream, ONE read-back.  A pattern with a byte the text does not hold: no launch.
-int psearch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                 uint64_t* counts, double* pre_ms, double* run_ms)
-{
-    if (text->planes == 3) return psearch3_impl(P, m, K, text, off, n, counts, pre_ms, run_ms);
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    const double t_pre = now_ms();
-    constexpr size_t kPatBytes = 2 * 4 * sg::kPatWords;  // one pattern's two planes
-    if (static_cast<size_t>(K) * kPatBytes > d->pinned_bytes) { set_error("psearch_batch: %u patterns exceed the staging buffer", K); return SMARTGPU_ERR_ARG; }
-    if (!batch_reserve(d, static_cast<size_t>(K) * kPatBytes, K)) return SMARTGPU_ERR_NOMEM;
-    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
-    uint32_t* host_pat = reinterpret_cast<uint32_t*>(d->pinned);
-    std::vector<uint8_t> present(K, 0);
-    for (uint32_t k = 0; k < K; ++k) {
-        if (!P[k]) { set_error("pattern %u is NULL", k); return SMARTGPU_ERR_ARG; }
-        uint32_t* X = host_pat + 2 * sg::kPatWords * k;
-        present[k] = sg::encode_pattern(text->values, text->nvalues, P[k], m, X, X + sg::kPatWords, nullptr) == 0;
-    }
-    const bool fits = n >= m;  // m > n: no window fits, count 0
-    if (m > 32 && fits)
-        HIP_TRY(hipMemcpyAsync(d->arena, host_pat, static_cast<size_t>(K) * kPatBytes, hipMemcpyHostToDevice, d->stream), return SMARTGPU_ERR_HIP);
-    if (pre_ms) *pre_ms = now_ms() - t_pre;
-    const double t0 = now_ms();
-    HIP_TRY(hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream), return SMARTGPU_ERR_HIP);
-    for (uint32_t k = 0; k < K && fits; ++k) {
-        if (!present[k]) continue;
-        const sg::PlaneArgs a = plane_args(d, text, host_pat, k, m, off, n);
-        HIP_TRY(sg::launch_planes_scan(a, text->planes, d->num_cus, d->stream), return SMARTGPU_ERR_HIP);
-    }
-    HIP_TRY(hipMemcpyAsync(d->pinned_counts, d->batch_counts, static_cast<size_t>(K) * 8, hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-    if (run_ms) *run_ms = now_ms() - t0;
-    for (uint32_t k = 0; k < K; ++k) {
-        // more occurrences than start positions: refused like a poisoned count, never reported
-        if (d->pinned_counts[k] > (fits ? n - m + 1 : 0)) { set_error("planes_scan: count %llu exceeds the %llu start positions", (unsigned long long)d->pinned_counts[k], (unsigned long long)(fits ? n - m + 1 : 0)); return SMARTGPU_ERR_HIP; }
-        counts[k] = d->pinned_counts[k];
-    }
-    return SMARTGPU_OK;
-}
-
-// The device buffer of `cap` positions for a find.  Up to kFindKeep entries it is the device's own, grown when a call needs
-// more and kept (no hipMalloc per call: a find on a packed text takes less time than an allocation); a larger one is the
-// call's (*own, to be freed by the caller).
-constexpr size_t kFindKeep = size_t(8) << 20;  // entries: 64 MiB
-unsigned long long* find_reserve(DeviceCtx* d, uint64_t cap, bool* own)
-{
-    *own = false;
-    if (cap <= d->find_out_cap) return d->find_out;
-    unsigned long long* out = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&out), cap * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("pfind: cannot allocate %llu positions on the device", (unsigned long long)cap);
-        return nullptr;
-    }
-    if (cap > kFindKeep) {
-        *own = true;
-        return out;
-    }
-    if (d->find_out) (void)hipFree(d->find_out);  // (idle: every find ends with a synchronisation of the device's stream)
-    d->find_out = out;
-    d->find_out_cap = static_cast<size_t>(cap);
-    return out;
-}
-
-// Positions from the device to the caller's (pageable) memory through the device's pinned staging buffer, part by part
-// (no overlap of copy and memcpy): a hipMemcpy into pageable memory stages as well, through buffers it sets up per call.
-// The staging buffer is free: the patterns it held have been launched and the stream is synchronised.
-bool copy_positions(DeviceCtx* d, uint64_t* dst, const unsigned long long* src, uint64_t count)
-{
-    for (uint64_t done = 0; done < count;) {
-        const uint64_t part = std::min<uint64_t>(count - done, d->pinned_bytes / 8);
-        if (hipMemcpyAsync(d->pinned, src + done, part * 8, hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
-            hipStreamSynchronize(d->stream) != hipSuccess)
-            return false;
-        std::memcpy(dst + done, d->pinned, part * 8);
-        done += part;
-    }
-    return true;
-}
-
-// ---- ONE host path for every single-pattern count and find on a packed text and for the edit-distance calls on a byte
-// text: count_run and find_run.  The skeleton fixes the order of the steps — the device's context with nothing queued, the
-// arena (batch_reserve), for a find the entries' device buffer (find_reserve; none: the call still counts), the family's
-// staging, the slot's memset, the kernel, the read-back, the synchronisation —, the refusal of a count or cursor beyond
-// the bound, what *count receives, the find's outcomes (planes_host.hpp: find_outcome) with their return codes and texts,
-// and the times (pre: arena and staging; run: memset to synchronisation; counts only).  A family supplies its names
-// (RunNames), its bound — n - m + 1 start positions, or n end positions whatever m is —, the bytes it stages into the
-// arena, and two lambdas: `stage` (may do nothing; false is a HIP error) and `launch` (fills what its arguments need of the
-// device — the result slot is d->batch_counts — and launches).  A find adds a third, `order`: the entries in ascending
-// order, or set_error and false for what its kernel cannot have written.  So a family is: checks, masks, args, two
-// lambdas; what needs no launch it answers before it comes here. ----
-struct RunNames {
-    const char* call;     // the entry point: "<call>: ..." for what the caller can mend
-    const char* kernel;   // the kernel, for refusals of what the device wrote
-    const char* bound;    // what the bound counts: "start positions", "end positions"
-    const char* entries;  // what a find lists: "positions", "entries"
-};
-
-// What a count call answers: the times for smartgpu_last_times, the count and the times for the caller.
-int pcount_done(uint64_t c, double pre, double run, uint64_t* count, double* pre_ms, double* run_ms)
-{
-    g_last_pre_ms = pre;
-    g_last_run_ms = run;
-    if (count) *count = c;
-    if (pre_ms) *pre_ms = pre;
-    if (run_ms) *run_ms = run;
-    return SMARTGPU_OK;
-}
-
-template <typename Stage, typename Launch>
-int count_run(const RunNames& w, int device, size_t arena_bytes, uint64_t bound, Stage stage, Launch launch, uint64_t* count, double* pre_ms,
-              double* run_ms)
-{
-    DeviceCtx* d = device_ctx_flushed(device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    const double t_pre = now_ms();
-    if (!batch_reserve(d, arena_bytes, 1)) return SMARTGPU_ERR_NOMEM;
-    if (!stage(d)) { set_error("%s: %s", w.call, hipGetErrorString(hipGetLastError())); return SMARTGPU_ERR_HIP; }
-    const double pre = now_ms() - t_pre;
-    const double t0 = now_ms();
-    HIP_TRY(hipMemsetAsync(d->batch_counts, 0, sizeof(unsigned long long), d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(launch(d), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipMemcpyAsync(d->pinned_counts, d->batch_counts, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream), return SMARTGPU_ERR_HIP);
-    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-    const double run = now_ms() - t0;
-    // more occurrences than positions: refused like a poisoned count, never reported
-    if (d->pinned_counts[0] > bound) { set_error("%s: count %llu exceeds the %llu %s", w.kernel, (unsigned long long)d->pinned_counts[0], (unsigned long long)bound, w.bound); return SMARTGPU_ERR_HIP; }
-    return pcount_done(d->pinned_counts[0], pre, run, count, pre_ms, run_ms);
-}
-
-// *count receives the number of occurrences whenever the device answered with a cursor within the bound, on
-// SMARTGPU_ERR_NOMEM too; `entries` receives the list, in order, on SMARTGPU_OK only, and nothing behind entries[cap] is
-// touched.  The entries reach `order` as the kernel wrote them; unpacking distances is the caller's.
-template <typename Stage, typename Launch, typename Order>
-int find_run(const RunNames& w, int device, size_t arena_bytes, uint64_t bound, Stage stage, Launch launch, Order order, uint64_t* entries,
-             uint64_t cap, uint64_t* count)
-{
-    DeviceCtx* d = device_ctx_flushed(device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, arena_bytes, 1)) return SMARTGPU_ERR_NOMEM;
-    const uint64_t room = cap < bound ? cap : bound;  // no more entries than positions
-    bool own = false;
-    unsigned long long* out = nullptr;
-    uint64_t room_got = room;
-    if (room && !(out = find_reserve(d, room, &own))) room_got = 0;  // no device room: the call still counts
-    const bool ok = stage(d) && hipMemsetAsync(d->batch_counts, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
-                    launch(d, out, room_got) == hipSuccess &&
-                    hipMemcpyAsync(d->pinned_counts, d->batch_counts, sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
-                    hipStreamSynchronize(d->stream) == hipSuccess;
-    const unsigned long long total = ok ? d->pinned_counts[0] : 0;
-    int r = SMARTGPU_OK;
-    if (!ok) {
-        set_error("%s: %s", w.call, hipGetErrorString(hipGetLastError()));
-        r = SMARTGPU_ERR_HIP;
-    } else switch (sg::find_outcome(total, bound, room_got, cap)) {
-    case sg::FindOutcome::kBeyondBound:
-        set_error("%s: cursor %llu exceeds the %llu %s", w.kernel, total, (unsigned long long)bound, w.bound);
-        r = SMARTGPU_ERR_HIP;
-        break;
-    case sg::FindOutcome::kComplete:
-        if (total && !copy_positions(d, entries, out, total)) {
-            set_error("%s: %s", w.call, hipGetErrorString(hipGetLastError()));
-            r = SMARTGPU_ERR_HIP;
-        } else if (total && !order(entries, total)) {
-            r = SMARTGPU_ERR_HIP;
-        }
-        break;
-    case sg::FindOutcome::kOverCap:
-        set_error("%s: %llu occurrences, room for %llu", w.call, total, (unsigned long long)cap);
-        r = SMARTGPU_ERR_NOMEM;
-        break;
-    case sg::FindOutcome::kNoRoom:
-        set_error("%s: %llu occurrences, room for %llu, but the device has no memory for %llu %s", w.call, total, (unsigned long long)cap, (unsigned long long)room, w.entries);
-        r = SMARTGPU_ERR_NOMEM;
-        break;
-    }
-    if (own) (void)hipFree(out);
-    if (r != SMARTGPU_ERR_HIP) *count = total;
-    return r;
-}
-
-// find_run's `order` for the kernels that write spans (planes.hpp): order_spans over the positions [lo, hi]
-bool spans_in_order(const RunNames& w, uint64_t* entries, uint64_t total, uint64_t lo, uint64_t hi, uint32_t shift)
-{
-    if (sg::order_spans(entries, total, lo, hi, shift)) return true;
-    set_error("%s: the %s are not ascending spans of %llu %s", w.kernel, w.entries, (unsigned long long)sg::kFindSpan, w.bound);
-    return false;
-}
-
-// A find whose every start position is an occurrence (full sets): no launch
-int find_every_start(const char* call, uint64_t off, uint64_t total, uint64_t* positions, uint64_t cap, uint64_t* count)
-{
-    *count = total;
-    if (total > cap) { set_error("%s: %llu occurrences, room for %llu", call, (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-    for (uint64_t i = 0; i < total; ++i) positions[i] = off + i;
-    return SMARTGPU_OK;
-}
-
-// The pattern's planes (`bytes` at `words`) through the staging buffer into the device's arena, for m > 32 only: the first
-// 32 positions travel as kernel arguments.
-bool stage_pattern(DeviceCtx* d, const uint32_t* words, size_t bytes, uint32_t m)
-{
-    if (m <= 32) return true;
-    // (the staging buffer is free: every call that fills it ends with a synchronisation of the device's stream)
-    std::memcpy(d->pinned, words, bytes);
-    return hipMemcpyAsync(d->arena, d->pinned, bytes, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
-
-// count_run / find_run for the kernels of planes.hpp and planes3.hpp, n >= m: start positions, the pattern's planes at
-// `words` staged when m > 32, `a` holds the kind's own fields.  shift: order_spans'.
-template <typename Args>
-int pcount_run(const char* call, const char* kernel, hipError_t (*launch)(const Args&, int, int, hipStream_t), Args a, const smartgpu_ptext* text,
-               const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return count_run({call, kernel, "start positions", "positions"}, text->device, bytes, n - m + 1,
-                     [&](DeviceCtx* d) { return stage_pattern(d, words, bytes, m); },
-                     [&](DeviceCtx* d) { plane_head(a, d, text, m, off, n); return launch(a, text->planes, d->num_cus, d->stream); },
-                     count, pre_ms, run_ms);
-}
-
-template <typename Args>
-int pfind_run(const char* call, const char* kernel, hipError_t (*launch)(const Args&, unsigned long long*, unsigned long long, int, int, hipStream_t),
-              Args a, const smartgpu_ptext* text, const uint32_t* words, size_t bytes, uint32_t m, uint64_t off, uint64_t n, uint64_t* positions,
-              uint64_t cap, uint64_t* count, uint32_t shift = 0)
-{
-    const RunNames w = {call, kernel, "start positions", "positions"};
-    return find_run(w, text->device, bytes, n - m + 1,
-                    [&](DeviceCtx* d) { return stage_pattern(d, words, bytes, m); },
-                    [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { plane_head(a, d, text, m, off, n); return launch(a, out, room, text->planes, d->num_cus, d->stream); },
-                    [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - m, shift); },
-                    positions, cap, count);
-}
-
-// The entries of a find with distances, position << shift | distance in ascending order, unpacked in place.
-void unpack_mis(uint64_t* positions, uint8_t* mismatches, uint64_t count, uint32_t shift = sg::kMisShift)
-{
-    for (uint64_t i = 0; i < count; ++i) {
-        const uint64_t e = positions[i];
-        if (mismatches) mismatches[i] = static_cast<uint8_t>(e & ((1u << shift) - 1u));
-        positions[i] = e >> shift;
-    }
-}
-
-// The checks of the set, mis and sets-mis calls that need no device; `what` names the pattern argument, k = 0 without mismatches.
-int check_pext_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off,
-                    uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u mismatches, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
-    const int rc = check_psearch_args(P, m, text, off, n);
-    if (rc != SMARTGPU_OK) return rc;
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// encode_sets for a checked call.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
-int sets_planes(const smartgpu_ptext* t, const uint8_t* sets, uint32_t m, bool fill_empty, uint32_t* Y, uint32_t* empty, bool* full)
-{
-    const int bad = sg::encode_sets(t->nvalues, sets, m, fill_empty, Y, empty, full);
-    if (bad < 0) return SMARTGPU_OK;
-    set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, sets[bad], t->nvalues);
-    return SMARTGPU_ERR_ARG;
-}
-
-// a.y of PlaneSetArgs and PlaneSetMisArgs: the first dword of each membership plane
-template <typename Args>
-void set_words(Args& a, const uint32_t* Y)
-{
-    for (uint32_t c = 0; c < 4; ++c) a.y[c] = Y[c * sg::kPatWords];
-}
-
-constexpr size_t kMisWords = 3 * sg::kPatWords;  // a pattern's two code planes and its skip plane
-
-// The pattern as X0, X1, SKIP in X[kMisWords] and a.x0, a.x1, a.skip.  Returns the number of foreign positions.
-uint32_t mis_planes(const smartgpu_ptext* t, const uint8_t* P, uint32_t m, uint32_t* X, sg::PlaneMisArgs* a)
-{
-    const uint32_t foreign = sg::encode_pattern(t->values, t->nvalues, P, m, X, X + sg::kPatWords, X + 2 * sg::kPatWords);
-    a->x0 = X[0];
-    a->x1 = X[sg::kPatWords];
-    a->skip = X[2 * sg::kPatWords];
-    return foreign;
-}
-
-// ---- three-plane texts (planes3.hpp): the exact, set, mismatch and set-with-mismatch calls, count and find, through ONE
-// kernel pair.  The callers have made their own checks (check_psearch_args / check_pext_args) ----
-
-// The pattern — bytes, or sets when `sets` — as eight membership planes at Y[kSet8Words] and as a.y, a.foreign, a.budget for
-// k mismatches.  *none: more positions that accept nothing (empty sets, foreign bytes) than k, no start position is an
-// occurrence; *full: every position accepts every value.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
-int plane3_pattern(const smartgpu_ptext* t, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t* Y, sg::Plane3Args* a, bool* none,
-                   bool* full)
-{
-    uint32_t empty = 0;
-    *full = false;
-    if (sets) {
-        const int bad = sg::encode_sets8(t->nvalues, pat, m, true, Y, &empty, full);
-        if (bad >= 0) {
-            set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, pat[bad], t->nvalues);
-            return SMARTGPU_ERR_ARG;
-        }
-    } else {
-        empty = sg::encode_pattern8(t->values, t->nvalues, pat, m, true, Y);
-    }
-    *none = empty > k;
-    a->foreign = empty;
-    a->budget = *none ? 0 : k - empty;
-    a->shift = 0;
-    set_words8(*a, Y);
-    return SMARTGPU_OK;
-}
-
-// mis: the call takes k and reports distances (its no-launch cases are those of the two-plane mismatch calls: a pattern of
-// full sets is launched there, and answered without a launch by the set calls).
-int p3_count(const char* call, const uint8_t* pat, bool sets, bool mis, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-             uint64_t* count, double* pre_ms, double* run_ms)
-{
-    uint32_t Y[sg::kSet8Words];
-    sg::Plane3Args a;
-    bool none = false, full = false;
-    const int rc = plane3_pattern(text, pat, sets, m, k, Y, &a, &none, &full);
-    if (rc != SMARTGPU_OK) return rc;
-    if (none || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);
-    if (full && !mis) return pcount_done(n - m + 1, 0.0, 0.0, count, pre_ms, run_ms);
-    if (!planes3_linked(call)) return SMARTGPU_ERR_HIP;
-    return pcount_run(call, "planes3_scan", sg::g_planes3_scan, a, text, Y, sizeof Y, m, off, n, count, pre_ms, run_ms);
-}
-
-int p3_find(const char* call, const uint8_t* pat, bool sets, bool mis, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-            uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
-{
-    uint32_t Y[sg::kSet8Words];
-    sg::Plane3Args a;
-    bool none = false, full = false;
-    const int rc = plane3_pattern(text, pat, sets, m, k, Y, &a, &none, &full);
-    if (rc != SMARTGPU_OK) return rc;
-    if (none || m > n) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    if (full && !mis) return find_every_start(call, off, n - m + 1, positions, cap, count);
-    if (!planes3_linked(call)) return SMARTGPU_ERR_HIP;
-    a.shift = mis ? sg::kMisShift : 0u;
-    const int r = pfind_run(call, "planes3_find", sg::g_planes3_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count, a.shift);
-    if (mis && r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
-    return r;
-}
-
-// The edit-distance and alignment calls do not read a third plane.
-int refuse_planes3(const char* call, const smartgpu_ptext* text)
-{
-    if (text->planes != 3) return SMARTGPU_OK;
-    set_error("%s: three-plane texts (five to eight values) are not offered here: edit distance and alignments read one or two planes", call);
-    return SMARTGPU_ERR_ARG;
-}
-
-// The edit-distance families below count and list END positions, n of them whatever m is, and m > n is legal; their
-// entries are end << shift | distance.  None of them stages planes: `stage` does nothing, or (byte texts) sends the masks.
-constexpr auto no_stage = [](DeviceCtx*) { return true; };
-
-// The checks of the edit, editl and align calls that need no device; `what` names the pattern argument, max_m and max_k are
-// the family's, flags is 0 for a call that takes none.
-int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t max_m, uint32_t k, uint32_t max_k, uint32_t flags,
-                     const smartgpu_ptext* text, uint64_t off, uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > max_m) { set_error("%s: pattern length %u outside [1,%u]", call, m, max_m); return SMARTGPU_ERR_ARG; }
-    if (k > max_k) { set_error("%s: k = %u edits, at most %u", call, k, max_k); return SMARTGPU_ERR_ARG; }
-    if (flags & ~SMARTGPU_PEDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_PEDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_PEDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
-    if (refuse_planes3(call, text) != SMARTGPU_OK) return SMARTGPU_ERR_ARG;
-    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// The fields that PlaneEditArgs, PlaneEditlArgs and PlaneAlignArgs share
-template <typename Args>
-void edit_head(Args& a, const smartgpu_ptext* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
-{
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
-}
-
-// Edit distance, m <= 64 and k <= 7 (pedit.hpp).  The pattern's masks for a checked call, kernel arguments: from bytes
-// (sets == false) or from sets.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
-int edit_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, sg::PlaneEditArgs* a)
-{
-    if (!sets) {
-        sg::edit_peq_pattern(t->values, t->nvalues, pat, m, a->peq);
-        return SMARTGPU_OK;
-    }
-    const int bad = sg::edit_peq_sets(t->nvalues, pat, m, a->peq);
-    if (bad < 0) return SMARTGPU_OK;
-    set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, pat[bad], t->nvalues);
-    return SMARTGPU_ERR_ARG;
-}
-
-int pedit_count(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                uint64_t* count, double* pre_ms, double* run_ms)
-{
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    sg::PlaneEditArgs a;
-    if ((rc = edit_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
-    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
-    if (!sg::g_planes_edit_scan) { set_error("%s: this program holds no planes_edit_scan kernel (k_pedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    edit_head(a, text, m, k, off, n);
-    return count_run({call, "planes_edit_scan", "end positions", "entries"}, text->device, 0, n, no_stage,
-                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_planes_edit_scan(a, text->planes, d->num_cus, d->stream); },
-                     count, pre_ms, run_ms);
-}
-
-int pedit_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-               uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    sg::PlaneEditArgs a;
-    if ((rc = edit_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
-    if (n + k < m) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    if (!sg::g_planes_edit_find) { set_error("%s: this program holds no planes_edit_find kernel (k_pedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    edit_head(a, text, m, k, off, n);
-    const RunNames w = {call, "planes_edit_find", "end positions", "entries"};
-    rc = find_run(w, text->device, 0, n, no_stage,
-                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_planes_edit_find(a, out, room, text->planes, d->num_cus, d->stream); },
-                  [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
-                  ends, cap, count);
-    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count);
-    return rc;
-}
-
-// BYTE texts: edit distance (tedit.hpp) and mismatches (tmis.hpp), the contracts of the packed calls above with a
-// smartgpu_text in place of the planes.  The checks of their calls that need no device; `what` names the pattern argument,
-// `noun` what k counts.
-int check_text_args(const char* call, const char* what, int max_m, const char* noun, const uint8_t* P, uint32_t m, uint32_t k,
-                    const smartgpu_text* text, uint64_t off, uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > (uint32_t)max_m) { set_error("%s: pattern length %u outside [1,%d]", call, m, max_m); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u %s, at most %d", call, k, noun, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
-    if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// The pattern is 256 masks (tedit_host.hpp), too many for kernel arguments: bytes or classes as the kernel's table in the
-// staging buffer, on their way to the arena (kTEditArena bytes of it), as psearch_impl's patterns travel.  The staging
-// buffer is free: every call that fills it ends with a synchronisation.
-constexpr size_t kTEditArena = sizeof(uint32_t) * 256 * sg::kTEditWords;
-bool text_table_stage(DeviceCtx* d, const uint32_t (&table)[256][sg::kTEditWords], uint32_t words, const uint32_t** dev)
-{
-    sg::edit_peq_table(table, words, reinterpret_cast<uint32_t*>(d->pinned));
-    *dev = reinterpret_cast<const uint32_t*>(d->arena);
-    return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
-
-bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
-{
-    uint32_t peq[256][sg::kTEditWords];
-    if (classes) sg::edit_peq_classes(pat, m, peq); else sg::edit_peq_bytes(pat, m, peq);
-    return text_table_stage(d, peq, m <= 32 ? 1u : 2u, dev);
-}
-
-// what TextEditArgs, TextMisArgs and TextAlignArgs share: the text and the range, the pattern's length and k
-template <class Args>
-void text_head(Args& a, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
-{
-    a.text = text->data();
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
-}
-
-int tedit_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                uint64_t* count, double* pre_ms, double* run_ms)
-{
-    const int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_EDIT_MAXM, "edits", pat, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
-    if (!sg::g_text_edit_scan) { set_error("%s: this program holds no text_edit_scan kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    sg::TextEditArgs a;
-    text_head(a, text, m, k, off, n);
-    return count_run({call, "text_edit_scan", "end positions", "entries"}, text->device, kTEditArena, n,
-                     [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a.peq); },
-                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_edit_scan(a, d->num_cus, d->stream); },
-                     count, pre_ms, run_ms);
-}
-
-int tedit_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-               uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_EDIT_MAXM, "edits", pat, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (n + k < m) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    if (!sg::g_text_edit_find) { set_error("%s: this program holds no text_edit_find kernel (k_tedit.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    sg::TextEditArgs a;
-    text_head(a, text, m, k, off, n);
-    const RunNames w = {call, "text_edit_find", "end positions", "entries"};
-    rc = find_run(w, text->device, kTEditArena, n,
-                  [&](DeviceCtx* d) { return tedit_stage(d, pat, classes, m, &a.peq); },
-                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_edit_find(a, out, room, d->num_cus, d->stream); },
-                  [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
-                  ends, cap, count);
-    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count);
-    return rc;
-}
-
-// Mismatches on BYTE texts (tmis.hpp).  The 256 masks "position j does NOT accept this byte" (tmis_host.hpp) travel as
-// tedit_stage's: the same table, the same arena.
-bool tmis_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
-{
-    uint32_t neq[256][sg::kTEditWords];
-    if (classes) sg::mis_neq_classes(pat, m, neq); else sg::mis_neq_bytes(pat, m, neq);
-    return text_table_stage(d, neq, static_cast<uint32_t>(sg::mis_words(m)), dev);
-}
-
-int tmis_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-               uint64_t* count, double* pre_ms, double* run_ms)
-{
-    const int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_MIS_MAXM, "mismatches", pat, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // no window fits: no launch
-    if (!sg::g_text_mis_scan) { set_error("%s: this program holds no text_mis_scan kernel (k_tmis.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    sg::TextMisArgs a;
-    text_head(a, text, m, k, off, n);
-    return count_run({call, "text_mis_scan", "start positions", "positions"}, text->device, kTEditArena, n - m + 1,
-                     [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a.neq); },
-                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_mis_scan(a, d->num_cus, d->stream); },
-                     count, pre_ms, run_ms);
-}
-
-int tmis_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-              uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
-{
-    if (cap && !positions) { set_error("%s: positions NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_MIS_MAXM, "mismatches", pat, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (m > n) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    if (!sg::g_text_mis_find) { set_error("%s: this program holds no text_mis_find kernel (k_tmis.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    sg::TextMisArgs a;
-    text_head(a, text, m, k, off, n);
-    const RunNames w = {call, "text_mis_find", "start positions", "positions"};
-    // the kernel's entries hold END positions, the spans order_spans knows (tmis.hpp); a window's start is m - 1 below its end
-    rc = find_run(w, text->device, kTEditArena, n - m + 1,
-                  [&](DeviceCtx* d) { return tmis_stage(d, pat, classes, m, &a.neq); },
-                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_mis_find(a, out, room, d->num_cus, d->stream); },
-                  [&](uint64_t* e, uint64_t total) { return spans_in_order(w, e, total, off, off + n - 1, sg::kMisShift); },
-                  positions, cap, count);
-    if (rc == SMARTGPU_OK) {
-        unpack_mis(positions, mismatches, *count);
-        for (uint64_t i = 0; i < *count; ++i) positions[i] -= m - 1;
-    }
-    return rc;
-}
-
-// Edit distance, long patterns (peditl.hpp): m <= 256 and k <= 31, a switch that travels with the call, and entries that
-// the kernel writes in no order (order_editl sorts them).  edit_masks, eight dwords wide:
-int editl_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, sg::PlaneEditlArgs* a)
-{
-    if (!sets) {
-        sg::editl_peq_pattern(t->values, t->nvalues, pat, m, a->peq);
-        return SMARTGPU_OK;
-    }
-    const int bad = sg::editl_peq_sets(t->nvalues, pat, m, a->peq);
-    if (bad < 0) return SMARTGPU_OK;
-    set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, pat[bad], t->nvalues);
-    return SMARTGPU_ERR_ARG;
-}
-
-int peditl_count(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off,
-                 uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
-{
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDITL_MAXM, k, SMARTGPU_PEDITL_MAXK, flags, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    sg::PlaneEditlArgs a;
-    if ((rc = editl_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
-    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
-    if (!sg::g_planes_editl_scan) { set_error("%s: this program holds no planes_editl_scan kernel (k_peditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    edit_head(a, text, m, k, off, n);
-    a.all_blocks = flags & SMARTGPU_PEDITL_ALL_BLOCKS;
-    return count_run({call, "planes_editl_scan", "end positions", "entries"}, text->device, 0, n, no_stage,
-                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_planes_editl_scan(a, text->planes, d->num_cus, d->stream); },
-                     count, pre_ms, run_ms);
-}
-
-int peditl_find(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off,
-                uint64_t n, uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDITL_MAXM, k, SMARTGPU_PEDITL_MAXK, flags, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    sg::PlaneEditlArgs a;
-    if ((rc = editl_masks(text, pat, m, sets, &a)) != SMARTGPU_OK) return rc;
-    if (n + k < m) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    if (!sg::g_planes_editl_find) { set_error("%s: this program holds no planes_editl_find kernel (k_peditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    edit_head(a, text, m, k, off, n);
-    a.all_blocks = flags & SMARTGPU_PEDITL_ALL_BLOCKS;
-    rc = find_run({call, "planes_editl_find", "end positions", "entries"}, text->device, 0, n, no_stage,
-                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_planes_editl_find(a, out, room, text->planes, d->num_cus, d->stream); },
-                  [&](uint64_t* e, uint64_t total) {
-                      if (sg::order_editl(e, total, off, off + n - 1, k, sg::kEditlShift)) return true;
-                      set_error("planes_editl_find: the entries are not distinct end positions of the range with distances <= %u", k);
-                      return false;
-                  },
-                  ends, cap, count);
-    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count, sg::kEditlShift);
-    return rc;
-}
-
-// Edit distance on BYTE texts, long patterns (teditl.hpp): tedit_count / tedit_find with peditl's bounds, its switch and its
-// unordered entries.  check_text_args' checks, in its order and style, with the wider bounds and the flags check.
-int check_teditl_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text,
-                      uint64_t off, uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > SMARTGPU_EDITL_MAXM) { set_error("%s: pattern length %u outside [1,%d]", call, m, SMARTGPU_EDITL_MAXM); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_EDITL_MAXK) { set_error("%s: k = %u edits, at most %d", call, k, SMARTGPU_EDITL_MAXK); return SMARTGPU_ERR_ARG; }
-    if (flags & ~SMARTGPU_EDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_EDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_EDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
-    if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// The 256 masks, word-major (teditl_host.hpp: 2, 4 or 8 KiB), through the staging buffer into the arena, as text_table_stage
-// sends the short patterns' table.
-constexpr size_t kTEditlArena = sizeof(uint32_t) * 256 * sg::kTEditlWords;
-bool teditl_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
-{
-    uint32_t peq[256][sg::kTEditlWords];
-    if (classes) sg::editl_peq_classes(pat, m, peq); else sg::editl_peq_bytes(pat, m, peq);
-    const uint32_t words = m <= 64 ? 2u : m <= 128 ? 4u : 8u;  // the kernels' WORDS (k_teditl.hip)
-    sg::editl_peq_table(peq, words, reinterpret_cast<uint32_t*>(d->pinned));
-    *dev = reinterpret_cast<const uint32_t*>(d->arena);
-    return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
-
-int teditl_count(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
-                 uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
-{
-    const int rc = check_teditl_args(call, classes ? "classes" : "P", pat, m, k, flags, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (n + k < m) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // not even with k deletions: no launch
-    if (!sg::g_text_editl_scan) { set_error("%s: this program holds no text_editl_scan kernel (k_teditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    sg::TextEditlArgs a;
-    text_head(a, text, m, k, off, n);
-    a.all_blocks = flags & SMARTGPU_EDITL_ALL_BLOCKS;
-    return count_run({call, "text_editl_scan", "end positions", "entries"}, text->device, kTEditlArena, n,
-                     [&](DeviceCtx* d) { return teditl_stage(d, pat, classes, m, &a.peq); },
-                     [&](DeviceCtx* d) { a.count = d->batch_counts; return sg::g_text_editl_scan(a, d->num_cus, d->stream); },
-                     count, pre_ms, run_ms);
-}
-
-int teditl_find(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
-                uint64_t n, uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    if (cap && !ends) { set_error("%s: ends NULL with cap > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_teditl_args(call, classes ? "classes" : "P", pat, m, k, flags, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (n + k < m) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    if (!sg::g_text_editl_find) { set_error("%s: this program holds no text_editl_find kernel (k_teditl.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    sg::TextEditlArgs a;
-    text_head(a, text, m, k, off, n);
-    a.all_blocks = flags & SMARTGPU_EDITL_ALL_BLOCKS;
-    rc = find_run({call, "text_editl_find", "end positions", "entries"}, text->device, kTEditlArena, n,
-                  [&](DeviceCtx* d) { return teditl_stage(d, pat, classes, m, &a.peq); },
-                  [&](DeviceCtx* d, unsigned long long* out, uint64_t room) { a.count = d->batch_counts; return sg::g_text_editl_find(a, out, room, d->num_cus, d->stream); },
-                  [&](uint64_t* e, uint64_t total) {
-                      if (sg::order_editl(e, total, off, off + n - 1, k, sg::kTEditlShift)) return true;
-                      set_error("text_editl_find: the entries are not distinct end positions of the range with distances <= %u", k);
-                      return false;
-                  },
-                  ends, cap, count);
-    if (rc == SMARTGPU_OK) unpack_mis(ends, distances, *count, sg::kTEditlShift);
-    return rc;
-}
-
-// ---- starts and alignments of edit-distance occurrences (palign.hpp): a list of END positions in, one lane each ----
-
-// copy_positions the other way: the caller's (pageable) end positions to the device through the pinned staging buffer
-bool upload_positions(DeviceCtx* d, unsigned long long* dst, const uint64_t* src, uint64_t count)
-{
-    for (uint64_t done = 0; done < count;) {
-        const uint64_t part = std::min<uint64_t>(count - done, d->pinned_bytes / 8);
-        std::memcpy(d->pinned, src + done, part * 8);
-        if (hipMemcpyAsync(dst + done, d->pinned, part * 8, hipMemcpyHostToDevice, d->stream) != hipSuccess ||
-            hipStreamSynchronize(d->stream) != hipSuccess)
-            return false;
-        done += part;
-    }
-    return true;
-}
-
-// The refusal of a listed end outside the range [off, off+n), shared by the align calls: the message names i and the value
-bool ends_in_range(const char* call, const uint64_t* ends, uint64_t count, uint64_t off, uint64_t n)
-{
-    for (uint64_t i = 0; i < count; ++i)
-        if (ends[i] < off || ends[i] - off >= n) {
-            set_error("%s: ends[%llu] = %llu outside the range [%llu,+%llu)", call, (unsigned long long)i, (unsigned long long)ends[i], (unsigned long long)off, (unsigned long long)n);
-            return false;
-        }
-    return true;
-}
-
-// Every align call.  The device works in the find's own buffer (find_reserve, at most kFindKeep entries, so never an
-// allocation per call beyond the first): a piece of `part` occurrences is [io: part entries | ops: 3 * part words], so a piece
-// is kFindKeep occurrences without ops and kFindKeep / 4 with them; longer lists go through piece after piece.
-// `launch(io, ops, part)` starts the family's kernel on d->stream over one piece.
-template <typename Launch>
-int align_pieces(const char* call, DeviceCtx* d, Launch launch, const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances,
-                 uint64_t* ops)
-{
-    const uint64_t piece = ops ? kFindKeep / 4 : kFindKeep;
-    for (uint64_t done = 0; done < count;) {
-        const uint64_t part = std::min<uint64_t>(count - done, piece);
-        bool own = false;
-        unsigned long long* buf = find_reserve(d, part * (ops ? 4 : 1), &own);
-        if (!buf) return SMARTGPU_ERR_NOMEM;
-        unsigned long long* const dev_ops = ops ? buf + part : nullptr;
-        const bool ok = upload_positions(d, buf, ends + done, part) &&
-                        launch(buf, dev_ops, part) == hipSuccess &&
-                        hipStreamSynchronize(d->stream) == hipSuccess &&
-                        copy_positions(d, starts + done, buf, part) &&
-                        (!ops || copy_positions(d, ops + 3 * done, dev_ops, 3 * part));
-        if (!ok) set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-        if (own) (void)hipFree(buf);
-        if (!ok) return SMARTGPU_ERR_HIP;
-        for (uint64_t i = done; i < done + part; ++i) {
-            const uint64_t v = starts[i];
-            const bool none = v == sg::kAlignNone;
-            starts[i] = none ? UINT64_MAX : v >> sg::kMisShift;
-            if (distances) distances[i] = none ? 255 : static_cast<uint8_t>(v & ((1u << sg::kMisShift) - 1u));
-        }
-        done += part;
-    }
-    return SMARTGPU_OK;
-}
-
-int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, &count);
-    if (rc != SMARTGPU_OK) return rc;
-    sg::PlaneEditArgs masks;
-    if ((rc = edit_masks(text, pat, m, sets, &masks)) != SMARTGPU_OK) return rc;  // (the pattern as given: the message names ITS position)
-    if (!ends_in_range(call, ends, count, off, n)) return SMARTGPU_ERR_ARG;
-    if (count == 0) return SMARTGPU_OK;
-    if (!sg::g_planes_edit_align) { set_error("%s: this program holds no planes_edit_align kernel (k_palign.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    uint8_t rev[SMARTGPU_PEDIT_MAXM];
-    for (uint32_t j = 0; j < m; ++j) rev[j] = pat[m - 1 - j];
-    (void)edit_masks(text, rev, m, sets, &masks);  // the kernel walks backward: the masks of the REVERSED pattern
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    sg::PlaneAlignArgs a;
-    edit_head(a, text, m, k, off, n);
-    std::memcpy(a.peq, masks.peq, sizeof a.peq);
-    return align_pieces(call, d,
-                        [&](unsigned long long* io, unsigned long long* dev_ops, uint64_t part) {
-                            a.io = io;
-                            a.ops = dev_ops;
-                            a.count = part;
-                            return sg::g_planes_edit_align(a, text->planes, d->stream);
-                        },
-                        ends, count, starts, distances, ops);
-}
-
-// The same on a BYTE text (talign.hpp).  The 256 masks of the REVERSED pattern travel to the arena as tedit_stage sends them;
-// the staging buffer they leave from is the one upload_positions fills next, so the stream is synchronised in between.
-int talign_run(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    const int rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_EDIT_MAXM, "edits", pat, m, k, text, off, n, &count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (!ends_in_range(call, ends, count, off, n)) return SMARTGPU_ERR_ARG;
-    if (count == 0) return SMARTGPU_OK;
-    if (!sg::g_text_edit_align) { set_error("%s: this program holds no text_edit_align kernel (k_talign.hip is not linked)", call); return SMARTGPU_ERR_HIP; }
-    uint8_t rev[32 * SMARTGPU_EDIT_MAXM];
-    if (classes) sg::talign_reverse_classes(pat, m, rev); else sg::talign_reverse_bytes(pat, m, rev);
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, kTEditArena, 1)) return SMARTGPU_ERR_NOMEM;
-    sg::TextAlignArgs a;
-    if (!tedit_stage(d, rev, classes, m, &a.peq) || hipStreamSynchronize(d->stream) != hipSuccess) {
-        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-        return SMARTGPU_ERR_HIP;
-    }
-    static_assert(sg::kTextAlignNone == sg::kAlignNone, "align_pieces unpacks both kernels' entries");
-    text_head(a, text, m, k, off, n);
-    return align_pieces(call, d,
-                        [&](unsigned long long* io, unsigned long long* dev_ops, uint64_t part) {
-                            a.io = io;
-                            a.ops = dev_ops;
-                            a.count = part;
-                            return sg::g_text_edit_align(a, d->stream);
-                        },
-                        ends, count, starts, distances, ops);
-}
-
-}  // namespace
-
-extern "C" {
-
-int smartgpu_ptext_layout(uint64_t n, int nvalues, int* planes, uint64_t* plane_bytes)
-{
-    if (nvalues < 1 || nvalues > 4) { set_error("a packed text holds 1 to 4 distinct byte values, not %d", nvalues); return SMARTGPU_ERR_ARG; }
-    if (planes) *planes = nvalues <= 2 ? 1 : 2;
-    if (plane_bytes) *plane_bytes = sg::plane_bytes(n);
-    return SMARTGPU_OK;
-}
-
-int smartgpu_ptext_layout8(uint64_t n, int nvalues, int* planes, uint64_t* plane_bytes)
-{
-    if (nvalues < 1 || nvalues > SMARTGPU_PTEXT_MAXVALUES) { set_error("a packed text of the ...8 constructors holds 1 to %d distinct byte values, not %d", SMARTGPU_PTEXT_MAXVALUES, nvalues); return SMARTGPU_ERR_ARG; }
-    if (planes) *planes = nvalues <= 2 ? 1 : nvalues <= 4 ? 2 : 3;
-    if (plane_bytes) *plane_bytes = sg::plane_bytes(n);
-    return SMARTGPU_OK;
-}
-
-// smartgpu_ptext_pack (most = 4) and smartgpu_ptext_pack8 (most = 8): at most four values give one or two planes through
-// planes_pack either way, five to eight three planes through planes3_pack.
-static smartgpu_ptext* ptext_pack_impl(const smartgpu_text* t, int most)
-{
-    if (!t) { set_error("text handle is NULL"); return nullptr; }
-    uint8_t values[8] = {255, 255, 255, 255, 255, 255, 255, 255};
-    int k = 0;
-    for (int c = 0; c < 256; ++c)
-        if (t->alphabet[c >> 5] >> (c & 31) & 1u) {
-            if (k < 8) values[k] = static_cast<uint8_t>(c);
-            ++k;
-        }
-    if (k > most) { set_error("the text holds %d distinct byte values: a packed text holds at most %d", k, most); return nullptr; }
-    if (k > 4 && !sg::g_planes3_pack) { set_error("ptext_pack8: this program holds no planes3_pack kernel (k_planes3.hip is not linked)"); return nullptr; }
-    DeviceCtx* d = device_ctx_flushed(t->device);
-    if (!d) return nullptr;
-    smartgpu_ptext* p = new smartgpu_ptext;
-    p->device = t->device;
-    p->n = t->n;
-    p->planes = k <= 2 ? 1 : k <= 4 ? 2 : 3;
-    p->nvalues = k;
-    for (int i = 0; i < k; ++i) p->values[i] = values[i];
-    if (hipMalloc(reinterpret_cast<void**>(&p->base), p->alloc_bytes()) != hipSuccess) {
-        set_error("hipMalloc of %llu bytes failed", (unsigned long long)p->alloc_bytes());
-        delete p;
-        return nullptr;
-    }
-    // code = number of these below the byte (255: none is)
-    hipError_t e = hipMemsetAsync(p->base, 0, p->alloc_bytes(), d->stream);  // pads and tail bits are zero
-    if (e == hipSuccess)
-        e = p->planes == 3 ? sg::g_planes3_pack(t->data(), t->n, p->plane(0), p->plane(1), p->plane(2), values, d->stream)
-                           : sg::launch_planes_pack(t->data(), t->n, p->plane(0), p->plane(p->planes - 1), p->planes, values, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    if (e != hipSuccess) {
-        set_error("%s failed: %s", p->planes == 3 ? "planes3_pack" : "planes_pack", hipGetErrorString(e));
-        smartgpu_ptext_free(p);
-        return nullptr;
-    }
-    return p;
-}
-
-smartgpu_ptext* smartgpu_ptext_pack(const smartgpu_text* t) { return ptext_pack_impl(t, 4); }
-smartgpu_ptext* smartgpu_ptext_pack8(const smartgpu_text* t) { return ptext_pack_impl(t, SMARTGPU_PTEXT_MAXVALUES); }
-
-smartgpu_ptext* smartgpu_ptext_upload(const void* host, uint64_t n, int device)
-{
-    smartgpu_text* t = smartgpu_text_upload(host, n, device);
-    if (!t) return nullptr;
-    smartgpu_ptext* p = smartgpu_ptext_pack(t);
-    smartgpu_text_free(t);
-    return p;
-}
-
-smartgpu_ptext* smartgpu_ptext_upload8(const void* host, uint64_t n, int device)
-{
-    smartgpu_text* t = smartgpu_text_upload(host, n, device);
-    if (!t) return nullptr;
-    smartgpu_ptext* p = smartgpu_ptext_pack8(t);
-    smartgpu_text_free(t);
-    return p;
-}
-
-void smartgpu_ptext_free(smartgpu_ptext* t)
-{
-    if (!t) return;
-    if (t->base) {
-        hipSetDevice(t->device);
-        hipFree(t->base);
-    }
-    delete t;
-}
-
-uint64_t smartgpu_ptext_length(const smartgpu_ptext* t) { return t ? t->n : 0; }
-int smartgpu_ptext_device(const smartgpu_ptext* t) { return t ? t->device : -1; }
-int smartgpu_ptext_planes(const smartgpu_ptext* t) { return t ? t->planes : 0; }
-uint64_t smartgpu_ptext_bytes(const smartgpu_ptext* t) { return t ? static_cast<uint64_t>(t->planes) * sg::plane_bytes(t->n) : 0; }
-
-int smartgpu_ptext_symbols(const smartgpu_ptext* t, uint8_t values[4])
-{
-    if (!t || !values) { set_error("bad ptext_symbols arguments"); return SMARTGPU_ERR_ARG; }
-    if (t->planes == 3) { set_error("ptext_symbols: a three-plane text holds %d values, more than the four entries of this call: use smartgpu_ptext_symbols8", t->nvalues); return SMARTGPU_ERR_ARG; }
-    std::memcpy(values, t->values, 4);
-    return t->nvalues;
-}
-
-int smartgpu_ptext_symbols8(const smartgpu_ptext* t, uint8_t values[8])
-{
-    if (!t || !values) { set_error("bad ptext_symbols8 arguments"); return SMARTGPU_ERR_ARG; }
-    std::memcpy(values, t->values, 8);
-    return t->nvalues;
-}
-
-int smartgpu_ptext_read(const smartgpu_ptext* t, uint64_t off, uint64_t len, void* host)
-{
-    if (!t || (!host && len) || off > t->n || len > t->n - off) { set_error("bad ptext_read range"); return SMARTGPU_ERR_ARG; }
-    if (len == 0) return SMARTGPU_OK;
-    DeviceCtx* d = device_ctx_flushed(t->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    HIP_TRY(hipStreamSynchronize(d->stream), return SMARTGPU_ERR_HIP);
-    const uint64_t w0 = off / 32, nw = (off + len + 31) / 32 - w0;
-    std::vector<uint32_t> w[3];
-    for (int b = 0; b < t->planes; ++b) {
-        w[b].resize(nw);
-        HIP_TRY(hipMemcpy(w[b].data(), t->plane(b) + w0, nw * 4, hipMemcpyDeviceToHost), return SMARTGPU_ERR_HIP);
-    }
-    uint8_t* out = static_cast<uint8_t*>(host);
-    for (uint64_t i = 0; i < len; ++i) {
-        const uint64_t s = off + i - 32 * w0;
-        uint32_t code = w[0][s >> 5] >> (s & 31) & 1u;
-        if (t->planes >= 2) code |= (w[1][s >> 5] >> (s & 31) & 1u) << 1;
-        if (t->planes == 3) code |= (w[2][s >> 5] >> (s & 31) & 1u) << 2;
-        out[i] = t->values[code];
-    }
-    return SMARTGPU_OK;
-}
-
-int smartgpu_ptext_probe_read_ms(const smartgpu_ptext* t, int reps, double* ms_per_pass)
-{
-    if (!t || reps < 1 || !ms_per_pass) { set_error("bad probe arguments"); return SMARTGPU_ERR_ARG; }
-    DeviceCtx* d = device_ctx_flushed(t->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    // the planes and the pad between them: one contiguous region of the allocation
-    const uint8_t* first = reinterpret_cast<const uint8_t*>(t->plane(0));
-    const uint64_t bytes = static_cast<uint64_t>(t->planes - 1) * sg::plane_stride(t->n) + sg::plane_bytes(t->n);
-    if (!batch_reserve(d, 0, 1)) return SMARTGPU_ERR_NOMEM;
-    // (the sink: probe_read adds to it practically never; every search zeroes its slots first)
-    return probe_read_ms(d, first, bytes, d->batch_counts, reps, ms_per_pass);
-}
-
-int smartgpu_psearch64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n, uint64_t* count,
-                       double* pre_ms, double* run_ms)
-{
-    const int rc = check_psearch_args(P, m, text, off, n);
-    if (rc != SMARTGPU_OK) return rc;
-    const uint8_t* set[1] = {P};
-    uint64_t c = 0;
-    double pre = 0.0, run = 0.0;
-    const int r = psearch_impl(set, m, 1, text, off, n, &c, &pre, &run);
-    if (r != SMARTGPU_OK) return r;
-    return pcount_done(c, pre, run, count, pre_ms, run_ms);
-}
-
-int smartgpu_psearch_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                             uint64_t* counts, double* batch_ms)
-{
-    if (!P || K < 1 || !counts) { set_error("psearch_batch: P/counts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
-    int rc = check_psearch_args(P[0], m, text, off, n);
-    if (rc != SMARTGPU_OK) return rc;
-    if ((rc = check_batch3("psearch_batch", text, K)) != SMARTGPU_OK) return rc;
-    double pre = 0.0, run = 0.0;
-    const int r = psearch_impl(P, m, K, text, off, n, counts, &pre, &run);
-    if (r != SMARTGPU_OK) return r;
-    if (batch_ms) *batch_ms = run;
-    g_last_pre_ms = pre / K;
-    g_last_run_ms = run / K;
-    return SMARTGPU_OK;
-}
-
-/* ---- occurrence positions on a packed text (planes_find) ---------------------------------------------------------- */
-int smartgpu_pfind64(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                     uint64_t* positions, uint64_t cap, uint64_t* count)
-{
-    const int rc = check_psearch_args(P, m, text, off, n);
-    if (rc != SMARTGPU_OK) return rc;
-    if (!count || (cap && !positions)) { set_error("pfind64: count must not be NULL, positions only with cap = 0"); return SMARTGPU_ERR_ARG; }
-    if (text->planes == 3) return p3_find("pfind64", P, false, false, m, 0, text, off, n, positions, nullptr, cap, count);
-    uint32_t X[2 * sg::kPatWords];
-    if (sg::encode_pattern(text->values, text->nvalues, P, m, X, X + sg::kPatWords, nullptr) || m > n) {
-        *count = 0;  // a byte the text does not hold, or no window fits: no launch
-        return SMARTGPU_OK;
-    }
-    sg::PlaneArgs a;
-    a.x0 = X[0];
-    a.x1 = X[sg::kPatWords];
-    return pfind_run("pfind64","planes_find", sg::launch_planes_find, a, text, X, sizeof X, m, off, n, positions, cap, count);
-}
-
-int smartgpu_pfind_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                           uint64_t* positions, uint64_t cap, uint64_t* starts)
-{
-    if (!P || K < 1 || !starts) { set_error("pfind_batch: P/starts NULL or K = 0"); return SMARTGPU_ERR_ARG; }
-    int rc = check_psearch_args(P[0], m, text, off, n);
-    if (rc != SMARTGPU_OK) return rc;
-    if (cap && !positions) { set_error("pfind_batch: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
-    if ((rc = check_batch3("pfind_batch", text, K)) != SMARTGPU_OK) return rc;
-    // pass 1: the K counts (the planes are read twice: a one-pass ordered batch is not built)
-    std::vector<uint64_t> counts(K);
-    const int r1 = psearch_impl(P, m, K, text, off, n, counts.data(), nullptr, nullptr);
-    if (r1 != SMARTGPU_OK) return r1;
-    starts[0] = 0;
-    for (uint32_t k = 0; k < K; ++k) starts[k + 1] = starts[k] + counts[k];
-    const uint64_t total = starts[K];
-    if (total > cap) { set_error("pfind_batch: %llu occurrences, room for %llu", (unsigned long long)total, (unsigned long long)cap); return SMARTGPU_ERR_NOMEM; }
-    if (total == 0) return SMARTGPU_OK;
-    // pass 2: a find for every pattern that occurs, each with its own cursor and its own slice as base and cap.  The
-    // patterns' planes are where psearch_impl left them: the staging buffer and, for m > 32, the arena.
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    const uint32_t* host_pat = reinterpret_cast<const uint32_t*>(d->pinned);
-    bool own = false;
-    unsigned long long* out = find_reserve(d, total, &own);
-    if (!out) return SMARTGPU_ERR_NOMEM;
-    bool ok = hipMemsetAsync(d->batch_counts, 0, static_cast<size_t>(K) * 8, d->stream) == hipSuccess;
-    for (uint32_t k = 0; k < K && ok; ++k) {
-        if (counts[k] == 0) continue;
-        if (text->planes == 3) {  // (linked: psearch3_impl has counted)
-            const sg::Plane3Args a = plane3_args(d, text, host_pat, k, m, off, n);
-            ok = sg::g_planes3_find(a, out + starts[k], counts[k], text->planes, d->num_cus, d->stream) == hipSuccess;
-            continue;
-        }
-        const sg::PlaneArgs a = plane_args(d, text, host_pat, k, m, off, n);
-        ok = sg::launch_planes_find(a, out + starts[k], counts[k], text->planes, d->num_cus, d->stream) == hipSuccess;
-    }
-    ok = ok && hipMemcpyAsync(d->pinned_counts, d->batch_counts, static_cast<size_t>(K) * 8, hipMemcpyDeviceToHost, d->stream) == hipSuccess &&
-         hipStreamSynchronize(d->stream) == hipSuccess && copy_positions(d, positions, out, total);
-    int r = SMARTGPU_OK;
-    if (!ok) {
-        set_error("pfind_batch: %s", hipGetErrorString(hipGetLastError()));
-        r = SMARTGPU_ERR_HIP;
-    }
-    for (uint32_t k = 0; k < K && r == SMARTGPU_OK; ++k) {
-        if (d->pinned_counts[k] != counts[k]) {  // the two passes disagree: refused, never reported
-            set_error("planes_find: pattern %u: cursor %llu, planes_scan counted %llu", k, d->pinned_counts[k], (unsigned long long)counts[k]);
-            r = SMARTGPU_ERR_HIP;
-        } else if (!sg::order_spans(positions + starts[k], counts[k], off, off + n - m)) {
-            set_error("planes_find: pattern %u: the positions are not ascending spans of %llu start positions", k, (unsigned long long)sg::kFindSpan);
-            r = SMARTGPU_ERR_HIP;
-        }
-    }
-    if (own) (void)hipFree(out);
-    return r;
-}
-
 /* ---- occurrence positions of a pattern set on a BYTE text (k_hormf.hip: hor_multi_find) ----------------------------- */
 // smartgpu_pfind_batch64's contract, asked of a smartgpu_text.  The set goes through the staging buffer into the arena
 // once (rows, and whole patterns where a window is completed in memory); its passes, find_width(m) patterns each, run
@@ -3222,342 +1978,6 @@ int smartgpu_find_batch64(const uint8_t* const* P, uint32_t m, uint32_t K, const
     }
     if (own) (void)hipFree(out);
     return r;
-}
-
-/* ---- set patterns: every pattern position accepts a set of the text's values ---------------------------------------- */
-int smartgpu_psearch_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                            uint64_t* count, double* pre_ms, double* run_ms)
-{
-    int rc = check_pext_args("psearch_sets64", "sets", sets, m, 0, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (text->planes == 3) return p3_count("psearch_sets64", sets, true, false, m, 0, text, off, n, count, pre_ms, run_ms);
-    uint32_t Y[sg::kSetWords], empty = 0;
-    bool full = false;
-    if ((rc = sets_planes(text, sets, m, false, Y, &empty, &full)) != SMARTGPU_OK) return rc;
-    if (empty || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);  // a position that accepts nothing, or no window fits: no launch
-    if (full) return pcount_done(n - m + 1, 0.0, 0.0, count, pre_ms, run_ms);    // every start position of the range: no launch
-    sg::PlaneSetArgs a;
-    set_words(a, Y);
-    return pcount_run("psearch_sets64", "planes_sets_scan", sg::launch_planes_sets_scan, a, text, Y, sizeof Y, m, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_pfind_sets64(const uint8_t* sets, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                          uint64_t* positions, uint64_t cap, uint64_t* count)
-{
-    if (cap && !positions) { set_error("pfind_sets64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
-    int rc = check_pext_args("pfind_sets64", "sets", sets, m, 0, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (text->planes == 3) return p3_find("pfind_sets64", sets, true, false, m, 0, text, off, n, positions, nullptr, cap, count);
-    uint32_t Y[sg::kSetWords], empty = 0;
-    bool full = false;
-    if ((rc = sets_planes(text, sets, m, false, Y, &empty, &full)) != SMARTGPU_OK) return rc;
-    if (empty || m > n) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    if (full) return find_every_start("pfind_sets64", off, n - m + 1, positions, cap, count);
-    sg::PlaneSetArgs a;
-    set_words(a, Y);
-    return pfind_run("pfind_sets64", "planes_sets_find", sg::launch_planes_sets_find, a, text, Y, sizeof Y, m, off, n, positions, cap, count);
-}
-
-/* ---- mismatches: occurrences within Hamming distance k ---------------------------------------------------------------- */
-int smartgpu_psearch_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                           uint64_t* count, double* pre_ms, double* run_ms)
-{
-    const int rc = check_pext_args("psearch_mis64", "P", P, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (text->planes == 3) return p3_count("psearch_mis64", P, false, true, m, k, text, off, n, count, pre_ms, run_ms);
-    uint32_t X[kMisWords];
-    sg::PlaneMisArgs a;
-    a.foreign = mis_planes(text, P, m, X, &a);
-    // more foreign bytes than mismatches allowed, or no window fits: no launch
-    if (a.foreign > k || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);
-    a.budget = k - a.foreign;
-    return pcount_run("psearch_mis64", "planes_mis_scan", sg::launch_planes_mis_scan, a, text, X, sizeof X, m, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_pfind_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                         uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
-{
-    if (cap && !positions) { set_error("pfind_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
-    const int rc = check_pext_args("pfind_mis64", "P", P, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (text->planes == 3) return p3_find("pfind_mis64", P, false, true, m, k, text, off, n, positions, mismatches, cap, count);
-    uint32_t X[kMisWords];
-    sg::PlaneMisArgs a;
-    a.foreign = mis_planes(text, P, m, X, &a);
-    if (a.foreign > k || m > n) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    a.budget = k - a.foreign;
-    const int r = pfind_run("pfind_mis64", "planes_mis_find", sg::launch_planes_mis_find, a, text, X, sizeof X, m, off, n, positions, cap, count,
-                            sg::kMisShift);
-    if (r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
-    return r;
-}
-
-/* ---- set patterns with mismatches: at most k positions whose symbol is no member of the position's set ---------------- */
-int smartgpu_psearch_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                                uint64_t* count, double* pre_ms, double* run_ms)
-{
-    int rc = check_pext_args("psearch_sets_mis64", "sets", sets, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (text->planes == 3) return p3_count("psearch_sets_mis64", sets, true, true, m, k, text, off, n, count, pre_ms, run_ms);
-    uint32_t Y[sg::kSetWords];
-    bool full = false;
-    sg::PlaneSetMisArgs a;
-    if ((rc = sets_planes(text, sets, m, true, Y, &a.foreign, &full)) != SMARTGPU_OK) return rc;
-    // more empty sets than mismatches allowed, or no window fits: no launch
-    if (a.foreign > k || m > n) return pcount_done(0, 0.0, 0.0, count, pre_ms, run_ms);
-    a.budget = k - a.foreign;
-    set_words(a, Y);
-    return pcount_run("psearch_sets_mis64", "planes_sets_mis_scan", sg::launch_planes_sets_mis_scan, a, text, Y, sizeof Y, m, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_pfind_sets_mis64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                              uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
-{
-    if (cap && !positions) { set_error("pfind_sets_mis64: positions NULL with cap > 0"); return SMARTGPU_ERR_ARG; }
-    int rc = check_pext_args("pfind_sets_mis64", "sets", sets, m, k, text, off, n, count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (text->planes == 3) return p3_find("pfind_sets_mis64", sets, true, true, m, k, text, off, n, positions, mismatches, cap, count);
-    uint32_t Y[sg::kSetWords];
-    bool full = false;
-    sg::PlaneSetMisArgs a;
-    if ((rc = sets_planes(text, sets, m, true, Y, &a.foreign, &full)) != SMARTGPU_OK) return rc;
-    if (a.foreign > k || m > n) {
-        *count = 0;
-        return SMARTGPU_OK;
-    }
-    a.budget = k - a.foreign;
-    set_words(a, Y);
-    const int r = pfind_run("pfind_sets_mis64", "planes_sets_mis_find", sg::launch_planes_sets_mis_find, a, text, Y, sizeof Y, m, off, n, positions,
-                            cap, count, sg::kMisShift);
-    if (r == SMARTGPU_OK) unpack_mis(positions, mismatches, *count);
-    return r;
-}
-
-/* ---- edit distance: end positions within k substitutions, insertions and deletions (pedit.hpp, k_pedit.hip) ------------ */
-int smartgpu_psearch_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                            uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return pedit_count("psearch_edit64", P, false, m, k, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_pfind_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                          uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return pedit_find("pfind_edit64", P, false, m, k, text, off, n, ends, distances, cap, count);
-}
-
-int smartgpu_psearch_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                                 uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return pedit_count("psearch_sets_edit64", sets, true, m, k, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_pfind_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                               uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return pedit_find("pfind_sets_edit64", sets, true, m, k, text, off, n, ends, distances, cap, count);
-}
-
-/* ---- edit distance on byte texts: the same question of a smartgpu_text (tedit.hpp, k_tedit.hip) ------------------------- */
-int smartgpu_search_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                           uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return tedit_count("search_edit64", P, false, m, k, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_find_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                         uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return tedit_find("find_edit64", P, false, m, k, text, off, n, ends, distances, cap, count);
-}
-
-int smartgpu_search_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                                   uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return tedit_count("search_edit_classes64", classes, true, m, k, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_find_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                                 uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return tedit_find("find_edit_classes64", classes, true, m, k, text, off, n, ends, distances, cap, count);
-}
-
-/* ---- edit distance on byte texts, long patterns: m <= 256, k <= 31 (teditl.hpp, k_teditl.hip) --------------------------- */
-int smartgpu_search_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off, uint64_t n,
-                            uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return teditl_count("search_editl64", P, false, m, k, flags, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_find_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off, uint64_t n,
-                          uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return teditl_find("find_editl64", P, false, m, k, flags, text, off, n, ends, distances, cap, count);
-}
-
-int smartgpu_search_editl_classes64(const uint8_t* classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
-                                    uint64_t n, uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return teditl_count("search_editl_classes64", classes, true, m, k, flags, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_find_editl_classes64(const uint8_t* classes, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off,
-                                  uint64_t n, uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return teditl_find("find_editl_classes64", classes, true, m, k, flags, text, off, n, ends, distances, cap, count);
-}
-
-/* ---- mismatches on byte texts: smartgpu_psearch_mis64's question of a smartgpu_text (tmis.hpp, k_tmis.hip) --------------- */
-int smartgpu_search_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                          uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return tmis_count("search_mis64", P, false, m, k, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_find_mis64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                        uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
-{
-    return tmis_find("find_mis64", P, false, m, k, text, off, n, positions, mismatches, cap, count);
-}
-
-int smartgpu_search_mis_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                                  uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return tmis_count("search_mis_classes64", classes, true, m, k, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_find_mis_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                                uint64_t* positions, uint8_t* mismatches, uint64_t cap, uint64_t* count)
-{
-    return tmis_find("find_mis_classes64", classes, true, m, k, text, off, n, positions, mismatches, cap, count);
-}
-
-/* ---- edit distance, long patterns: m <= 256, k <= 31 (peditl.hpp, k_peditl.hip) ---------------------------------------- */
-int smartgpu_psearch_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                             uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return peditl_count("psearch_editl64", P, false, m, k, flags, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_pfind_editl64(const uint8_t* P, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                           uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return peditl_find("pfind_editl64", P, false, m, k, flags, text, off, n, ends, distances, cap, count);
-}
-
-int smartgpu_psearch_sets_editl64(const uint8_t* sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                                  uint64_t* count, double* pre_ms, double* run_ms)
-{
-    return peditl_count("psearch_sets_editl64", sets, true, m, k, flags, text, off, n, count, pre_ms, run_ms);
-}
-
-int smartgpu_pfind_sets_editl64(const uint8_t* sets, uint32_t m, uint32_t k, uint32_t flags, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                                uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
-{
-    return peditl_find("pfind_sets_editl64", sets, true, m, k, flags, text, off, n, ends, distances, cap, count);
-}
-
-/* ---- edit distance: start positions and alignments of listed end positions (palign.hpp, k_palign.hip) ------------------ */
-int smartgpu_palign_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                           const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return palign_run("palign_edit64", P, false, m, k, text, off, n, ends, count, starts, distances, ops);
-}
-
-int smartgpu_palign_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                                const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return palign_run("palign_sets_edit64", sets, true, m, k, text, off, n, ends, count, starts, distances, ops);
-}
-
-/* ---- the same on byte texts (talign.hpp, k_talign.hip) ------------------------------------------------------------------ */
-int smartgpu_align_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                          const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return talign_run("align_edit64", P, false, m, k, text, off, n, ends, count, starts, distances, ops);
-}
-
-int smartgpu_align_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                                  const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return talign_run("align_edit_classes64", classes, true, m, k, text, off, n, ends, count, starts, distances, ops);
-}
-
-// smartgpu_iupac_sets (most = 4) and smartgpu_iupac_sets8 (most = 8): one set of rules
-static int iupac_sets_impl(const char* call, int most, const uint8_t* values, int nvalues, const char* P, uint32_t m, uint8_t* sets)
-{
-    if (!values || (m && (!P || !sets))) { set_error("%s: NULL argument", call); return SMARTGPU_ERR_ARG; }
-    if (nvalues < 1 || nvalues > most) { set_error("%s: a packed text holds 1 to %d distinct byte values, not %d", call, most, nvalues); return SMARTGPU_ERR_ARG; }
-    // the bases a letter accepts, bit 0..3 = A C G T
-    static const struct { char letter; uint8_t bases; } kIupac[] = {
-        {'A', 1}, {'C', 2}, {'G', 4}, {'T', 8}, {'U', 8}, {'R', 1 | 4}, {'Y', 2 | 8}, {'S', 2 | 4}, {'W', 1 | 8}, {'K', 4 | 8}, {'M', 1 | 2},
-        {'B', 2 | 4 | 8}, {'D', 1 | 4 | 8}, {'H', 1 | 2 | 8}, {'V', 1 | 2 | 4}, {'N', 15}};
-    int bases_of[256];
-    for (int c = 0; c < 256; ++c) bases_of[c] = -1;
-    for (const auto& e : kIupac) bases_of[(uint8_t)e.letter] = bases_of[(uint8_t)(e.letter | 0x20)] = e.bases;
-    uint8_t base_of_code[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the base (one bit) value v stands for; 0: none (N, a separator)
-    for (int v = 0; v < nvalues; ++v) {
-        const int b = bases_of[values[v]];
-        if (b == 1 || b == 2 || b == 4 || b == 8) base_of_code[v] = static_cast<uint8_t>(b);
-    }
-    for (uint32_t j = 0; j < m; ++j)
-        if (bases_of[(uint8_t)P[j]] < 0) {
-            set_error("%s: position %u: byte 0x%02x is no IUPAC nucleotide letter", call, j, (unsigned)(uint8_t)P[j]);
-            return SMARTGPU_ERR_ARG;
-        }
-    for (uint32_t j = 0; j < m; ++j) {
-        uint8_t s = 0;
-        for (int v = 0; v < nvalues; ++v)
-            if (bases_of[(uint8_t)P[j]] & base_of_code[v]) s |= static_cast<uint8_t>(1u << v);
-        sets[j] = s;
-    }
-    return SMARTGPU_OK;
-}
-
-int smartgpu_iupac_sets(const uint8_t values[4], int nvalues, const char* P, uint32_t m, uint8_t* sets)
-{
-    return iupac_sets_impl("iupac_sets", 4, values, nvalues, P, m, sets);
-}
-
-int smartgpu_iupac_sets8(const uint8_t values[8], int nvalues, const char* P, uint32_t m, uint8_t* sets)
-{
-    return iupac_sets_impl("iupac_sets8", SMARTGPU_PTEXT_MAXVALUES, values, nvalues, P, m, sets);
-}
-
-int smartgpu_iupac_revcomp(const char* P, uint32_t m, char* out)
-{
-    if (m && (!P || !out)) { set_error("iupac_revcomp: NULL argument"); return SMARTGPU_ERR_ARG; }
-    // the complement of every letter smartgpu_iupac_sets accepts; U reads as T
-    static const char kPairs[][2] = {{'A', 'T'}, {'T', 'A'}, {'U', 'A'}, {'C', 'G'}, {'G', 'C'}, {'R', 'Y'}, {'Y', 'R'}, {'K', 'M'}, {'M', 'K'},
-                                     {'B', 'V'}, {'V', 'B'}, {'D', 'H'}, {'H', 'D'}, {'S', 'S'}, {'W', 'W'}, {'N', 'N'}};
-    char comp[256] = {0};
-    for (const auto& e : kPairs) {
-        comp[(uint8_t)e[0]] = e[1];
-        comp[(uint8_t)(e[0] | 0x20)] = static_cast<char>(e[1] | 0x20);  // case is preserved
-    }
-    for (uint32_t j = 0; j < m; ++j)
-        if (!comp[(uint8_t)P[j]]) {
-            set_error("iupac_revcomp: position %u: byte 0x%02x is no IUPAC nucleotide letter", j, (unsigned)(uint8_t)P[j]);
-            return SMARTGPU_ERR_ARG;
-        }
-    if (out == P) {  // in place: swap the ends
-        for (uint32_t i = 0, j = m; i < j; ++i) {
-            --j;
-            const char lo = comp[(uint8_t)P[i]], hi = comp[(uint8_t)P[j]];
-            out[i] = hi;
-            out[j] = lo;
-        }
-    } else {
-        for (uint32_t j = 0; j < m; ++j) out[j] = comp[(uint8_t)P[m - 1 - j]];
-    }
-    return SMARTGPU_OK;
 }
 
 }  // extern "C"

@@ -177,7 +177,7 @@ static hipError_t launch_planes_edit_align(const PlaneAlignArgs& a, int planes, 
     return hipGetLastError();
 }
 
-// api.cpp reaches the launcher once this unit is part of the program (palign.hpp)
+// match_calls.cpp reaches the launcher once this unit is part of the program (palign.hpp)
 namespace {
 struct RegisterPlanesAlign {
     RegisterPlanesAlign() { g_planes_edit_align = &launch_planes_edit_align; }

@@ -199,7 +199,7 @@ static hipError_t launch_planes_edit_find(const PlaneEditArgs& a, unsigned long 
     return hipGetLastError();
 }
 
-// api.cpp reaches the launchers once this unit is part of the program (pedit.hpp)
+// match_calls.cpp reaches the launchers once this unit is part of the program (pedit.hpp)
 namespace {
 struct RegisterPlanesEdit {
     RegisterPlanesEdit()

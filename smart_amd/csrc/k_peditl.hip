@@ -204,7 +204,7 @@ static hipError_t launch_planes_editl_find(const PlaneEditlArgs& a, unsigned lon
     return hipGetLastError();
 }
 
-// api.cpp reaches the launchers once this unit is part of the program (peditl.hpp)
+// match_calls.cpp reaches the launchers once this unit is part of the program (peditl.hpp)
 namespace {
 struct RegisterPlanesEditl {
     RegisterPlanesEditl()

@@ -230,7 +230,7 @@ hipError_t launch_planes_scan(const PlaneArgs& a, int planes, int num_cus, hipSt
 // ordinary vector stores while slot < cap.  Entries beyond cap are dropped, the cursor counts them all the same.
 // A span — one wave, one chunk row: kFindSpan start positions from the range's first chunk on — is contiguous and ascending
 // in `out`; the spans of a launch cover disjoint position ranges and lie in the order their waves reserved them (the host
-// orders them by their first entry, api.cpp).  No LDS, no scratch.
+// orders them by their first entry, match_calls.cpp).  No LDS, no scratch.
 // ---------------------------------------------------------------------------
 static_assert(kFindSpan == 64 * 32 * kChunk, "a span of planes_find: one wave's lanes, one chunk each");
 static_assert(kPlanesT % 64 == 0, "every wave's chunk row starts a multiple of 64 chunks behind the range's first: the host's span number");
@@ -572,7 +572,7 @@ hipError_t launch_planes_sets_find(const PlaneSetArgs& a, unsigned long long* ou
 // Positions outside the range start with their S bit set.  After every eight symbols the wave leaves when all of its
 // positions are over budget: later than the exact scan, the more so the larger the budget.
 // Symbols from the 32nd on: planes_mis_verify.  The find's entries are pos << 3 | distance: monotone in pos, so the spans
-// are ordered on the host as planes_find's (api.cpp order_spans, with a shift).
+// are ordered on the host as planes_find's (match_calls.cpp order_spans, with a shift).
 // kUnroll: planes_scan's (2 chunks per trip).  Occupancy: planes_scan's 8 workgroups per CU (39-63 VGPRs) — except BITS = 3
 // on TWO planes, which keeps 3 * kChunk * kUnroll counter dwords beside both planes' words and does not fit 64 VGPRs
 // without scratch (67 / 69 for scan / find): it is bounded for 128 and launched at 7 workgroups per CU.  Neither choice is swept.  planes_scan,

@@ -414,7 +414,7 @@ static hipError_t launch_planes3_find(const Plane3Args& a, unsigned long long* o
     return hipGetLastError();
 }
 
-// api.cpp reaches the launchers once this unit is part of the program (planes3.hpp)
+// match_calls.cpp reaches the launchers once this unit is part of the program (planes3.hpp)
 namespace {
 struct RegisterPlanes3 {
     RegisterPlanes3()

@@ -163,7 +163,7 @@ static hipError_t launch_text_edit_align(const TextAlignArgs& a, hipStream_t str
     return hipGetLastError();
 }
 
-// api.cpp reaches the launcher once this unit is part of the program (talign.hpp)
+// match_calls.cpp reaches the launcher once this unit is part of the program (talign.hpp)
 namespace {
 struct RegisterTextAlign {
     RegisterTextAlign() { g_text_edit_align = &launch_text_edit_align; }

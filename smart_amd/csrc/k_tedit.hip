@@ -202,7 +202,7 @@ static hipError_t launch_text_edit_find(const TextEditArgs& a, unsigned long lon
     return hipGetLastError();
 }
 
-// api.cpp reaches the launchers once this unit is part of the program (tedit.hpp)
+// match_calls.cpp reaches the launchers once this unit is part of the program (tedit.hpp)
 namespace {
 struct RegisterTextEdit {
     RegisterTextEdit()

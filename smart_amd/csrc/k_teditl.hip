@@ -222,7 +222,7 @@ static hipError_t launch_text_editl_find(const TextEditlArgs& a, unsigned long l
     return hipGetLastError();
 }
 
-// api.cpp reaches the launchers once this unit is part of the program (teditl.hpp)
+// match_calls.cpp reaches the launchers once this unit is part of the program (teditl.hpp)
 namespace {
 struct RegisterTextEditl {
     RegisterTextEditl()

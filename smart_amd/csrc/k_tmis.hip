@@ -218,7 +218,7 @@ static hipError_t launch_text_mis_find(const TextMisArgs& a, unsigned long long*
     return hipGetLastError();
 }
 
-// api.cpp reaches the launchers once this unit is part of the program (tmis.hpp)
+// match_calls.cpp reaches the launchers once this unit is part of the program (tmis.hpp)
 namespace {
 struct RegisterTextMis {
     RegisterTextMis()

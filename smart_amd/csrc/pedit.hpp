@@ -29,8 +29,8 @@ static_assert(kFindSpan == 64 * kEditRun, "a span: one wave's lanes, one run eac
 
 // Grid: a workgroup of 256 lanes per 256 runs, at most 8 per CU.  The find's entries are (e << kMisShift) | D(e).
 // The launchers of k_pedit.hip are reached through pointers that the unit's own static initialiser sets (as multi.hpp's
-// g_hor_multi): api.cpp holds them — null: the edit calls answer SMARTGPU_ERR_HIP, they never fall back to anything — so a
-// program that includes api.cpp without k_pedit.hip still links.
+// g_hor_multi): match_calls.cpp holds them — null: the edit calls answer SMARTGPU_ERR_HIP, they never fall back to anything — so a
+// program that includes match_calls.cpp without k_pedit.hip still links.
 extern hipError_t (*g_planes_edit_scan)(const PlaneEditArgs& a, int planes, int num_cus, hipStream_t stream);
 extern hipError_t (*g_planes_edit_find)(const PlaneEditArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,
                                         hipStream_t stream);

@@ -1,4 +1,4 @@
-// pedit_host.hpp — what the edit-distance calls of api.cpp decide on the host before a launch: the pattern as the masks
+// pedit_host.hpp — what the edit-distance calls of match_calls.cpp decide on the host before a launch: the pattern as the masks
 // Peq the recurrence of edit_step.hpp consumes.  Host only: no HIP call, no error text — tests/packed_edit_check.cpp runs
 // it without a device.
 #pragma once

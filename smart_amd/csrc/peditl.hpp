@@ -43,7 +43,7 @@ constexpr uint32_t kEditlShift = 5;
 static_assert(kEditlMaxK < (1u << kEditlShift), "a distance fits below the position");
 
 // Grid: a workgroup of 256 lanes per 256 runs, at most 8 per CU.  The launchers of k_peditl.hip are reached through
-// pointers that the unit's own static initialiser sets (as pedit.hpp's): api.cpp holds them — null: the editl calls answer
+// pointers that the unit's own static initialiser sets (as pedit.hpp's): match_calls.cpp holds them — null: the editl calls answer
 // SMARTGPU_ERR_HIP, they never fall back to anything.
 extern hipError_t (*g_planes_editl_scan)(const PlaneEditlArgs& a, int planes, int num_cus, hipStream_t stream);
 extern hipError_t (*g_planes_editl_find)(const PlaneEditlArgs& a, unsigned long long* out, unsigned long long cap, int planes, int num_cus,

@@ -1,4 +1,4 @@
-// peditl_host.hpp — what the long-pattern edit-distance calls of api.cpp decide on the host before a launch: the pattern
+// peditl_host.hpp — what the long-pattern edit-distance calls of match_calls.cpp decide on the host before a launch: the pattern
 // as the masks Peq the recurrence of edit_block.hpp consumes — pedit_host.hpp's, eight dwords wide.  Host only: no HIP
 // call, no error text — tests/packed_editl_check.cpp runs it without a device.
 #pragma once

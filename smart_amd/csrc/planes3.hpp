@@ -56,8 +56,8 @@ static_assert(mem2_table(1) == 0x10 && mem2_table(2) == 0x40 && mem2_table(4) ==
               "singleton sets: planes_kill's and planes_mis_add's tables");
 
 // The launchers of k_planes3.hip are reached through pointers that the unit's own static initialiser sets (as pedit.hpp's):
-// api.cpp holds them — null: the calls on a three-plane text answer SMARTGPU_ERR_HIP, they never fall back to anything —
-// so a program that includes api.cpp without k_planes3.hip still links.
+// match_calls.cpp holds them — null: the calls on a three-plane text answer SMARTGPU_ERR_HIP, they never fall back to anything —
+// so a program that includes match_calls.cpp without k_planes3.hip still links.
 // byte text -> three planes.  values[0..6]: the byte values of codes 0..6 (255 where the text has fewer: no byte is
 // greater); the text's back pad (zero bytes) is read up to 31 bytes beyond n, the planes must be zero-filled before
 extern hipError_t (*g_planes3_pack)(const uint8_t* text, uint64_t n, uint32_t* p0, uint32_t* p1, uint32_t* p2, const uint8_t values[7],

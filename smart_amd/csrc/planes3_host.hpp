@@ -1,4 +1,4 @@
-// planes3_host.hpp — what the calls of api.cpp on a THREE-PLANE packed text decide on the host before a launch: the
+// planes3_host.hpp — what the calls of match_calls.cpp on a THREE-PLANE packed text decide on the host before a launch: the
 // pattern as eight membership planes.  Host only: no HIP call, no error text — tests/packed_wide_check.cpp runs it all
 // without a device.  The layout is planes3.hpp's; the find's spans are ordered by planes_host.hpp's order_spans.
 #pragma once

@@ -1,4 +1,4 @@
-// planes_host.hpp — what the packed-text calls of api.cpp decide on the host before (the pattern as planes) and after
+// planes_host.hpp — what the packed-text calls of match_calls.cpp decide on the host before (the pattern as planes) and after
 // (what a find's cursor means, the find's entries in order) a launch.  Host only: no HIP call, no error text —
 // tests/packed_host_check.cpp runs it all without a device.  The planes' layout is planes.hpp's.
 #pragma once

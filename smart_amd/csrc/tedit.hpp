@@ -22,7 +22,7 @@ struct TextEditArgs {
 };
 
 // The launchers of k_tedit.hip are reached through pointers that the unit's own static initialiser sets (as pedit.hpp's):
-// api.cpp holds them — null: the calls answer SMARTGPU_ERR_HIP, they never fall back to anything.
+// match_calls.cpp holds them — null: the calls answer SMARTGPU_ERR_HIP, they never fall back to anything.
 extern hipError_t (*g_text_edit_scan)(const TextEditArgs& a, int num_cus, hipStream_t stream);
 extern hipError_t (*g_text_edit_find)(const TextEditArgs& a, unsigned long long* out, unsigned long long cap, int num_cus, hipStream_t stream);
 

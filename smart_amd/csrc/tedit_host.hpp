@@ -1,4 +1,4 @@
-// tedit_host.hpp — byte texts: what the edit-distance calls of api.cpp (smartgpu_search_edit64 and its kin) decide on the
+// tedit_host.hpp — byte texts: what the edit-distance calls of match_calls.cpp (smartgpu_search_edit64 and its kin) decide on the
 // host before a launch, and the run geometry the kernels of k_tedit.hip share with it.  The pattern becomes 256 masks, one
 // per byte value, which the recurrence of edit_step.hpp consumes; a lane's run becomes three numbers.  No HIP call, no
 // error text — tests/text_edit_check.cpp runs all of it without a device.

@@ -49,7 +49,7 @@ constexpr uint32_t kTEditlShift = 5;
 static_assert(kTEditlMaxK < (1u << kTEditlShift), "a distance fits below the position");
 
 // The launchers of k_teditl.hip are reached through pointers that the unit's own static initialiser sets (as tedit.hpp's):
-// api.cpp holds them — null: the calls answer SMARTGPU_ERR_HIP, they never fall back to anything.
+// match_calls.cpp holds them — null: the calls answer SMARTGPU_ERR_HIP, they never fall back to anything.
 extern hipError_t (*g_text_editl_scan)(const TextEditlArgs& a, int num_cus, hipStream_t stream);
 extern hipError_t (*g_text_editl_find)(const TextEditlArgs& a, unsigned long long* out, unsigned long long cap, int num_cus, hipStream_t stream);
 

@@ -1,4 +1,4 @@
-// teditl_host.hpp — byte texts, LONG patterns: what the calls of api.cpp (smartgpu_search_editl64 and its kin) decide on the
+// teditl_host.hpp — byte texts, LONG patterns: what the calls of match_calls.cpp (smartgpu_search_editl64 and its kin) decide on the
 // host before a launch, and the geometry the kernels of k_teditl.hip share with it.  The pattern becomes 256 masks of up to
 // eight dwords, which the block recurrence of edit_block.hpp consumes one dword per active block; a lane's run becomes three
 // numbers; a range becomes a number of super-tiles.  No HIP call, no error text — tests/text_editl_check.cpp runs all of it

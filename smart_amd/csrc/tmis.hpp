@@ -24,7 +24,7 @@ struct TextMisArgs {
 };
 
 // The launchers of k_tmis.hip are reached through pointers that the unit's own static initialiser sets (as tedit.hpp's):
-// api.cpp holds them — null: the calls answer SMARTGPU_ERR_HIP, they never fall back to anything.
+// match_calls.cpp holds them — null: the calls answer SMARTGPU_ERR_HIP, they never fall back to anything.
 extern hipError_t (*g_text_mis_scan)(const TextMisArgs& a, int num_cus, hipStream_t stream);
 extern hipError_t (*g_text_mis_find)(const TextMisArgs& a, unsigned long long* out, unsigned long long cap, int num_cus, hipStream_t stream);
 

@@ -1,4 +1,4 @@
-// tmis_host.hpp — byte texts: what the mismatch calls of api.cpp (smartgpu_search_mis64 and its kin) decide on the host
+// tmis_host.hpp — byte texts: what the mismatch calls of match_calls.cpp (smartgpu_search_mis64 and its kin) decide on the host
 // before a launch, and the recurrence the kernels of k_tmis.hip run per text byte and lane.  The pattern becomes 256 masks,
 // one per byte value — tedit_host.hpp's, complemented below m —; a lane's run becomes three numbers (edit_run_walk with a
 // warm-up of m - 1 bytes); a window's mismatches are counted in bit-sliced counters that move with the text.  Host and

@@ -4,6 +4,7 @@ include/smartgpu.h declares, and its host-side preprocessing equals the oracle's
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -31,6 +32,21 @@ def test_library_exports_every_declared_symbol():
     assert len(names) >= 28
     for n in names:
         assert hasattr(L, n), n
+
+
+def test_library_exports_no_smartgpu_symbol_the_header_does_not_declare():
+    """The dynamic symbols named smartgpu_* ARE the header's functions, in both libraries: what the host units share among
+    themselves (host_ctx.hpp, plan.hpp: hidden visibility) is no part of the ABI."""
+    for path in (engine.LIB_PATH, engine.AB_LIB_PATH):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("smartgpu_"))
+        assert exported == declared_symbols(), (path, set(exported) ^ set(declared_symbols()))
+        # and none of host_ctx.hpp's functions (C++ linkage, so not named smartgpu_*) is a dynamic symbol at all
+        shared = re.findall(r"^[A-Za-z_][\w \*]*?\b(\w+)\(.*\);$", open(os.path.join(ROOT, "smart_amd", "csrc", "host_ctx.hpp")).read(), flags=re.M)
+        assert {"set_error", "device_ctx_flushed", "batch_reserve", "find_reserve", "copy_positions", "now_ms", "probe_read_ms", "pcount_done"} <= set(shared)
+        demangled = subprocess.run(["nm", "-D", "--defined-only", "-C", path], capture_output=True, text=True, check=True).stdout
+        for name in shared:
+            assert not re.search(r"\b%s\(" % name, demangled), (path, name)
 
 
 def test_algorithm_registry():

@@ -1,6 +1,7 @@
-"""The contract every find call shares (find_run in api.cpp), stated once through the C ABI: pfind64, pfind_sets64, pfind_mis64
-and pfind_sets_mis64 on a two-plane and on a three-plane text, pfind_edit64, pfind_sets_edit64, pfind_editl64,
-pfind_sets_editl64, find_edit64 and find_edit_classes64.
+"""The contract every find call shares (find_run in match_calls.cpp), stated once through the C ABI: pfind64, pfind_sets64,
+pfind_mis64 and pfind_sets_mis64 on a two-plane and on a three-plane text, pfind_edit64, pfind_sets_edit64, pfind_editl64,
+pfind_sets_editl64, and on the same symbols as a byte text find_edit64, find_edit_classes64, find_editl64,
+find_editl_classes64, find_mis64 and find_mis_classes64.
 
   cap = count      SMARTGPU_OK, the full ascending list (and its distances)
   cap = count - 1  SMARTGPU_ERR_NOMEM, *count = count, the message names both numbers
@@ -12,7 +13,8 @@ which a find's entries come from three spans (planes.hpp: kFindSpan start positi
 that can reach the cursor out of order, the first of them beginning off a 128 boundary.  Every span holds a copy of the
 pattern, one span a second copy with a substitution.  m = 33 is the first length that stages a pattern, m = 70 is beyond the
 short edit kernels; k = 1.  The expected lists are definitions in numpy: positions_by_definition (test_packed_find_gpu.py),
-by_definition (test_packed_wide_gpu.py) and the dynamic-programming row edit_row (test_packed_edit.py)."""
+by_definition (test_packed_wide_gpu.py; for the byte text's mismatch calls the one of test_text_mis_gpu.py) and the
+dynamic-programming row edit_row (test_packed_edit.py)."""
 import ctypes
 
 import numpy as np
@@ -27,6 +29,7 @@ from test_packed_edit import byte_accepts, edit_row, set_accepts  # noqa: E402
 from test_packed_find_gpu import positions_by_definition  # noqa: E402
 from test_packed_wide_gpu import by_definition, sets_of  # noqa: E402
 from test_text_edit_gpu import class_accepts  # noqa: E402
+import test_text_mis_gpu as text_mis  # noqa: E402
 
 OK, ERR_NOMEM = 0, -5
 SPAN, OFF, K = 8192, 129, 1
@@ -47,6 +50,10 @@ CALLS = {
     "pfind_sets_editl64": ("psearch_sets_editl64", False, "sets", 70, (K, 0), True, "ends"),
     "find_edit64": ("search_edit64", False, "bytes", 33, (K,), True, "ends"),
     "find_edit_classes64": ("search_edit_classes64", False, "classes", 33, (K,), True, "ends"),
+    "find_editl64": ("search_editl64", False, "bytes", 70, (K, 0), True, "ends"),
+    "find_editl_classes64": ("search_editl_classes64", False, "classes", 70, (K, 0), True, "ends"),
+    "find_mis64": ("search_mis64", False, "bytes", 33, (K,), True, "starts"),
+    "find_mis_classes64": ("search_mis_classes64", False, "classes", 33, (K,), True, "starts"),
 }
 CASES = [(name, wide) for name, c in CALLS.items() for wide in ((False, True) if c[1] else (False,))]
 
@@ -106,6 +113,9 @@ def expected(name, wide, w):
     """(entries as uint64, distances as uint8) by definition over the range [OFF, N)."""
     _, _, kind, m, extra, dist, what = CALLS[name]
     T, vals, k, ln = w["T"], VALUES[wide], (extra[0] if extra else 0), N - OFF
+    if name.startswith("find_mis"):  # a byte text: the window's bytes against the pattern's bytes or classes
+        accepts = text_mis.byte_accepts(w["bytes"]) if kind == "bytes" else text_mis.class_accepts(w["classes"])
+        return text_mis.by_definition(m, accepts, T, k, OFF, ln)
     if what == "starts":
         if kind == "bytes" and not extra:
             pos = positions_by_definition(w["bytes"], T, OFF, ln)
@@ -123,7 +133,7 @@ def find_c(name, w, cap):
     pre-filled with guard values, NULL at cap = 0."""
     _, _, kind, m, extra, dist, _ = CALLS[name]
     pat = np.ascontiguousarray(w[kind], dtype=np.uint8)
-    handle = (w["text"] if name.startswith("find_edit") else w["packed"])._h
+    handle = (w["text"] if name.startswith("find_") else w["packed"])._h
     ent = np.full(cap + GUARDS, GUARD64, dtype=np.uint64)
     dst = np.full(cap + GUARDS, GUARD8, dtype=np.uint8) if dist else None
     outs = [ent.ctypes.data if cap else None] + ([dst.ctypes.data if cap else None] if dist else [])
@@ -136,7 +146,7 @@ def find_c(name, w, cap):
 def count_c(name, w):
     cname, _, kind, m, extra, _, _ = CALLS[name]
     pat = np.ascontiguousarray(w[kind], dtype=np.uint8)
-    handle = (w["text"] if name.startswith("find_edit") else w["packed"])._h
+    handle = (w["text"] if name.startswith("find_") else w["packed"])._h
     c = ctypes.c_uint64(0xFFFFFFFF)
     rc = getattr(smart_amd.lib(), "smartgpu_" + cname)(pat.ctypes.data, m, *extra, handle, OFF, N - OFF, ctypes.byref(c), None, None)
     assert rc == OK, (cname, rc)

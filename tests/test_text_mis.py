@@ -154,14 +154,28 @@ def test_refusals_that_need_no_device(kind):
 def test_count_null_is_refused_by_name():
     """count == NULL needs a text handle to be reached: the order of the checks is read from the source, the message from a
     call in tests/test_text_mis_gpu.py."""
-    api = open(os.path.join(sources.CSRC, "api.cpp")).read()
-    body = api[api.index("int check_text_args("):api.index("bool text_table_stage(")]
+    src = open(os.path.join(sources.CSRC, "match_calls.cpp")).read()
+    body = src[src.index("int check_text_args("):src.index("// ---- ONE host path")]
     order = [body.index(s) for s in ("%s is NULL", "outside [1,%d]", "k = %u %s, at most", "text handle is NULL", "outside the text", "count must not be NULL")]
     assert order == sorted(order)
-    # and every refusal of the two paths comes before the first thing that touches a device
-    for fn, until in (("int tmis_count(", "int tmis_find("), ("int tmis_find(", "// Edit distance, long patterns")):
-        path = api[api.index(fn):api.index(until)]
-        assert path.index('check_text_args(call, classes ? "classes" : "P", SMARTGPU_MIS_MAXM, "mismatches",') < path.index("_run(")
+    # and every refusal of the two paths comes before the first thing that touches a device: the family's prepare step begins
+    # with the checks, under the mismatch family's bounds and noun ...
+    family = src[src.index("struct TMis {"):src.index("template <typename F>\nstruct TextCall")]
+    assert "kMaxM = SMARTGPU_MIS_MAXM, kMaxK = SMARTGPU_PMIS_MAX;" in family and 'kNoun = "mismatches";' in family
+    prepare = src[src.index("struct TextCall : TQuestion {"):src.index("// ---- starts and alignments")]
+    prepare = prepare[prepare.index("Prepared prepare("):]
+    first = prepare[prepare.index("{") + 1:].lstrip()
+    assert first.startswith('const int rc = check_text_args(call, sets ? "classes" : "P", F::kMaxM, F::kMaxK, F::kNoun, F::kFlags,')
+    assert first.index("if (rc != SMARTGPU_OK) return refused(rc);") < first.index("missing_kernel<F>(find)") < first.index("text_head(")
+    # ... and run_count / run_find prepare before they run (the find refuses room without an array before that)
+    count = src[src.index("int run_count(const Q& q"):src.index("int run_find(const Q& q")]
+    assert count.index("f.prepare(false, count)") < count.index("if (p.rc != SMARTGPU_OK) return p.rc;") < count.index("_run(")
+    find = src[src.index("int run_find(const Q& q"):src.index("const char* missing_kernel(bool find)")]
+    assert find.index("check_room(q.call, what, entries, cap)") < find.index("f.prepare(true, count)") < find.index("if (p.rc != SMARTGPU_OK) return p.rc;") < find.index("_run(")
+    for call in ("search_mis64", "search_mis_classes64"):
+        assert 'return run_count<TextCall<TMis>>(TQuestion{"%s",' % call in src
+    for call in ("find_mis64", "find_mis_classes64"):
+        assert 'return run_find<TextCall<TMis>>(TQuestion{"%s",' % call in src and '"positions", positions, mismatches, cap, count);' in src
 
 
 def test_the_python_classes_calls_refuse_another_shape():

@@ -2,8 +2,9 @@
 """Host time of the packed-text calls, two builds against each other: python tools/packed_call_probe.py --parent <library> [--new <library>]
 
 Wall time per synchronous call (call_probe.py's manner: CALLS calls after a warm-up, patterns cut from the text) of psearch,
-pfind and the six set / mismatch calls on 64 Ki symbols of rand4, where the host dominates, at m = 16 and m = 64 — one on
-each side of the pattern's staging copy.  ROUNDS rounds per library, alternating, every round a process of its own under
+pfind, the six set / mismatch calls and the edit-distance calls (short and long kernels) on 64 Ki symbols of rand4, and of the
+edit-distance and mismatch calls on the same symbols as a byte text, where the host dominates, at m = 16 and m = 64 — one on
+each side of the pattern's staging copy; k = 1.  ROUNDS rounds per library, alternating, every round a process of its own under
 its own `timeout`; stops at the first that fails.  A cell passes when the new library's median lies inside the parent's
 min-max or below it.  Prints the table of the "Host path" section of profiles/packed/RESULTS.md; --out keeps the numbers."""
 import argparse
@@ -37,7 +38,12 @@ def one_round():
                  "psearch_sets": lambda j: smart_amd.psearch_sets(sets[j], pt), "pfind_sets": lambda j: smart_amd.pfind_sets(sets[j], pt, cap=CAP),
                  "psearch_mis": lambda j: smart_amd.psearch_mis(pats[j], pt, 1), "pfind_mis": lambda j: smart_amd.pfind_mis(pats[j], pt, 1, cap=CAP),
                  "psearch_sets_mis": lambda j: smart_amd.psearch_sets_mis(sets[j], pt, 1),
-                 "pfind_sets_mis": lambda j: smart_amd.pfind_sets_mis(sets[j], pt, 1, cap=CAP)}
+                 "pfind_sets_mis": lambda j: smart_amd.pfind_sets_mis(sets[j], pt, 1, cap=CAP),
+                 "psearch_edit": lambda j: smart_amd.psearch_edit(pats[j], pt, 1), "pfind_edit": lambda j: smart_amd.pfind_edit(pats[j], pt, 1, cap=CAP),
+                 "psearch_editl": lambda j: smart_amd.psearch_editl(pats[j], pt, 1), "pfind_editl": lambda j: smart_amd.pfind_editl(pats[j], pt, 1, cap=CAP),
+                 "search_edit": lambda j: smart_amd.search_edit(pats[j], text, 1), "find_edit": lambda j: smart_amd.find_edit(pats[j], text, 1, cap=CAP),
+                 "search_mis": lambda j: smart_amd.search_mis(pats[j], text, 1), "find_mis": lambda j: smart_amd.find_mis(pats[j], text, 1, cap=CAP),
+                 "search_editl": lambda j: smart_amd.search_editl(pats[j], text, 1), "find_editl": lambda j: smart_amd.find_editl(pats[j], text, 1, cap=CAP)}
         for name, call in calls.items():
             for j in range(WARM):
                 call(j)
