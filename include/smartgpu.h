@@ -746,8 +746,8 @@ int smartgpu_find_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k,
  * SMARTGPU_EDITL_MAXK (the messages name the limits), a flags bit other than SMARTGPU_EDITL_ALL_BLOCKS, a NULL text, a range
  * outside the text, count == NULL, ends == NULL with cap > 0.  The calls are synchronous: launches pending in the coalescing
  * queue are sent first, and they never enter it.
- * NOT offered: start positions and ALIGNMENTS of long patterns on a byte text (smartgpu_align_edit64 stays at m <= 64, k <= 7),
- * m > 256, k > 31, a batch call, MultiText shards, the `smart` harness.
+ * NOT offered: m > 256, k > 31, a batch call, MultiText shards, the `smart` harness.
+ * (Start positions and ALIGNMENTS of long patterns on a byte text: smartgpu_align_editl64 below.)
  * MEASURED on an MI355X, 1 GiB of rand128, English and rand4, m = 64, 65, 100, 150, 256, k = 0, 3, 7, 15, 31, the pattern cut
  * from the text (profiles/tedit/RESULTS.md, "Long patterns"; tools/teditl_probe.py; kernel times from a kernel trace taken in a
  * run of its own, medians of 5, run-to-run spread at most 2 % of the median; call times by the host clock, medians of 7, spread
@@ -801,7 +801,7 @@ int smartgpu_find_editl_classes64(const uint8_t *classes, uint32_t m, uint32_t k
  * reversed pattern's 256 masks, which the workgroup copies to LDS (one barrier); a lane parks the 11 or 19 aligned dwords
  * that hold its at most m + k <= 71 bytes in LDS and walks e, e-1, ...; with ops every column goes to LDS as well and the
  * traceback reads cell values back from the columns' bit vectors.
- * NOT offered: the longest start, all starts or all optimal alignments of a byte text; m > 64, k > 7; a kernel that finds
+ * NOT offered: the longest start, all starts or all optimal alignments of a byte text; m > 64, k > 7 (smartgpu_align_editl64 below); a kernel that finds
  * and aligns in one pass; a batch call; MultiText shards; the `smart` harness; three-plane texts.
  * MEASURED on an MI355X, 1 GiB of rand128, English and rand4 with planted copies of the pattern, about 1 Mi occurrences (9.5 Mi
  * for rand4 at m = 20, k = 7, which it holds by itself), every end of the find aligned, ms per call by the host clock, the
@@ -819,6 +819,54 @@ int smartgpu_align_edit64(const uint8_t *P, uint32_t m, uint32_t k, const smartg
                           const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 int smartgpu_align_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
                                   const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+/* START POSITIONS and ALIGNMENTS of LONG patterns on a byte text: smartgpu_align_edit64 for 1 <= m <= SMARTGPU_EDITL_MAXM =
+ * 256 bytes and 0 <= k <= SMARTGPU_EDITL_MAXK = 31 edits — which bytes an end position e reported by smartgpu_find_editl64 /
+ * smartgpu_find_editl_classes64 stands for (an interval of m - k to m + k bytes that the end and the distance do not
+ * identify), and which of them were substituted, added or skipped.  The contract is that of smartgpu_align_edit64, word for
+ * word: the LARGEST nearest start, D(e) computed and not taken on trust, the same four operations, the same fixed choice
+ * among optimal alignments (the diagonal first, then 'D', then 'I'), any e in [off, off+n) in any order with duplicates, the
+ * sentinels for D(e) > k decided exactly from min(m + k, e - off + 1) columns, start = e + 1 (the empty match, L = m
+ * deletions) when m <= k.  Lengths <= 64 with k <= 7 are legal too and give the starts, distances and operations of
+ * smartgpu_align_edit64, from an independent kernel.  Three things differ:
+ * BOUNDS: as above, and the messages name them.
+ * PACKING: ops has SMARTGPU_ALIGNL_OPS_WORDS = 10 words per entry, because an alignment has at most m + k = 287 operations:
+ * operation t in bits 2 * (t mod 32) of word t / 32, words 0 .. 8; word 9 holds the length L; every other bit is 0.  An end
+ * that is no occurrence gets ten zero words.  (The two-bit codes are smartgpu_palign_edit64's.)
+ * DISTANCES: distances[i] <= 31, or 255 for the sentinel (starts[i] = UINT64_MAX).
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written, in smartgpu_align_edit64's order: ends == NULL or starts ==
+ * NULL with count > 0, P / classes == NULL, m outside [1, SMARTGPU_EDITL_MAXM], k > SMARTGPU_EDITL_MAXK, a NULL text — with
+ * count == 0 too —, a range outside the text, and an ends[i] outside [off, off+n) (the message names i and the value).
+ * count == 0 with a valid text is SMARTGPU_OK with no launch.  Lists longer than the device's find buffer go through in
+ * pieces (a piece: the buffer's entries / 11 occurrences with ops).  The calls are synchronous: launches pending in the
+ * coalescing queue are sent first, and they never enter it.
+ * One WAVE per occurrence, one LANE per diagonal (text_editl_align; smart_amd/csrc/k_talignl.hip, alignl_band.hpp): a cost
+ * <= k <= 31 never leaves the 63 diagonals |i - j| <= k, which fit a 64-lane wave.  The wave parks the 73 aligned dwords that
+ * hold its at most 287 bytes in LDS, sweeps the anti-diagonals of the reversed matrix with two DPP wave shifts and one read
+ * of the reversed pattern's 256 masks (in LDS, one barrier) per step, and reduces row m to (D(e), J).  With ops every cell's
+ * two-bit decision goes to LDS, 17 dwords per lane, and a wave-uniform walk reads them back; no bit-vector column is stored.
+ * NOT offered: the longest start, all starts or all optimal alignments; packed texts (smartgpu_palign_edit64 stays at m <=
+ * 64, k <= 7); m > 256, k > 31; a kernel that finds and aligns in one pass; a batch call; MultiText shards; the `smart`
+ * harness.
+ * MEASURED on an MI355X, 1 GiB of rand128, English and rand4 with planted copies of the pattern, about 1 Mi occurrences, m = 64,
+ * 100, 150, 256, k = 7, 15, 31, every end of smartgpu_find_editl64 aligned, ms per call by the host clock, the list's copy to
+ * the device and the results' copy back included, medians of 7, run-to-run spread at most 5 % of the median
+ * (profiles/tedit/RESULTS.md, "Long patterns: starts and alignments"; tools/talignl_probe.py), on the three texts alike: without
+ * ops 9.5-11.8 ms at m = 64, 13.8-15.8 ms at m = 100, 19.8-21.8 ms at m = 150, 32.1-34.4 ms at m = 256 (9-33 ns per occurrence;
+ * the time follows 2 m + k, the number of anti-diagonals), which is 34-123 % OF THE FIND that produced the ends (23.7-33.0 ms);
+ * with ops 23.0-69.2 ms (22-65 ns per occurrence), 83-244 % of the find, 1.99-2.55 x the call without ops, outside the
+ * spread in every cell.  AGAINST smartgpu_align_edit64 (text_edit_align, unchanged) at m = 64, k = 7 on the same ends
+ * (identical starts, distances and operations): 5.0-5.3 x without ops, 4.8-5.2 x with ops: on the lengths both can do the
+ * short call is the one to use.  rand4 at m = 64, k = 31 holds 160 Mi occurrences by itself and was not measured.  The
+ * follow-up for the call without ops is a lane-per-occurrence bit-parallel walk (edit_block.hpp's recurrence in its
+ * distance form, no decisions kept); it is not built.
+ * NOT measured: the kernel's own time (no kernel trace: how a call divides between kernel and copies is not known), occupancy,
+ * DPP against ds_bpermute for the neighbours' values, the serial traceback's latency, the classes calls (the same kernels,
+ * another table), texts beyond 1 GiB (the at-size test checks answers beyond 2^32, not times). */
+#define SMARTGPU_ALIGNL_OPS_WORDS 10
+int smartgpu_align_editl64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                           const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+int smartgpu_align_editl_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
+                                   const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 /* MISMATCHES ON A BYTE TEXT: smartgpu_psearch_mis64 / smartgpu_pfind_mis64 asked of a smartgpu_text, whatever number of byte
  * values it holds ("which fixed-width record fields, barcodes, motifs lie within k substitutions of this one, no shifts?").
  * The contract is that of those calls with "byte" for "symbol": a START position s, off <= s <= off + n - m, is an occurrence

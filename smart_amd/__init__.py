@@ -10,6 +10,7 @@ from .engine import (ALGOS, MIN_M, MultiText, PackedText, Plan, SmartGpuError, T
                      pfind_sets_mis, psearch, psearch_batch, psearch_edit, psearch_mis, psearch_sets, psearch_sets_edit, psearch_sets_mis,
                      ptext_layout, ptext_layout8, search,
                      align_edit, align_edit_classes, find_edit_align, find_edit_classes_align,
+                     align_editl, align_editl_classes, find_editl_align, find_editl_classes_align,
                      byte_classes, find_edit, find_edit_classes, search_edit, search_edit_classes,
                      find_editl, find_editl_classes, search_editl, search_editl_classes,
                      find_mis, find_mis_classes, search_mis, search_mis_classes, search_batch, search_host, version)

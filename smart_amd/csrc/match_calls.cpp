@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "host_ctx.hpp"
+#include "align_host.hpp"
 #include "pedit.hpp"
 #include "peditl.hpp"
 #include "tedit.hpp"
@@ -137,9 +138,12 @@ int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint3
     return SMARTGPU_OK;
 }
 
+}  // namespace
+
 // BYTE texts: the checks of the edit, editl, mis and align calls that need no device; `what` names the pattern argument,
 // max_m and max_k are the family's, `noun` is what k counts, `flags_mask` the flag bits the family defines (0 for a call
-// that takes none, which passes flags = 0).
+// that takes none, which passes flags = 0).  Outside the anonymous namespace: alignl_calls.cpp makes the same checks
+// (align_host.hpp declares it, hidden as everything the host units share).
 int check_text_args(const char* call, const char* what, int max_m, int max_k, const char* noun, uint32_t flags_mask, const uint8_t* P, uint32_t m,
                     uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off, uint64_t n, const uint64_t* count)
 {
@@ -152,6 +156,8 @@ int check_text_args(const char* call, const char* what, int max_m, int max_k, co
     if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
     return SMARTGPU_OK;
 }
+
+namespace {
 
 // ---- ONE host path for every single-pattern count and find on a packed text and for the approximate matchers on a byte
 // text: count_run and find_run.  The skeleton fixes the order of the steps — the device's context with nothing queued, the
@@ -759,18 +765,8 @@ struct PEditCall : PQuestion {
 // ---- BYTE texts: edit distance (tedit.hpp, teditl.hpp) and mismatches (tmis.hpp), the contracts of the packed calls above
 // with a smartgpu_text in place of the planes ----
 
-// The pattern is 256 masks, too many for kernel arguments: they travel as the kernel's table (edit_peq_table: 1 or 2 dwords
-// per byte value; editl_peq_table: word-major, 2, 4 or 8) through the staging buffer into the arena, as psearch_impl's
-// patterns travel.  The staging buffer is free: every call that fills it ends with a synchronisation.
-template <uint32_t W>
-bool text_table_stage(DeviceCtx* d, const uint32_t (&table)[256][W], uint32_t words, const uint32_t** dev)
-{
-    if constexpr (W == sg::kTEditlWords) sg::editl_peq_table(table, words, reinterpret_cast<uint32_t*>(d->pinned));
-    else sg::edit_peq_table(table, words, reinterpret_cast<uint32_t*>(d->pinned));
-    *dev = reinterpret_cast<const uint32_t*>(d->arena);
-    return hipMemcpyAsync(d->arena, d->pinned, 256 * 4 * words, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-}
-
+// The pattern is 256 masks, too many for kernel arguments: they travel as the kernel's table through the staging buffer into
+// the arena (text_table_stage: align_host.hpp).
 // bytes or classes as tedit_host.hpp's masks "position j accepts this byte" (the edit calls and, with the reversed pattern, talign_run)
 bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
 {
@@ -879,72 +875,11 @@ struct TextCall : TQuestion {
 
 // ---- starts and alignments of edit-distance occurrences (palign.hpp): a list of END positions in, one lane each ----
 
-// copy_positions the other way: the caller's (pageable) end positions to the device through the pinned staging buffer
-bool upload_positions(DeviceCtx* d, unsigned long long* dst, const uint64_t* src, uint64_t count)
-{
-    for (uint64_t done = 0; done < count;) {
-        const uint64_t part = std::min<uint64_t>(count - done, d->pinned_bytes / 8);
-        std::memcpy(d->pinned, src + done, part * 8);
-        if (hipMemcpyAsync(dst + done, d->pinned, part * 8, hipMemcpyHostToDevice, d->stream) != hipSuccess ||
-            hipStreamSynchronize(d->stream) != hipSuccess)
-            return false;
-        done += part;
-    }
-    return true;
-}
-
-// The refusals of the lists, shared by the align calls.  An array that is missing: before every other check
-int check_align_lists(const char* call, const uint64_t* ends, uint64_t count, const uint64_t* starts)
-{
-    if (count && !ends) { set_error("%s: ends NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    if (count && !starts) { set_error("%s: starts NULL with count > 0", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// A listed end outside the range [off, off+n): after the other checks; the message names i and the value
-bool ends_in_range(const char* call, const uint64_t* ends, uint64_t count, uint64_t off, uint64_t n)
-{
-    for (uint64_t i = 0; i < count; ++i)
-        if (ends[i] < off || ends[i] - off >= n) {
-            set_error("%s: ends[%llu] = %llu outside the range [%llu,+%llu)", call, (unsigned long long)i, (unsigned long long)ends[i], (unsigned long long)off, (unsigned long long)n);
-            return false;
-        }
-    return true;
-}
-
-// Every align call.  The device works in the find's own buffer (find_reserve, at most kFindKeep entries, so never an
-// allocation per call beyond the first): a piece of `part` occurrences is [io: part entries | ops: 3 * part words], so a piece
-// is kFindKeep occurrences without ops and kFindKeep / 4 with them; longer lists go through piece after piece.
-// `launch(io, ops, part)` starts the family's kernel on d->stream over one piece.
-template <typename Launch>
-int align_pieces(const char* call, DeviceCtx* d, Launch launch, const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances,
-                 uint64_t* ops)
-{
-    const uint64_t piece = ops ? kFindKeep / 4 : kFindKeep;
-    for (uint64_t done = 0; done < count;) {
-        const uint64_t part = std::min<uint64_t>(count - done, piece);
-        bool own = false;
-        unsigned long long* buf = find_reserve(d, part * (ops ? 4 : 1), &own);
-        if (!buf) return SMARTGPU_ERR_NOMEM;
-        unsigned long long* const dev_ops = ops ? buf + part : nullptr;
-        const bool ok = upload_positions(d, buf, ends + done, part) &&
-                        launch(buf, dev_ops, part) == hipSuccess &&
-                        hipStreamSynchronize(d->stream) == hipSuccess &&
-                        copy_positions(d, starts + done, buf, part) &&
-                        (!ops || copy_positions(d, ops + 3 * done, dev_ops, 3 * part));
-        if (!ok) set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-        if (own) (void)hipFree(buf);
-        if (!ok) return SMARTGPU_ERR_HIP;
-        for (uint64_t i = done; i < done + part; ++i) {
-            const uint64_t v = starts[i];
-            const bool none = v == sg::kAlignNone;
-            starts[i] = none ? UINT64_MAX : v >> sg::kMisShift;
-            if (distances) distances[i] = none ? 255 : static_cast<uint8_t>(v & ((1u << sg::kMisShift) - 1u));
-        }
-        done += part;
-    }
-    return SMARTGPU_OK;
-}
+// The lists' refusals and way to the device, and the piece-wise loop every align call runs (check_align_lists, ends_in_range,
+// upload_positions, align_pieces: align_host.hpp).  The short calls' entries are (start << kMisShift) | distance with three
+// words of operations.
+constexpr uint32_t kAlignOpsWords = 3;
+static_assert(sg::kAlignNone == kAlignEntryNone, "align_pieces unpacks the kernels' entries");
 
 int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
                const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
@@ -973,7 +908,7 @@ int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint
                             a.count = part;
                             return sg::g_planes_edit_align(a, text->planes, d->stream);
                         },
-                        ends, count, starts, distances, ops);
+                        sg::kMisShift, kAlignOpsWords, ends, count, starts, distances, ops);
 }
 
 // The same on a BYTE text (talign.hpp).  The 256 masks of the REVERSED pattern travel to the arena as tedit_stage sends them;
@@ -1007,7 +942,7 @@ int talign_run(const char* call, const uint8_t* pat, bool classes, uint32_t m, u
                             a.count = part;
                             return sg::g_text_edit_align(a, d->stream);
                         },
-                        ends, count, starts, distances, ops);
+                        sg::kMisShift, kAlignOpsWords, ends, count, starts, distances, ops);
 }
 
 }  // namespace

@@ -202,6 +202,8 @@ def _load(path):
         "smartgpu_palign_sets_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_align_edit64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_align_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "smartgpu_align_editl64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "smartgpu_align_editl_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
         # packed texts of five to eight values (three bit planes)
         "smartgpu_ptext_layout8": (i32, [u64, i32, C.POINTER(i32), C.POINTER(u64)]),
@@ -768,15 +770,19 @@ def pfind_edit_align(P, ptext, k, off=0, n=None, cap=1 << 20):
 
 
 def edit_cigar(ops_row, sam=False):
-    """The run-length string of one alignment (a row of palign_edit's ops: three uint64), e.g. "12=1X3=1D4=": '=' accepted,
+    """The run-length string of one alignment (a row of palign_edit's ops: three uint64, the length in the top byte of the
+    third; or a row of align_editl's: ten uint64, the length in the tenth), e.g. "12=1X3=1D4=": '=' accepted,
     'X' substituted, 'I' a text symbol with no pattern partner, 'D' a pattern symbol with no text partner — the PATTERN's
     edits.  sam=True swaps the letters I and D: SAM's CIGAR with the text as the reference.  No operations: ""."""
     w = [int(x) for x in ops_row]
-    if len(w) != 3:
-        raise ValueError("an alignment is three uint64 words, not %d" % len(w))
+    if len(w) not in (3, 10):
+        raise ValueError("an alignment is three uint64 words (ten for a long pattern), not %d" % len(w))
+    length = w[2] >> 56 if len(w) == 3 else w[9]
+    if len(w) == 10 and length > 32 * 9:
+        raise ValueError("a long alignment has at most %d operations, not %d" % (32 * 9, length))
     letters = "=XDI" if sam else "=XID"
     out, run, last = [], 0, None
-    for t in range(w[2] >> 56):
+    for t in range(length):
         op = letters[w[t // 32] >> (2 * (t % 32)) & 3]
         if op != last and run:
             out.append("%d%s" % (run, last))
@@ -1061,14 +1067,14 @@ def find_mis_classes(classes, text, k, off=0, n=None, cap=1 << 20):
     return _tedit_find("find_mis_classes64", classes, m, text, k, off, n, cap)
 
 
-def _talign(name, pat, m, text, k, ends, off, n, ops):
+def _talign(name, pat, m, text, k, ends, off, n, ops, words_per=3):
     if n is None:
         n = len(text) - off
     ends = np.ascontiguousarray(ends, dtype=np.uint64)
     count = len(ends)
     starts = np.empty(count, dtype=np.uint64)
     dist = np.empty(count, dtype=np.uint8)
-    words = np.empty((count, 3), dtype=np.uint64) if ops else None
+    words = np.empty((count, words_per), dtype=np.uint64) if ops else None
     rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, m, k, text._h, off, n, ends.ctypes.data if count else None, count,
                                             starts.ctypes.data if count else None, dist.ctypes.data if count else None,
                                             words.ctypes.data if ops and count else None)
@@ -1111,6 +1117,35 @@ def find_edit_align(P, text, k, off=0, n=None, cap=1 << 20):
 def find_edit_classes_align(classes, text, k, off=0, n=None, cap=1 << 20):
     """find_edit_align for a pattern of byte classes (find_edit_classes, then align_edit_classes)."""
     return _find_then_align("find_edit_classes_align", find_edit_classes, align_edit_classes, classes, text, k, off, n, cap)
+
+
+ALIGNL_OPS_WORDS = 10  # SMARTGPU_ALIGNL_OPS_WORDS
+
+
+def align_editl(P, text, k, ends, off=0, n=None, ops=True):
+    """align_edit for LONG patterns (search_editl: up to 256 bytes, k up to 31; smartgpu_align_editl64): (starts, distances,
+    ops) of the END positions `ends` as find_editl returns them — the same contract, with ops as uint64 of shape (count, 10):
+    operation t in bits 2 * (t % 32) of word t // 32, words 0 .. 8, the length in word 9 (edit_cigar reads a row), or None
+    with ops=False.  An end with D(e) > k: start 2**64 - 1, distance 255, ops 0."""
+    P = _u8(P)
+    return _talign("align_editl64", P, len(P), text, k, ends, off, n, ops, ALIGNL_OPS_WORDS)
+
+
+def align_editl_classes(classes, text, k, ends, off=0, n=None, ops=True):
+    """align_editl for a pattern of byte CLASSES (search_editl_classes; smartgpu_align_editl_classes64)."""
+    classes, m = _classes(classes)
+    return _talign("align_editl_classes64", classes, m, text, k, ends, off, n, ops, ALIGNL_OPS_WORDS)
+
+
+def find_editl_align(P, text, k, off=0, n=None, cap=1 << 20):
+    """(starts, ends, distances, ops): find_editl, then align_editl on its ends — find_edit_align for LONG patterns, ops of
+    shape (count, 10)."""
+    return _find_then_align("find_editl_align", find_editl, align_editl, P, text, k, off, n, cap)
+
+
+def find_editl_classes_align(classes, text, k, off=0, n=None, cap=1 << 20):
+    """find_editl_align for a pattern of byte classes (find_editl_classes, then align_editl_classes)."""
+    return _find_then_align("find_editl_classes_align", find_editl_classes, align_editl_classes, classes, text, k, off, n, cap)
 
 
 def search_host(algo, P, T):

@@ -30,6 +30,7 @@ UNITS = {
     "k_tedit": ("k_tedit.hip", "text_tile.hpp", "tedit.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_teditl": ("k_teditl.hip", "teditl.hpp", "teditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_tmis": ("k_tmis.hip", "text_tile.hpp", "tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_talignl": ("k_talignl.hip", "talignl.hpp", "alignl_band.hpp", "talign_host.hpp", "tedit_host.hpp", "teditl_host.hpp", "edit_align.hpp", "edit_block.hpp", "edit_step.hpp", "planes.hpp"),
     "k_talign": ("k_talign.hip", "talign.hpp", "talign_host.hpp", "tedit.hpp", "tedit_host.hpp", "edit_align.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {
@@ -47,6 +48,7 @@ KERNEL_UNIT = {
     "text_edit_scan": "k_tedit", "text_edit_find": "k_tedit",
     "text_editl_scan": "k_teditl", "text_editl_find": "k_teditl",
     "text_edit_align": "k_talign",
+    "text_editl_align": "k_talignl",
     "text_mis_scan": "k_tmis", "text_mis_find": "k_tmis",
 }
 
