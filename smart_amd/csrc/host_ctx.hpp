@@ -1,6 +1,7 @@
 // host_ctx.hpp — what the host units of the C ABI share: api.cpp (texts, plans, the launch queue, the exact calls on byte
-// texts) defines all of it, match_calls.cpp (packed texts, the approximate matchers, the align calls) uses it.  Host only,
-// included by those two and by no kernel unit.
+// texts) defines all of it, match_calls.cpp (packed texts, the approximate matchers) and align_calls.cpp (the align calls) use
+// it, through call_host.hpp.  Host only, included by those three and by no kernel unit.  The two handles are plain structs, so
+// that a program without a device can fill them in (tests/host_calls_check.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 
 #include "../../include/smartgpu.h"
 #include "kernels.hpp"
+#include "planes.hpp"
 
 #pragma GCC visibility push(hidden)  // as when all of this lived in api.cpp: no symbol of the library's
 
@@ -94,4 +96,17 @@ struct smartgpu_text {
     // the 4 bytes at every 28th position (sample.hpp), written once behind the alphabet pass; null: the text has none
     // (smartgpu_text_sampling, a one-search upload, or no memory for it) and its passes read the text itself
     uint32_t* sample = nullptr;
+};
+
+/* ---- packed texts: at most four byte values as bit planes (planes.hpp, k_planes.hip), five to eight on three
+ * (planes3.hpp, k_planes3.hip) ------------------------------------------------------------------------------------- */
+struct smartgpu_ptext {
+    int device = 0;
+    uint64_t n = 0;            // symbols
+    int planes = 1;            // 1: at most two values, 2: three or four, 3: five to eight
+    int nvalues = 0;
+    uint8_t values[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // values[code], ascending
+    uint8_t* base = nullptr;   // allocation start; plane b at base + kFrontPad + b * plane_stride(n)
+    uint32_t* plane(int b) const { return reinterpret_cast<uint32_t*>(base + sg::kFrontPad + static_cast<uint64_t>(b) * sg::plane_stride(n)); }
+    uint64_t alloc_bytes() const { return sg::kFrontPad + static_cast<uint64_t>(planes) * sg::plane_stride(n); }
 };

@@ -1,6 +1,7 @@
-// match_calls.cpp — the C ABI's calls on PACKED texts (bit planes: planes.hpp, planes3.hpp), the approximate matchers on both
-// kinds of text (mismatches, edit distance) and the align calls.  Host code, compiled with hipcc as api.cpp is.  api.cpp keeps
-// texts, plans, the launch queue and the exact calls on byte texts, and defines what host_ctx.hpp declares for this unit.
+// match_calls.cpp — the C ABI's calls on PACKED texts (bit planes: planes.hpp, planes3.hpp) and the approximate matchers on both
+// kinds of text (mismatches, edit distance).  Host code, compiled with hipcc as api.cpp is.  api.cpp keeps texts, plans, the
+// launch queue and the exact calls on byte texts, and defines what host_ctx.hpp declares for this unit; the align calls are
+// align_calls.cpp, which shares call_host.hpp with this unit: the refusals that need no device, the masks, the staged tables.
 //
 // As in api.cpp there is no CPU search path here: a kernel that is not linked is an error, never a fall-back.
 #include "../../include/smartgpu.h"
@@ -12,15 +13,12 @@
 #include <type_traits>
 #include <vector>
 
-#include "host_ctx.hpp"
-#include "align_host.hpp"
+#include "call_host.hpp"
 #include "pedit.hpp"
 #include "peditl.hpp"
 #include "tedit.hpp"
 #include "teditl.hpp"
 #include "tmis.hpp"
-#include "palign.hpp"
-#include "talign.hpp"
 #include "planes.hpp"
 #include "planes_host.hpp"
 #include "planes3.hpp"
@@ -44,117 +42,10 @@ hipError_t (*g_text_editl_find)(const TextEditlArgs&, unsigned long long*, unsig
 // tmis.hpp: k_tmis.hip
 hipError_t (*g_text_mis_scan)(const TextMisArgs&, int, hipStream_t) = nullptr;
 hipError_t (*g_text_mis_find)(const TextMisArgs&, unsigned long long*, unsigned long long, int, hipStream_t) = nullptr;
-// palign.hpp: k_palign.hip; talign.hpp: k_talign.hip
-hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
-hipError_t (*g_text_edit_align)(const TextAlignArgs&, hipStream_t) = nullptr;
 // planes3.hpp: k_planes3.hip
 hipError_t (*g_planes3_pack)(const uint8_t*, uint64_t, uint32_t*, uint32_t*, uint32_t*, const uint8_t[7], hipStream_t) = nullptr;
 hipError_t (*g_planes3_scan)(const Plane3Args&, int, int, hipStream_t) = nullptr;
 hipError_t (*g_planes3_find)(const Plane3Args&, unsigned long long*, unsigned long long, int, int, hipStream_t) = nullptr;
-}
-
-/* ---- packed texts: at most four byte values as bit planes (planes.hpp, k_planes.hip), five to eight on three
- * (planes3.hpp, k_planes3.hip) ------------------------------------------------------------------------------------- */
-struct smartgpu_ptext {
-    int device = 0;
-    uint64_t n = 0;            // symbols
-    int planes = 1;            // 1: at most two values, 2: three or four, 3: five to eight
-    int nvalues = 0;
-    uint8_t values[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // values[code], ascending
-    uint8_t* base = nullptr;   // allocation start; plane b at base + kFrontPad + b * plane_stride(n)
-    uint32_t* plane(int b) const { return reinterpret_cast<uint32_t*>(base + sg::kFrontPad + static_cast<uint64_t>(b) * sg::plane_stride(n)); }
-    uint64_t alloc_bytes() const { return sg::kFrontPad + static_cast<uint64_t>(planes) * sg::plane_stride(n); }
-};
-
-namespace {
-
-// ---- refusals that more than one family makes ----
-
-// A kernel this program does not hold (its unit is not linked): an error, never a fall-back.
-int kernel_missing(const char* call, const char* kernel, const char* unit)
-{
-    set_error("%s: this program holds no %s kernel (%s is not linked)", call, kernel, unit);
-    return SMARTGPU_ERR_HIP;
-}
-
-// A find with room for entries and no array to put them in; `what` names the array.
-int check_room(const char* call, const char* what, const void* out, uint64_t cap)
-{
-    if (!cap || out) return SMARTGPU_OK;
-    set_error("%s: %s NULL with cap > 0", call, what);
-    return SMARTGPU_ERR_ARG;
-}
-
-// A set pattern that names a code the text does not hold.  `bad`: what the set encoders return, the first such position, or
-// a negative number for none.
-int refuse_code(const smartgpu_ptext* t, const uint8_t* sets, int bad)
-{
-    if (bad < 0) return SMARTGPU_OK;
-    set_error("set pattern: position %d: set 0x%02x names a code >= %d, the number of values the text holds", bad, sets[bad], t->nvalues);
-    return SMARTGPU_ERR_ARG;
-}
-
-int check_psearch_args(const uint8_t* P, uint32_t m, const smartgpu_ptext* text, uint64_t off, uint64_t n)
-{
-    if (!P || m < 1 || m > SMARTGPU_XSIZE) { set_error("pattern length %u outside [1,%d]", m, SMARTGPU_XSIZE); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
-    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// The checks of the set, mis and sets-mis calls that need no device; `what` names the pattern argument, k = 0 without mismatches.
-int check_pext_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off,
-                    uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (k > SMARTGPU_PMIS_MAX) { set_error("%s: k = %u mismatches, at most %d", call, k, SMARTGPU_PMIS_MAX); return SMARTGPU_ERR_ARG; }
-    const int rc = check_psearch_args(P, m, text, off, n);
-    if (rc != SMARTGPU_OK) return rc;
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-// The edit-distance and alignment calls do not read a third plane.
-int refuse_planes3(const char* call, const smartgpu_ptext* text)
-{
-    if (text->planes != 3) return SMARTGPU_OK;
-    set_error("%s: three-plane texts (five to eight values) are not offered here: edit distance and alignments read one or two planes", call);
-    return SMARTGPU_ERR_ARG;
-}
-
-// The checks of the edit, editl and align calls on a packed text that need no device; `what` names the pattern argument,
-// max_m and max_k are the family's, flags is 0 for a call that takes none.
-int check_pedit_args(const char* call, const char* what, const uint8_t* P, uint32_t m, uint32_t max_m, uint32_t k, uint32_t max_k, uint32_t flags,
-                     const smartgpu_ptext* text, uint64_t off, uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > max_m) { set_error("%s: pattern length %u outside [1,%u]", call, m, max_m); return SMARTGPU_ERR_ARG; }
-    if (k > max_k) { set_error("%s: k = %u edits, at most %u", call, k, max_k); return SMARTGPU_ERR_ARG; }
-    if (flags & ~SMARTGPU_PEDITL_ALL_BLOCKS) { set_error("%s: flags 0x%x: only SMARTGPU_PEDITL_ALL_BLOCKS (0x%x) is defined", call, flags, SMARTGPU_PEDITL_ALL_BLOCKS); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("packed text handle is NULL"); return SMARTGPU_ERR_ARG; }
-    if (refuse_planes3(call, text) != SMARTGPU_OK) return SMARTGPU_ERR_ARG;
-    if (off > text->n || n > text->n - off) { set_error("range [%llu,+%llu) outside the packed text (%llu symbols)", (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
-}
-
-}  // namespace
-
-// BYTE texts: the checks of the edit, editl, mis and align calls that need no device; `what` names the pattern argument,
-// max_m and max_k are the family's, `noun` is what k counts, `flags_mask` the flag bits the family defines (0 for a call
-// that takes none, which passes flags = 0).  Outside the anonymous namespace: alignl_calls.cpp makes the same checks
-// (align_host.hpp declares it, hidden as everything the host units share).
-int check_text_args(const char* call, const char* what, int max_m, int max_k, const char* noun, uint32_t flags_mask, const uint8_t* P, uint32_t m,
-                    uint32_t k, uint32_t flags, const smartgpu_text* text, uint64_t off, uint64_t n, const uint64_t* count)
-{
-    if (!P) { set_error("%s: %s is NULL", call, what); return SMARTGPU_ERR_ARG; }
-    if (m < 1 || m > (uint32_t)max_m) { set_error("%s: pattern length %u outside [1,%d]", call, m, max_m); return SMARTGPU_ERR_ARG; }
-    if (k > (uint32_t)max_k) { set_error("%s: k = %u %s, at most %d", call, k, noun, max_k); return SMARTGPU_ERR_ARG; }
-    if (flags & ~flags_mask) { set_error("%s: flags 0x%x: only SMARTGPU_EDITL_ALL_BLOCKS (0x%x) is defined", call, flags, flags_mask); return SMARTGPU_ERR_ARG; }
-    if (!text) { set_error("%s: text handle is NULL", call); return SMARTGPU_ERR_ARG; }
-    if (off > text->n || n > text->n - off) { set_error("%s: range [%llu,+%llu) outside the text (%llu bytes)", call, (unsigned long long)off, (unsigned long long)n, (unsigned long long)text->n); return SMARTGPU_ERR_ARG; }
-    if (!count) { set_error("%s: count must not be NULL", call); return SMARTGPU_ERR_ARG; }
-    return SMARTGPU_OK;
 }
 
 namespace {
@@ -284,25 +175,13 @@ void unpack_mis(uint64_t* positions, uint8_t* mismatches, uint64_t count, uint32
     }
 }
 
-// ---- ONE prepare step per family, used by its count and by its find.  A call is a Question; a family (PlaneCall, PEditCall,
-// TextCall below) is the question plus what `prepare` leaves for count_run / find_run.  prepare decides, in this order: the
+// ---- ONE prepare step per family, used by its count and by its find.  A call is a Question (call_host.hpp); a family (PlaneCall,
+// PEditCall, TextCall below) is the question plus what `prepare` leaves for count_run / find_run.  prepare decides, in this order: the
 // checks that need no device, the pattern's masks, what is answered without a launch, the refusal of a kernel that is not
 // linked, the arguments' head, the names and the bound.  Behind it a family has `stage`, `scan`, `find`, `order` (find_run's
 // lambdas) and `post` (the entries as the caller gets them).  run_count and run_find are all that tells a count from a
 // find: *count = 0 against pcount_done(0), find_every_start, the room check, the launcher.  Families live on the stack of
 // the call: no allocation, no indirect call beyond the launcher's pointer. ----
-template <typename Text>
-struct Question {
-    const char* call;    // the entry point's name in messages
-    const uint8_t* pat;  // m bytes, or — `sets` — m sets of codes (packed texts) or m classes of 32 bytes (byte texts)
-    bool sets;
-    bool mis;            // plane kinds only: the call takes k and reports distances
-    uint32_t m, k, flags;
-    const Text* text;
-    uint64_t off, n;
-};
-using PQuestion = Question<smartgpu_ptext>;
-using TQuestion = Question<smartgpu_text>;
 
 // What prepare answers.  rc != SMARTGPU_OK: refused, the message is set.  Otherwise a launch, or none: the first `every` start
 // positions of the range are the occurrences (0: there is none; n - m + 1: a pattern of full sets).
@@ -678,33 +557,6 @@ int pfind_batch_impl(const uint8_t* const* P, uint32_t m, uint32_t K, const smar
 // count and list END positions, n of them whatever m is, and m > n is legal; their entries are end << shift | distance.
 // They stage no planes: the masks are kernel arguments here, and a table in the arena on byte texts. ----
 
-// The fields that PlaneEditArgs, PlaneEditlArgs and PlaneAlignArgs share
-template <typename Args>
-void edit_head(Args& a, const smartgpu_ptext* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
-{
-    a.p0 = text->plane(0);
-    a.p1 = text->plane(text->planes - 1);
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
-}
-
-// The pattern's masks for a checked call, kernel arguments (a->peq of PlaneEditArgs, two dwords wide, or of PlaneEditlArgs,
-// eight): from bytes (sets == false) or from sets.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
-template <typename Args>
-int edit_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, Args* a)
-{
-    constexpr bool kLong = std::is_same<Args, sg::PlaneEditlArgs>::value;
-    if (!sets) {
-        if constexpr (kLong) sg::editl_peq_pattern(t->values, t->nvalues, pat, m, a->peq);
-        else sg::edit_peq_pattern(t->values, t->nvalues, pat, m, a->peq);
-        return SMARTGPU_OK;
-    }
-    if constexpr (kLong) return refuse_code(t, pat, sg::editl_peq_sets(t->nvalues, pat, m, a->peq));
-    else return refuse_code(t, pat, sg::edit_peq_sets(t->nvalues, pat, m, a->peq));
-}
-
 // What tells the two families apart.  Short (pedit.hpp): m <= 64, k <= 7, entries in spans.  Long (peditl.hpp): m <= 256,
 // k <= 31, a switch that travels with the call, and entries that the kernel writes in no order (order_editl sorts them).
 struct PEdit {
@@ -765,27 +617,6 @@ struct PEditCall : PQuestion {
 // ---- BYTE texts: edit distance (tedit.hpp, teditl.hpp) and mismatches (tmis.hpp), the contracts of the packed calls above
 // with a smartgpu_text in place of the planes ----
 
-// The pattern is 256 masks, too many for kernel arguments: they travel as the kernel's table through the staging buffer into
-// the arena (text_table_stage: align_host.hpp).
-// bytes or classes as tedit_host.hpp's masks "position j accepts this byte" (the edit calls and, with the reversed pattern, talign_run)
-bool tedit_stage(DeviceCtx* d, const uint8_t* pat, bool classes, uint32_t m, const uint32_t** dev)
-{
-    uint32_t peq[256][sg::kTEditWords];
-    if (classes) sg::edit_peq_classes(pat, m, peq); else sg::edit_peq_bytes(pat, m, peq);
-    return text_table_stage(d, peq, m <= 32 ? 1u : 2u, dev);
-}
-
-// what TextEditArgs, TextEditlArgs, TextMisArgs and TextAlignArgs share: the text and the range, the pattern's length and k
-template <class Args>
-void text_head(Args& a, const smartgpu_text* text, uint32_t m, uint32_t k, uint64_t off, uint64_t n)
-{
-    a.text = text->data();
-    a.e_begin = off;
-    a.e_end = off + n;
-    a.m = m;
-    a.k = k;
-}
-
 // What tells the three families apart: the bounds, what k counts, the flag bits, the table, and what is counted — END
 // positions (kStarts == false: n of them, no launch when n + k < m), or, for mismatches, START positions (n - m + 1, no
 // launch when m > n; the kernel's entries hold the windows' ENDS, the spans order_spans knows, and a window's start is
@@ -798,7 +629,7 @@ struct TEdit {
     static constexpr const char* kNoun = "edits";
     static constexpr const char* kKernel[2] = {"text_edit_scan", "text_edit_find"};
     static constexpr const char* kUnit = "k_tedit.hip";
-    static constexpr size_t kArena = sizeof(uint32_t) * 256 * sg::kTEditWords;
+    static constexpr size_t kArena = kTEditArena;
     static auto scan() { return sg::g_text_edit_scan; }
     static auto find() { return sg::g_text_edit_find; }
     static bool stage(DeviceCtx* d, const TQuestion& q, Args& a) { return tedit_stage(d, q.pat, q.sets, q.m, &a.peq); }
@@ -812,15 +643,10 @@ struct TEditl {
     static constexpr const char* kNoun = "edits";
     static constexpr const char* kKernel[2] = {"text_editl_scan", "text_editl_find"};
     static constexpr const char* kUnit = "k_teditl.hip";
-    static constexpr size_t kArena = sizeof(uint32_t) * 256 * sg::kTEditlWords;
+    static constexpr size_t kArena = kTEditlArena;
     static auto scan() { return sg::g_text_editl_scan; }
     static auto find() { return sg::g_text_editl_find; }
-    static bool stage(DeviceCtx* d, const TQuestion& q, Args& a)  // teditl_host.hpp's masks, eight dwords wide: 2, 4 or 8 KiB of table
-    {
-        uint32_t peq[256][sg::kTEditlWords];
-        if (q.sets) sg::editl_peq_classes(q.pat, q.m, peq); else sg::editl_peq_bytes(q.pat, q.m, peq);
-        return text_table_stage(d, peq, q.m <= 64 ? 2u : q.m <= 128 ? 4u : 8u, &a.peq);  // the kernels' WORDS (k_teditl.hip)
-    }
+    static bool stage(DeviceCtx* d, const TQuestion& q, Args& a) { return teditl_stage(d, q.pat, q.sets, q.m, &a.peq); }
 };
 
 struct TMis {
@@ -834,7 +660,7 @@ struct TMis {
     static constexpr size_t kArena = TEdit::kArena;
     static auto scan() { return sg::g_text_mis_scan; }
     static auto find() { return sg::g_text_mis_find; }
-    static bool stage(DeviceCtx* d, const TQuestion& q, Args& a)  // tmis_host.hpp's masks "position j does NOT accept this byte": tedit_stage's table and arena
+    static bool stage(DeviceCtx* d, const TQuestion& q, Args& a)  // tmis_host.hpp's masks "position j does NOT accept this byte": tedit_stage's table and arena (call_host.hpp)
     {
         uint32_t neq[256][sg::kTEditWords];
         if (q.sets) sg::mis_neq_classes(q.pat, q.m, neq); else sg::mis_neq_bytes(q.pat, q.m, neq);
@@ -872,78 +698,6 @@ struct TextCall : TQuestion {
             for (uint64_t i = 0; i < count; ++i) entries[i] -= m - 1;
     }
 };
-
-// ---- starts and alignments of edit-distance occurrences (palign.hpp): a list of END positions in, one lane each ----
-
-// The lists' refusals and way to the device, and the piece-wise loop every align call runs (check_align_lists, ends_in_range,
-// upload_positions, align_pieces: align_host.hpp).  The short calls' entries are (start << kMisShift) | distance with three
-// words of operations.
-constexpr uint32_t kAlignOpsWords = 3;
-static_assert(sg::kAlignNone == kAlignEntryNone, "align_pieces unpacks the kernels' entries");
-
-int palign_run(const char* call, const uint8_t* pat, bool sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    int rc = check_align_lists(call, ends, count, starts);
-    if (rc != SMARTGPU_OK) return rc;
-    rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDIT_MAXM, k, SMARTGPU_PMIS_MAX, 0, text, off, n, &count);
-    if (rc != SMARTGPU_OK) return rc;
-    sg::PlaneEditArgs masks;
-    if ((rc = edit_masks(text, pat, m, sets, &masks)) != SMARTGPU_OK) return rc;  // (the pattern as given: the message names ITS position)
-    if (!ends_in_range(call, ends, count, off, n)) return SMARTGPU_ERR_ARG;
-    if (count == 0) return SMARTGPU_OK;
-    if (!sg::g_planes_edit_align) return kernel_missing(call, "planes_edit_align", "k_palign.hip");
-    uint8_t rev[SMARTGPU_PEDIT_MAXM];
-    for (uint32_t j = 0; j < m; ++j) rev[j] = pat[m - 1 - j];
-    (void)edit_masks(text, rev, m, sets, &masks);  // the kernel walks backward: the masks of the REVERSED pattern
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    sg::PlaneAlignArgs a;
-    edit_head(a, text, m, k, off, n);
-    std::memcpy(a.peq, masks.peq, sizeof a.peq);
-    return align_pieces(call, d,
-                        [&](unsigned long long* io, unsigned long long* dev_ops, uint64_t part) {
-                            a.io = io;
-                            a.ops = dev_ops;
-                            a.count = part;
-                            return sg::g_planes_edit_align(a, text->planes, d->stream);
-                        },
-                        sg::kMisShift, kAlignOpsWords, ends, count, starts, distances, ops);
-}
-
-// The same on a BYTE text (talign.hpp).  The 256 masks of the REVERSED pattern travel to the arena as tedit_stage sends them;
-// the staging buffer they leave from is the one upload_positions fills next, so the stream is synchronised in between.
-int talign_run(const char* call, const uint8_t* pat, bool classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-               const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    int rc = check_align_lists(call, ends, count, starts);
-    if (rc != SMARTGPU_OK) return rc;
-    rc = check_text_args(call, classes ? "classes" : "P", SMARTGPU_EDIT_MAXM, SMARTGPU_PMIS_MAX, "edits", 0, pat, m, k, 0, text, off, n, &count);
-    if (rc != SMARTGPU_OK) return rc;
-    if (!ends_in_range(call, ends, count, off, n)) return SMARTGPU_ERR_ARG;
-    if (count == 0) return SMARTGPU_OK;
-    if (!sg::g_text_edit_align) return kernel_missing(call, "text_edit_align", "k_talign.hip");
-    uint8_t rev[32 * SMARTGPU_EDIT_MAXM];
-    if (classes) sg::talign_reverse_classes(pat, m, rev); else sg::talign_reverse_bytes(pat, m, rev);
-    DeviceCtx* d = device_ctx_flushed(text->device);
-    if (!d) return SMARTGPU_ERR_HIP;
-    if (!batch_reserve(d, TEdit::kArena, 1)) return SMARTGPU_ERR_NOMEM;
-    sg::TextAlignArgs a;
-    if (!tedit_stage(d, rev, classes, m, &a.peq) || hipStreamSynchronize(d->stream) != hipSuccess) {
-        set_error("%s: %s", call, hipGetErrorString(hipGetLastError()));
-        return SMARTGPU_ERR_HIP;
-    }
-    static_assert(sg::kTextAlignNone == sg::kAlignNone, "align_pieces unpacks both kernels' entries");
-    text_head(a, text, m, k, off, n);
-    return align_pieces(call, d,
-                        [&](unsigned long long* io, unsigned long long* dev_ops, uint64_t part) {
-                            a.io = io;
-                            a.ops = dev_ops;
-                            a.count = part;
-                            return sg::g_text_edit_align(a, d->stream);
-                        },
-                        sg::kMisShift, kAlignOpsWords, ends, count, starts, distances, ops);
-}
 
 }  // namespace
 
@@ -1307,32 +1061,6 @@ int smartgpu_pfind_sets_editl64(const uint8_t* sets, uint32_t m, uint32_t k, uin
                                 uint64_t* ends, uint8_t* distances, uint64_t cap, uint64_t* count)
 {
     return run_find<PEditCall<PEditl>>(PQuestion{"pfind_sets_editl64", sets, true, false, m, k, flags, text, off, n}, "ends", ends, distances, cap, count);
-}
-
-/* ---- edit distance: start positions and alignments of listed end positions (palign.hpp, k_palign.hip) ------------------ */
-int smartgpu_palign_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                           const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return palign_run("palign_edit64", P, false, m, k, text, off, n, ends, count, starts, distances, ops);
-}
-
-int smartgpu_palign_sets_edit64(const uint8_t* sets, uint32_t m, uint32_t k, const smartgpu_ptext* text, uint64_t off, uint64_t n,
-                                const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return palign_run("palign_sets_edit64", sets, true, m, k, text, off, n, ends, count, starts, distances, ops);
-}
-
-/* ---- the same on byte texts (talign.hpp, k_talign.hip) ------------------------------------------------------------------ */
-int smartgpu_align_edit64(const uint8_t* P, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                          const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return talign_run("align_edit64", P, false, m, k, text, off, n, ends, count, starts, distances, ops);
-}
-
-int smartgpu_align_edit_classes64(const uint8_t* classes, uint32_t m, uint32_t k, const smartgpu_text* text, uint64_t off, uint64_t n,
-                                  const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
-{
-    return talign_run("align_edit_classes64", classes, true, m, k, text, off, n, ends, count, starts, distances, ops);
 }
 
 // smartgpu_iupac_sets (most = 4) and smartgpu_iupac_sets8 (most = 8): one set of rules

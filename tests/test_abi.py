@@ -36,14 +36,21 @@ def test_library_exports_every_declared_symbol():
 
 def test_library_exports_no_smartgpu_symbol_the_header_does_not_declare():
     """The dynamic symbols named smartgpu_* ARE the header's functions, in both libraries: what the host units share among
-    themselves (host_ctx.hpp, plan.hpp: hidden visibility) is no part of the ABI."""
+    themselves (host_ctx.hpp, call_host.hpp, plan.hpp: hidden visibility) is no part of the ABI."""
     for path in (engine.LIB_PATH, engine.AB_LIB_PATH):
         out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
         exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("smartgpu_"))
         assert exported == declared_symbols(), (path, set(exported) ^ set(declared_symbols()))
-        # and none of host_ctx.hpp's functions (C++ linkage, so not named smartgpu_*) is a dynamic symbol at all
-        shared = re.findall(r"^[A-Za-z_][\w \*]*?\b(\w+)\(.*\);$", open(os.path.join(ROOT, "smart_amd", "csrc", "host_ctx.hpp")).read(), flags=re.M)
+        # and none of host_ctx.hpp's functions (C++ linkage, so not named smartgpu_*) is a dynamic symbol at all, nor one of
+        # call_host.hpp's, which are defined there
+        csrc = os.path.join(ROOT, "smart_amd", "csrc")
+        shared = re.findall(r"^[A-Za-z_][\w \*]*?\b(\w+)\(.*\);$", open(os.path.join(csrc, "host_ctx.hpp")).read(), flags=re.M)
         assert {"set_error", "device_ctx_flushed", "batch_reserve", "find_reserve", "copy_positions", "now_ms", "probe_read_ms", "pcount_done"} <= set(shared)
+        calls = re.findall(r"^inline (?:int|bool|void) (\w+)\(", open(os.path.join(csrc, "call_host.hpp")).read(), flags=re.M)
+        assert {"kernel_missing", "check_room", "refuse_code", "check_psearch_args", "check_pext_args", "refuse_planes3", "check_pedit_args",
+                "check_text_args", "check_align_lists", "ends_in_range", "text_table_stage", "tedit_stage", "teditl_stage", "edit_masks", "edit_head",
+                "text_head"} == set(calls), calls
+        shared += calls
         demangled = subprocess.run(["nm", "-D", "--defined-only", "-C", path], capture_output=True, text=True, check=True).stdout
         for name in shared:
             assert not re.search(r"\b%s\(" % name, demangled), (path, name)

@@ -1,5 +1,5 @@
-"""Every exported call of match_calls.cpp (the packed-text calls, the approximate matchers on both kinds of text, the
-align calls, the IUPAC helpers), refused before the first HIP call: its return code and the text of smartgpu_last_error(),
+"""Every exported call of match_calls.cpp and align_calls.cpp (the packed-text calls, the approximate matchers on both kinds of
+text, the align calls, the IUPAC helpers), refused before the first HIP call: its return code and the text of smartgpu_last_error(),
 compared with tests/golden/refusal_messages.json, which was recorded from the library as it stood before these calls left
 api.cpp (`python tests/test_refusal_messages.py --record` with SMARTGPU_LIB naming that build).  A refactoring of the host
 path may not change a code, a letter of a message or the order of two checks.
@@ -37,6 +37,8 @@ for stem, max_m, max_k, flags in (("%s_edit", 64, 7, False), ("%s_edit_classes",
     MATCH[stem % "find" + "64"] = ("find", max_m, max_k, flags, True)
 for name in ("palign_edit64", "palign_sets_edit64", "align_edit64", "align_edit_classes64"):
     MATCH[name] = ("align", 64, 7, False, True)
+for name in ("align_editl64", "align_editl_classes64"):
+    MATCH[name] = ("align", 256, 31, False, True)
 MATCH["psearch_batch64"] = ("batch_count", XSIZE, None, False, False)
 MATCH["pfind_batch64"] = ("batch_find", XSIZE, None, False, False)
 
@@ -173,9 +175,10 @@ def test_the_fixture_names_exactly_these_cases(golden):
 
 
 def test_every_moved_call_is_covered():
-    """every function the new unit defines with C linkage has at least one case"""
+    """every function the two units define with C linkage has at least one case"""
     import re
-    src = open(os.path.join(os.path.dirname(HERE), "smart_amd", "csrc", "match_calls.cpp")).read()
+    csrc = os.path.join(os.path.dirname(HERE), "smart_amd", "csrc")
+    src = open(os.path.join(csrc, "match_calls.cpp")).read() + open(os.path.join(csrc, "align_calls.cpp")).read()
     defined = set(re.findall(r"^(?:int|void|uint64_t|smartgpu_ptext\*) smartgpu_([a-z0-9_]+)\(", src, flags=re.M))
     assert len(defined) >= 50, sorted(defined)
     assert defined == {name for _, name, _ in CASES}, defined ^ {name for _, name, _ in CASES}

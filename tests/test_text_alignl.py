@@ -194,19 +194,19 @@ def test_sources_registry_has_the_unit_and_leaves_the_other_units_alone():
     assert sources.UNITS["k_peditl"] == ("k_peditl.hip", "peditl.hpp", "peditl_host.hpp", "edit_block.hpp", "planes.hpp")
     makefile = open(os.path.join(sources.CSRC, "Makefile")).read()
     assert re.search(r"^KERNELS\s*:=.*\bk_talignl\b", makefile, flags=re.M)
-    assert re.search(r"^UNITS\s*:=.*\balignl_calls\b", makefile, flags=re.M)
-    for h in ("talignl.hpp", "alignl_band.hpp", "align_host.hpp"):
+    assert re.search(r"^UNITS\s*:=.*\balign_calls\b", makefile, flags=re.M)
+    for h in ("talignl.hpp", "alignl_band.hpp", "call_host.hpp"):
         assert re.search(r"^HEADERS\s*:=.*\$\(HERE\)%s\b" % re.escape(h), makefile, flags=re.M), h
-    # the exported functions live in their own host unit, which shares its helpers with match_calls.cpp through a header
-    unit = open(os.path.join(sources.CSRC, "alignl_calls.cpp")).read()
+    # the exported functions live in the align calls' host unit, which shares its helpers with match_calls.cpp through a header
+    unit = open(os.path.join(sources.CSRC, "align_calls.cpp")).read()
     defined = set(re.findall(r"^int smartgpu_([a-z0-9_]+)\(", unit, flags=re.M))
-    assert defined == {"align_editl64", "align_editl_classes64"}
-    shared = open(os.path.join(sources.CSRC, "align_host.hpp")).read()
-    for helper in ("check_text_args", "check_align_lists", "ends_in_range", "upload_positions", "align_pieces", "text_table_stage"):
+    assert defined == {"palign_edit64", "palign_sets_edit64", "align_edit64", "align_edit_classes64", "align_editl64", "align_editl_classes64"}
+    shared = open(os.path.join(sources.CSRC, "call_host.hpp")).read()
+    for helper in ("check_text_args", "check_align_lists", "ends_in_range", "text_table_stage", "teditl_stage"):
         assert re.search(r"\b%s\(" % helper, shared), helper
-        if helper != "upload_positions":  # (align_pieces calls it)
-            assert re.search(r"\b%s\(" % helper, unit), helper
-    assert '#include "align_host.hpp"' in open(os.path.join(sources.CSRC, "match_calls.cpp")).read()
+    for helper in ("upload_positions", "align_pieces"):  # the align unit's own
+        assert not re.search(r"\b%s\(" % helper, shared), helper
+    assert not os.path.exists(os.path.join(sources.CSRC, "alignl_calls.cpp")) and not os.path.exists(os.path.join(sources.CSRC, "align_host.hpp"))
 
 
 def test_documents_name_every_symbol():

@@ -152,30 +152,35 @@ def test_refusals_that_need_no_device(kind):
 
 
 def test_count_null_is_refused_by_name():
-    """count == NULL needs a text handle to be reached: the order of the checks is read from the source, the message from a
-    call in tests/test_text_mis_gpu.py."""
-    src = open(os.path.join(sources.CSRC, "match_calls.cpp")).read()
-    body = src[src.index("int check_text_args("):src.index("// ---- ONE host path")]
-    order = [body.index(s) for s in ("%s is NULL", "outside [1,%d]", "k = %u %s, at most", "text handle is NULL", "outside the text", "count must not be NULL")]
-    assert order == sorted(order)
-    # and every refusal of the two paths comes before the first thing that touches a device: the family's prepare step begins
-    # with the checks, under the mismatch family's bounds and noun ...
-    family = src[src.index("struct TMis {"):src.index("template <typename F>\nstruct TextCall")]
-    assert "kMaxM = SMARTGPU_MIS_MAXM, kMaxK = SMARTGPU_PMIS_MAX;" in family and 'kNoun = "mismatches";' in family
-    prepare = src[src.index("struct TextCall : TQuestion {"):src.index("// ---- starts and alignments")]
-    prepare = prepare[prepare.index("Prepared prepare("):]
-    first = prepare[prepare.index("{") + 1:].lstrip()
-    assert first.startswith('const int rc = check_text_args(call, sets ? "classes" : "P", F::kMaxM, F::kMaxK, F::kNoun, F::kFlags,')
-    assert first.index("if (rc != SMARTGPU_OK) return refused(rc);") < first.index("missing_kernel<F>(find)") < first.index("text_head(")
-    # ... and run_count / run_find prepare before they run (the find refuses room without an array before that)
-    count = src[src.index("int run_count(const Q& q"):src.index("int run_find(const Q& q")]
-    assert count.index("f.prepare(false, count)") < count.index("if (p.rc != SMARTGPU_OK) return p.rc;") < count.index("_run(")
-    find = src[src.index("int run_find(const Q& q"):src.index("const char* missing_kernel(bool find)")]
-    assert find.index("check_room(q.call, what, entries, cap)") < find.index("f.prepare(true, count)") < find.index("if (p.rc != SMARTGPU_OK) return p.rc;") < find.index("_run(")
-    for call in ("search_mis64", "search_mis_classes64"):
-        assert 'return run_count<TextCall<TMis>>(TQuestion{"%s",' % call in src
-    for call in ("find_mis64", "find_mis_classes64"):
-        assert 'return run_find<TextCall<TMis>>(TQuestion{"%s",' % call in src and '"positions", positions, mismatches, cap, count);' in src
+    """count == NULL needs a text handle to be reached: tests/host_calls_check.cpp makes one on the CPU and runs the four calls
+    through every violation and every pair of two (tests/test_host_calls.py builds it; the driver itself asserts that a pair
+    answers as its earlier violation alone, and that a refused call asks for no device and writes nothing)."""
+    from test_host_calls import driver_cases
+    cases = driver_cases()
+    for name in ("search_mis64", "find_mis64", "search_mis_classes64", "find_mis_classes64"):
+        find, what = name.startswith("find"), "classes" if "classes" in name else "P"
+        said = lambda case: cases["order/%s/%s" % (name, case)]["error"]  # noqa: E731
+        # the six checks, under the mismatch family's bounds and noun, in their order ...
+        checks = [("pat_null", "%s is NULL" % what), ("m_over", "pattern length 65 outside [1,64]"), ("k_over", "k = 8 mismatches, at most 7"),
+                  ("text_null", "text handle is NULL"), ("n_beyond", "range [10,+91) outside the text (100 bytes)"), ("count_null", "count must not be NULL")]
+        assert said("m_zero") == name + ": pattern length 0 outside [1,64]"
+        for i, (first, says) in enumerate(checks):
+            assert said(first) == name + ": " + says
+            for second, _ in checks[i + 1:]:
+                assert said(first + "+" + second) == name + ": " + says, (name, first, second)
+        # ... in the finds behind `positions NULL with cap > 0`, which comes before everything ...
+        if find:
+            assert said("out_null") == name + ": positions NULL with cap > 0"
+            for second, _ in checks:
+                assert said("out_null+" + second) == said("out_null"), (name, second)
+        else:
+            assert "order/%s/out_null" % name not in cases
+        assert all(v["rc"] == -3 and v["device"] == 0 and v["written"] == "-" for c, v in cases.items() if c.startswith("order/%s/" % name))
+        # ... and all of them before the refusal of a kernel that is not linked, which comes before the device
+        missing, device = cases["missing/" + name], cases["device/" + name]
+        assert (missing["rc"], missing["device"]) == (-4, 0)
+        assert missing["error"] == "%s: this program holds no text_mis_%s kernel (k_tmis.hip is not linked)" % (name, "find" if find else "scan")
+        assert (device["rc"], device["device"], device["launchers"], device["written"]) == (-4, 1, 0, "-")
 
 
 def test_the_python_classes_calls_refuse_another_shape():
