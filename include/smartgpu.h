@@ -615,9 +615,9 @@ int smartgpu_pfind_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, cons
  * One lane per occurrence (planes_edit_align; smart_amd/csrc/k_palign.hip): the recurrence of the edit calls in its DISTANCE
  * form over the reversed pattern, walking e, e-1, ...; with ops every column goes to LDS and the traceback reads cell values
  * back from the columns' bit vectors.
- * NOT offered: the longest start, all starts, all optimal alignments; m > 64, k > 7 (smartgpu_pfind_editl64 finds the ends of
- * longer patterns; their alignments are not offered), affine costs, a kernel that finds and aligns in one pass.  (Byte texts:
- * smartgpu_align_edit64 below.)
+ * NOT offered: the longest start, all starts, all optimal alignments; m > 64, k > 7 (smartgpu_palign_editl64 below: up to 256
+ * symbols and 31 edits, on the ends of smartgpu_pfind_editl64), affine costs, a kernel that finds and aligns in one pass.  (Byte
+ * texts: smartgpu_align_edit64 below.)
  * MEASURED on an MI355X, 1 Gi symbols of rand4 with planted copies of the pattern, about 1 Mi occurrences (7 Mi for m = 20,
  * k = 7, which rand4 holds by itself), every end of the find aligned, ms per call by the host clock, the list's copy to the
  * device and the results' copy back included (profiles/packed/RESULTS.md, "Edit distance: starts and alignments";
@@ -650,8 +650,8 @@ int smartgpu_palign_sets_edit64(const uint8_t *sets, uint32_t m, uint32_t k, con
  * SMARTGPU_PEDITL_MAXK (the messages name the limits), a flags bit other than SMARTGPU_PEDITL_ALL_BLOCKS, a NULL text, a
  * range outside the text, count == NULL, ends == NULL with cap > 0, and — the sets calls — a set with a bit at or above the
  * text's number of values (the message names the position).
- * NOT offered: start positions and ALIGNMENTS of long patterns (smartgpu_palign_edit64 stays at m <= 64, k <= 7), m > 256,
- * k > 31, affine or weighted costs, a batch call, byte texts.
+ * NOT offered: m > 256, k > 31, affine or weighted costs, a batch call, byte texts.
+ * (Start positions and ALIGNMENTS of long patterns on a packed text: smartgpu_palign_editl64 below.)
  * MEASURED on an MI355X, 1 Gi symbols, m = 64, 65, 100, 150, 256, k = 0, 3, 7, 15, 31, the pattern cut from the text
  * (profiles/packed/RESULTS.md, "Edit distance: long patterns"; tools/editl_probe.py).  rand4, planes_editl_scan: 1.48-1.77 ms
  * for m <= 100 at k <= 7 (0.60-0.72 T symbols/s), 2.13-2.22 ms at m = 150, 2.51-2.59 ms at m = 256 (one active block: the
@@ -844,9 +844,8 @@ int smartgpu_align_edit_classes64(const uint8_t *classes, uint32_t m, uint32_t k
  * hold its at most 287 bytes in LDS, sweeps the anti-diagonals of the reversed matrix with two DPP wave shifts and one read
  * of the reversed pattern's 256 masks (in LDS, one barrier) per step, and reduces row m to (D(e), J).  With ops every cell's
  * two-bit decision goes to LDS, 17 dwords per lane, and a wave-uniform walk reads them back; no bit-vector column is stored.
- * NOT offered: the longest start, all starts or all optimal alignments; packed texts (smartgpu_palign_edit64 stays at m <=
- * 64, k <= 7); m > 256, k > 31; a kernel that finds and aligns in one pass; a batch call; MultiText shards; the `smart`
- * harness.
+ * NOT offered: the longest start, all starts or all optimal alignments; m > 256, k > 31; a kernel that finds and aligns in one
+ * pass; a batch call; MultiText shards; the `smart` harness.  (Packed texts: smartgpu_palign_editl64 below.)
  * MEASURED on an MI355X, 1 GiB of rand128, English and rand4 with planted copies of the pattern, about 1 Mi occurrences, m = 64,
  * 100, 150, 256, k = 7, 15, 31, every end of smartgpu_find_editl64 aligned, ms per call by the host clock, the list's copy to
  * the device and the results' copy back included, medians of 7, run-to-run spread at most 5 % of the median
@@ -867,6 +866,40 @@ int smartgpu_align_editl64(const uint8_t *P, uint32_t m, uint32_t k, const smart
                            const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 int smartgpu_align_editl_classes64(const uint8_t *classes, uint32_t m, uint32_t k, const smartgpu_text *text, uint64_t off, uint64_t n,
                                    const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+/* START POSITIONS and ALIGNMENTS of LONG patterns on a PACKED text: smartgpu_palign_edit64 for 1 <= m <= SMARTGPU_PEDITL_MAXM =
+ * 256 symbols and 0 <= k <= SMARTGPU_PEDITL_MAXK = 31 edits — which symbols an end position e reported by smartgpu_pfind_editl64
+ * / smartgpu_pfind_sets_editl64 stands for, and which of them were substituted, added or skipped, with no byte copy of the text
+ * on the device.  The contract is that of smartgpu_palign_edit64 with the bounds, the packing and the distances of
+ * smartgpu_align_editl64 above: the LARGEST nearest start, D(e) computed and not taken on trust, the same four operations, the
+ * same fixed choice among optimal alignments (the diagonal first, then 'D', then 'I'), any e in [off, off+n) in any order with
+ * duplicates, the sentinels for D(e) > k (starts[i] = UINT64_MAX, distances[i] = 255, ten zero words) decided exactly from
+ * min(m + k, e - off + 1) columns, ops of SMARTGPU_ALIGNL_OPS_WORDS = 10 words per entry (operation t in bits 2 * (t mod 32) of
+ * word t / 32, words 0 .. 8; word 9 holds L).  On the same bytes uploaded as a smartgpu_text, smartgpu_align_editl64 gives the
+ * same starts, distances and ten words, bit for bit; for m <= 64 and k <= 7 smartgpu_palign_edit64 gives the same starts,
+ * distances and operations.  A foreign byte or an empty set accepts nothing, a full set everything, as in the finds.
+ * SMARTGPU_ERR_ARG, decided before any HIP call, nothing written, in smartgpu_palign_edit64's order: ends == NULL or starts ==
+ * NULL with count > 0, P / sets == NULL, m outside [1, SMARTGPU_PEDITL_MAXM], k > SMARTGPU_PEDITL_MAXK, a NULL text — with
+ * count == 0 too —, a three-plane text, a range outside the text, a set with a bit at or above the text's number of values (the
+ * message names the position), and an ends[i] outside [off, off+n) (the message names i and the value).  count == 0 with a
+ * valid text is SMARTGPU_OK with no launch.  Lists longer than the device's find buffer go through in pieces (a piece: the
+ * buffer's entries / 11 occurrences with ops).  The calls are synchronous: launches pending in the coalescing queue are sent
+ * first, and they never enter it.
+ * One WAVE per occurrence, one LANE per diagonal (planes_editl_align; smart_amd/csrc/k_palignl.hip, alignl_band.hpp): the
+ * decomposition of text_editl_align, fed from bit planes.  The wave parks the 10 aligned dwords of each plane that hold its at
+ * most 287 symbols in LDS (the byte kernel parks 73), takes a column's code from them by shift, and reads `miss` from the
+ * reversed pattern's four masks of eight dwords, which travel as kernel arguments and lie in LDS (one barrier); the sweep of
+ * the anti-diagonals with two DPP wave shifts, the decisions (17 dwords per lane), the reduction of row m and the wave-uniform
+ * walk are the byte kernel's.
+ * NOT offered: the longest start, all starts or all optimal alignments; three-plane texts; m > 256, k > 31; a kernel that finds
+ * and aligns in one pass; a batch call.
+ * NOT measured: everything — the call's time against smartgpu_align_editl64 on the same bytes unpacked, against
+ * smartgpu_palign_edit64 at m = 64, k = 7, and as a share of the smartgpu_pfind_editl64 that produced the ends
+ * (tools/palignl_probe.py takes the three; profiles/packed/RESULTS.md, "Long patterns: starts and alignments"), the kernel's own
+ * time, occupancy. */
+int smartgpu_palign_editl64(const uint8_t *P, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                            const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
+int smartgpu_palign_sets_editl64(const uint8_t *sets, uint32_t m, uint32_t k, const smartgpu_ptext *text, uint64_t off, uint64_t n,
+                                 const uint64_t *ends, uint64_t count, uint64_t *starts, uint8_t *distances, uint64_t *ops);
 /* MISMATCHES ON A BYTE TEXT: smartgpu_psearch_mis64 / smartgpu_pfind_mis64 asked of a smartgpu_text, whatever number of byte
  * values it holds ("which fixed-width record fields, barcodes, motifs lie within k substitutions of this one, no shifts?").
  * The contract is that of those calls with "byte" for "symbol": a START position s, off <= s <= off + n - m, is an occurrence

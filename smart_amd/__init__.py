@@ -7,6 +7,7 @@ mirror of SMART's harness vocabulary (texts, patterns, algorithms).
 from .engine import (ALGOS, MIN_M, MultiText, PackedText, Plan, SmartGpuError, Text, algo_id, build_table, device_count, kernel_for,  # noqa: F401
                      edit_cigar, find, find_batch, find_batch_max, find_width, iupac_revcomp, iupac_sets, lib, palign_edit, palign_sets_edit, pfind, pfind_batch, pfind_edit, pfind_edit_align, pfind_mis, pfind_sets, pfind_sets_edit,
                      pfind_editl, pfind_sets_editl, psearch_editl, psearch_sets_editl,
+                     palign_editl, palign_sets_editl, pfind_editl_align, pfind_sets_editl_align,
                      pfind_sets_mis, psearch, psearch_batch, psearch_edit, psearch_mis, psearch_sets, psearch_sets_edit, psearch_sets_mis,
                      ptext_layout, ptext_layout8, search,
                      align_edit, align_edit_classes, find_edit_align, find_edit_classes_align,

@@ -1,8 +1,9 @@
 // align_calls.cpp — the C ABI's align calls: starts and alignments of edit-distance occurrences, given as a list of END positions,
-// one lane (short patterns) or one wave (long patterns) each.  Three families, one per kernel — packed texts (palign.hpp,
-// k_palign.hip), byte texts (talign.hpp, k_talign.hip), byte texts with long patterns (talignl.hpp, k_talignl.hip) — and ONE
-// host path for the six exported calls: align_prepare and align_run.  Host code, compiled with hipcc as api.cpp and
-// match_calls.cpp are; what the three units share is host_ctx.hpp (defined in api.cpp) and, with match_calls.cpp, call_host.hpp.
+// one lane (short patterns) or one wave (long patterns) each.  Four families, one per kernel — packed texts (palign.hpp,
+// k_palign.hip), packed texts with long patterns (palignl.hpp, k_palignl.hip), byte texts (talign.hpp, k_talign.hip), byte
+// texts with long patterns (talignl.hpp, k_talignl.hip) — and ONE host path for the six calls exported here and for the two of
+// palignl_calls.cpp, which reach it through palignl_run: align_prepare and align_run.  Host code, compiled with hipcc as api.cpp
+// and match_calls.cpp are; what the units share is host_ctx.hpp (defined in api.cpp) and, with match_calls.cpp, call_host.hpp.
 //
 // As everywhere in the C ABI there is no CPU path here: a kernel that is not linked is an error, never a fall-back.
 #include "../../include/smartgpu.h"
@@ -14,13 +15,15 @@
 
 #include "call_host.hpp"
 #include "palign.hpp"
+#include "palignl.hpp"
 #include "talign.hpp"
 #include "talignl.hpp"
 
-// The launchers of the three kernel units: this unit holds the pointers (null: the calls answer SMARTGPU_ERR_HIP), each set by
+// The launchers of the four kernel units: this unit holds the pointers (null: the calls answer SMARTGPU_ERR_HIP), each set by
 // its unit's own static initialiser where that unit is linked.
 namespace sg {
 hipError_t (*g_planes_edit_align)(const PlaneAlignArgs&, int, hipStream_t) = nullptr;
+hipError_t (*g_planes_editl_align)(const PlaneAlignlArgs&, int, int, hipStream_t) = nullptr;
 hipError_t (*g_text_edit_align)(const TextAlignArgs&, hipStream_t) = nullptr;
 hipError_t (*g_text_editl_align)(const TextAlignlArgs&, int, hipStream_t) = nullptr;
 }
@@ -46,7 +49,8 @@ bool upload_positions(DeviceCtx* d, unsigned long long* dst, const uint64_t* src
 // occurrences without ops and kFindKeep / (1 + words) with them (3 words: the short calls; 10: the long ones); longer lists go
 // through piece after piece.  `launch(io, ops, part)` starts the family's kernel on d->stream over one piece.  An entry comes
 // back as (start << shift) | distance, or kAlignNone.
-static_assert(sg::kTextAlignNone == sg::kAlignNone && sg::kTextAlignlNone == sg::kAlignNone, "align_pieces unpacks the entries of all three kernels");
+static_assert(sg::kTextAlignNone == sg::kAlignNone && sg::kTextAlignlNone == sg::kAlignNone && sg::kPlaneAlignlNone == sg::kAlignNone,
+              "align_pieces unpacks the entries of all four kernels");
 template <typename Launch>
 int align_pieces(const char* call, DeviceCtx* d, Launch launch, uint32_t shift, uint32_t words, const uint64_t* ends, uint64_t count,
                  uint64_t* starts, uint8_t* distances, uint64_t* ops)
@@ -103,6 +107,30 @@ struct PAlign : PQuestion {
         edit_head(a, text, m, k, off, n);
     }
     hipError_t launch(DeviceCtx* d) { return sg::g_planes_edit_align(a, text->planes, d->stream); }
+};
+
+// packed texts, long patterns: the masks are eight dwords wide and still kernel arguments
+struct PAlignl : PQuestion {
+    static constexpr const char* kKernel = "planes_editl_align";
+    static constexpr const char* kUnit = "k_palignl.hip";
+    static constexpr uint32_t kShift = sg::kPAlignlShift, kOpsWords = SMARTGPU_ALIGNL_OPS_WORDS;
+    static constexpr size_t kArena = 0;
+    sg::PlaneAlignlArgs a;
+
+    static bool linked() { return sg::g_planes_editl_align != nullptr; }
+    int check(const uint64_t* count)  // and the masks of the pattern AS GIVEN: a bad set is refused by ITS position
+    {
+        const int rc = check_pedit_args(call, sets ? "sets" : "P", pat, m, SMARTGPU_PEDITL_MAXM, k, SMARTGPU_PEDITL_MAXK, 0, text, off, n, count);
+        return rc != SMARTGPU_OK ? rc : edit_masks(text, pat, m, sets, &a);
+    }
+    void reverse()
+    {
+        uint8_t rev[SMARTGPU_PEDITL_MAXM];
+        for (uint32_t j = 0; j < m; ++j) rev[j] = pat[m - 1 - j];
+        (void)edit_masks(text, rev, m, sets, &a);
+        edit_head(a, text, m, k, off, n);
+    }
+    hipError_t launch(DeviceCtx* d) { return sg::g_planes_editl_align(a, text->planes, d->num_cus, d->stream); }
 };
 
 // the two families on byte texts: what they share.  The table's masks leave from the staging buffer that upload_positions
@@ -188,6 +216,12 @@ int align_run(const typename F::Q& q, const uint64_t* ends, uint64_t count, uint
 }
 
 }  // namespace
+
+// packed texts, long patterns (palignl.hpp, k_palignl.hip): the exported calls are palignl_calls.cpp's, this is their host path
+int palignl_run(const PQuestion& q, const uint64_t* ends, uint64_t count, uint64_t* starts, uint8_t* distances, uint64_t* ops)
+{
+    return align_run<PAlignl>(q, ends, count, starts, distances, ops);
+}
 
 extern "C" {
 

@@ -17,7 +17,7 @@
 
 #pragma GCC visibility push(hidden)
 
-// A call as its family receives it (the families: PlaneCall, PEditCall, TextCall in match_calls.cpp; PAlign, TAlign, TAlignl)
+// A call as its family receives it (the families: PlaneCall, PEditCall, TextCall in match_calls.cpp; PAlign, PAlignl, TAlign, TAlignl)
 template <typename Text>
 struct Question {
     using Q = Question;
@@ -151,12 +151,12 @@ inline void edit_head(Args& a, const smartgpu_ptext* text, uint32_t m, uint32_t 
     a.k = k;
 }
 
-// The pattern's masks for a checked call (a->peq of PlaneEditArgs and PlaneAlignArgs, two dwords wide, or of PlaneEditlArgs,
-// eight): from bytes (sets == false) or from sets.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
+// The pattern's masks for a checked call (a->peq of PlaneEditArgs and PlaneAlignArgs, two dwords wide, or of PlaneEditlArgs
+// and PlaneAlignlArgs, eight): from bytes (sets == false) or from sets.  SMARTGPU_ERR_ARG: a set names a code the text does not hold.
 template <typename Args>
 inline int edit_masks(const smartgpu_ptext* t, const uint8_t* pat, uint32_t m, bool sets, Args* a)
 {
-    constexpr bool kLong = std::is_same<Args, sg::PlaneEditlArgs>::value;
+    constexpr bool kLong = std::is_same<decltype(Args::peq), uint32_t[4][sg::kEditlWords]>::value;
     if (!sets) {
         if constexpr (kLong) sg::editl_peq_pattern(t->values, t->nvalues, pat, m, a->peq);
         else sg::edit_peq_pattern(t->values, t->nvalues, pat, m, a->peq);

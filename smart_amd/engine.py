@@ -204,6 +204,8 @@ def _load(path):
         "smartgpu_align_edit_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_align_editl64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_align_editl_classes64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "smartgpu_palign_editl64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "smartgpu_palign_sets_editl64": (i32, [vp, u32, u32, vp, u64, u64, vp, u64, vp, vp, vp]),
         "smartgpu_iupac_revcomp": (i32, [vp, u32, vp]),
         # packed texts of five to eight values (three bit planes)
         "smartgpu_ptext_layout8": (i32, [u64, i32, C.POINTER(i32), C.POINTER(u64)]),
@@ -725,7 +727,7 @@ def pfind_sets_editl(sets, ptext, k, off=0, n=None, cap=1 << 20, all_blocks=Fals
     return _pfind("pfind_sets_editl64", sets, ptext, off, n, cap, k, int(bool(all_blocks)))
 
 
-def _palign(name, pat, ptext, k, ends, off, n, ops):
+def _palign(name, pat, ptext, k, ends, off, n, ops, words_per=3):
     pat = _u8(pat)
     if n is None:
         n = len(ptext) - off
@@ -733,7 +735,7 @@ def _palign(name, pat, ptext, k, ends, off, n, ops):
     count = len(ends)
     starts = np.empty(count, dtype=np.uint64)
     dist = np.empty(count, dtype=np.uint8)
-    words = np.empty((count, 3), dtype=np.uint64) if ops else None
+    words = np.empty((count, words_per), dtype=np.uint64) if ops else None
     rc = getattr(lib(), "smartgpu_" + name)(pat.ctypes.data, len(pat), k, ptext._h, off, n, ends.ctypes.data if count else None, count,
                                             starts.ctypes.data if count else None, dist.ctypes.data if count else None,
                                             words.ctypes.data if ops and count else None)
@@ -756,17 +758,45 @@ def palign_sets_edit(sets, ptext, k, ends, off=0, n=None, ops=True):
     return _palign("palign_sets_edit64", sets, ptext, k, ends, off, n, ops)
 
 
+def _pfind_then_align(name, find, align, pat, ptext, k, off, n, cap):
+    ends, dist, count = find(pat, ptext, k, off=off, n=n, cap=cap)
+    if ends is None:
+        return None, None, None, None, count
+    starts, adist, ops = align(pat, ptext, k, ends, off=off, n=n)
+    if not np.array_equal(adist, dist):
+        raise SmartGpuError("%s: the align call's distances differ from the find's" % name)
+    return starts, ends, dist, ops, count
+
+
 def pfind_edit_align(P, ptext, k, off=0, n=None, cap=1 << 20):
     """(starts, ends, distances, ops, count): pfind_edit, then palign_edit on its ends — every occurrence of P within edit
     distance k as the interval [start, end] of the text, its distance and its alignment.  More than `cap` occurrences:
     (None, None, None, None, count)."""
-    ends, dist, count = pfind_edit(P, ptext, k, off=off, n=n, cap=cap)
-    if ends is None:
-        return None, None, None, None, count
-    starts, adist, ops = palign_edit(P, ptext, k, ends, off=off, n=n)
-    if not np.array_equal(adist, dist):
-        raise SmartGpuError("pfind_edit_align: the align call's distances differ from the find's")
-    return starts, ends, dist, ops, count
+    return _pfind_then_align("pfind_edit_align", pfind_edit, palign_edit, P, ptext, k, off, n, cap)
+
+
+def palign_editl(P, ptext, k, ends, off=0, n=None, ops=True):
+    """palign_edit for LONG patterns (psearch_editl: up to 256 symbols, k up to 31; smartgpu_palign_editl64): (starts,
+    distances, ops) of the END positions `ends` as pfind_editl returns them — the same contract, with ops as uint64 of shape
+    (count, 10) as align_editl returns them: operation t in bits 2 * (t % 32) of word t // 32, words 0 .. 8, the length in
+    word 9 (edit_cigar reads a row), or None with ops=False.  An end with D(e) > k: start 2**64 - 1, distance 255, ops 0."""
+    return _palign("palign_editl64", P, ptext, k, ends, off, n, ops, ALIGNL_OPS_WORDS)
+
+
+def palign_sets_editl(sets, ptext, k, ends, off=0, n=None, ops=True):
+    """palign_editl for a SET pattern (psearch_sets_editl; smartgpu_palign_sets_editl64)."""
+    return _palign("palign_sets_editl64", sets, ptext, k, ends, off, n, ops, ALIGNL_OPS_WORDS)
+
+
+def pfind_editl_align(P, ptext, k, off=0, n=None, cap=1 << 20):
+    """(starts, ends, distances, ops, count): pfind_editl, then palign_editl on its ends — pfind_edit_align for LONG patterns,
+    ops of shape (count, 10).  More than `cap` occurrences: (None, None, None, None, count)."""
+    return _pfind_then_align("pfind_editl_align", pfind_editl, palign_editl, P, ptext, k, off, n, cap)
+
+
+def pfind_sets_editl_align(sets, ptext, k, off=0, n=None, cap=1 << 20):
+    """pfind_editl_align for a SET pattern (pfind_sets_editl, then palign_sets_editl)."""
+    return _pfind_then_align("pfind_sets_editl_align", pfind_sets_editl, palign_sets_editl, sets, ptext, k, off, n, cap)
 
 
 def edit_cigar(ops_row, sam=False):

@@ -31,6 +31,7 @@ UNITS = {
     "k_teditl": ("k_teditl.hip", "teditl.hpp", "teditl_host.hpp", "edit_block.hpp", "planes.hpp"),
     "k_tmis": ("k_tmis.hip", "text_tile.hpp", "tmis.hpp", "tmis_host.hpp", "tedit_host.hpp", "edit_step.hpp", "planes.hpp"),
     "k_talignl": ("k_talignl.hip", "talignl.hpp", "alignl_band.hpp", "talign_host.hpp", "tedit_host.hpp", "teditl_host.hpp", "edit_align.hpp", "edit_block.hpp", "edit_step.hpp", "planes.hpp"),
+    "k_palignl": ("k_palignl.hip", "palignl.hpp", "alignl_band.hpp", "talign_host.hpp", "tedit_host.hpp", "peditl_host.hpp", "edit_align.hpp", "edit_block.hpp", "edit_step.hpp", "planes.hpp"),
     "k_talign": ("k_talign.hip", "talign.hpp", "talign_host.hpp", "tedit.hpp", "tedit_host.hpp", "edit_align.hpp", "edit_step.hpp", "planes.hpp"),
 }
 KERNEL_UNIT = {
@@ -49,6 +50,7 @@ KERNEL_UNIT = {
     "text_editl_scan": "k_teditl", "text_editl_find": "k_teditl",
     "text_edit_align": "k_talign",
     "text_editl_align": "k_talignl",
+    "planes_editl_align": "k_palignl",
     "text_mis_scan": "k_tmis", "text_mis_find": "k_tmis",
 }
 

@@ -8,10 +8,10 @@ NAME=$1; shift
 D=$(cd "$(dirname "$0")/../smart_amd/csrc" && pwd)
 T=$(mktemp -d)
 FLAGS="-O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Wno-unused-value"
-for u in k_hor k_horm k_horg k_planes k_bm k_bmg k_bndm k_bndmx k_so k_kmp k_packed k_util k_tedit launch; do
+for u in k_hor k_horm k_horg k_planes k_bm k_bmg k_bndm k_bndmx k_so k_kmp k_packed k_util k_tedit k_palignl launch; do
   /opt/rocm/bin/hipcc $FLAGS "$@" --offload-arch=gfx950 -c -o $T/$u.o $D/$u.hip &
 done
-for u in api match_calls align_calls; do
+for u in api match_calls align_calls palignl_calls; do
   /opt/rocm/bin/hipcc $FLAGS "$@" --offload-arch=gfx950 -c -o $T/$u.o $D/$u.cpp &
 done
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC "$@" -c -o $T/tables.o $D/tables.cpp &
